@@ -6,13 +6,20 @@
                                                             touches the GPU and relays rank 0's line as its last stdout line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W          (the same ranks started by torchrun: WORLD_SIZE is set, nothing is re-launched)
+    python bench.py ... --full                              (everything below that is not the headline figure)
+    python bench.py ... --dump-outputs DIR                  (DIR/z.npy, loss.npy, u_test.npy: what the timed path computed, float64)
+
+A plain run does only what `value` needs: set-up (points, assembly, Cholesky of Theta), W warm-up steps, K timed steps, the L2 errors,
+the outputs, the line.  Everything else -- the secondary workloads, CPU baselines and `parity`, the structured solve, warm
+re-measurements of the one-time phases with their rooflines, at N > 1 the replicas and the 1-GPU point -- runs only with --full
+(the --no-* options then switch legs of it off).
 
 `value` at N = 1 is measured on BASELINE config 2 (N_domain=4000, N_boundary=400: the configuration the metric is quoted on, it
 fits one GPU); with N > 1 ranks `value` is the SHARDED BASELINE config 5 (N_domain=16000, Theta of order 34000: panel-sharded
 Cholesky + column-sharded Gauss-Newton step over RCCL, strong scaling) -- `value_workload` ("c2" / "c5") says which, machine-readably,
 and a sharded run that does not complete leaves `value: null`, never another workload's figure.  Config 5 on ONE GPU (the 1-GPU
 point of that series) is in every N = 1 line under `sharded_config`; N independent config-2 replicas in every N > 1 line under
-`replicas_c2`.
+`replicas_c2` (both with --full).
 
 The LAST stdout line is compact (bench_line.py, ~5 KB: contract fields, roofline, cpu_baseline, parity, one small object per
 secondary workload); the full result object goes to bench_detail.json and stderr.
@@ -199,6 +206,20 @@ def emit(out):
     print(bench_line.compact(out), flush=True)
 
 
+def dump_outputs(outputs, d, cap_bytes=64 << 20):
+    """--dump-outputs DIR: one DIR/<name>.npy (float64) per array the timed path returned in its last step; the inputs are seeded, so two
+    builds run with the same arguments can be compared output for output.  At most cap_bytes in all."""
+    if not outputs:
+        raise RuntimeError('--dump-outputs: the timed path of this workload returned no outputs')
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > cap_bytes:
+        raise RuntimeError(f'--dump-outputs: {total} bytes of outputs, more than the cap of {cap_bytes}')
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f'{name}.npy'), a)
+
+
 class AbortWatch:
     """Keeps the primary result alive while the SECONDARY (sharded) run is in flight.
     * N > 1 ranks: a rank that fails in the middle of that run cannot tell peers that are blocked inside a collective -- they
@@ -295,6 +316,7 @@ def run_single(args, workload, comm=None, secondary=False, steps=None, warmup=No
     world = comm.world if comm is not None else 1
     rank = comm.rank if comm is not None else 0
     local = int(os.environ.get('LOCAL_RANK', '0')) if world > 1 else 0
+    full = getattr(args, 'full', True)                            # a plain run (no --full): no re-measurement after the timed steps
     torch.cuda.set_device(local)
     ctx = gpk.Context(local)
     Xd, Xb, f, g, z0 = synthetic_problem(Nd, Nb)
@@ -383,27 +405,28 @@ def run_single(args, workload, comm=None, secondary=False, steps=None, warmup=No
     # roofline fraction is about the kernel, so it is taken from launches issued AFTER the timed steps: 8 assemblies (mean launch duration; min and
     # median beside it) and 3 factorisations into a scratch matrix; the first-call figures stay in one_time_ms.
     asm_cold_ms, chol_cold_ms = asm_kernel_ms, chol_ms
-    T2 = ctx.empty(N, N)
-    ctx.prof_enable(True)
-    asm_warm = []
-    for _ in range(8):                                            # 8 launches, each alone on the chip (host round trip in between)
-        ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
-        ctx.synchronize()
-        asm_warm.append(ctx.prof_read_assembly())
-    ctx.prof_enable(False)
-    # ... and 8 calls back to back (point packing + evaluator each): the SUSTAINED write rate.  A launch that runs alone ends while up to
-    # 256 MB of its 8 N^2 bytes still sit in the Infinity Cache; behind another write stream it has to wait for that one's write-back
-    # (config 2: 0.088-0.100 ms alone, 0.113 ms in a row; at config 5, 9.2 GB, the two agree: 5.6 TB/s)
-    ctx.synchronize(); ctx.timer_start()
-    for _ in range(8):
-        ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
-    asm_row_ms = ctx.timer_stop() / 8.0
-    chol_warm = []
-    for _ in range(3):
-        ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
-        ctx.timer_start(); ctx.potrf(T2); chol_warm.append(ctx.timer_stop())
-    T2.free()
-    asm_kernel_ms, chol_ms = float(np.mean(asm_warm)), min(chol_warm)     # (assembly: the AVERAGE launch duration, as rocprofv3 --stats reports it)
+    if full:
+        T2 = ctx.empty(N, N)
+        ctx.prof_enable(True)
+        asm_warm = []
+        for _ in range(8):                                            # 8 launches, each alone on the chip (host round trip in between)
+            ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
+            ctx.synchronize()
+            asm_warm.append(ctx.prof_read_assembly())
+        ctx.prof_enable(False)
+        # ... and 8 calls back to back (point packing + evaluator each): the SUSTAINED write rate.  A launch that runs alone ends while up to
+        # 256 MB of its 8 N^2 bytes still sit in the Infinity Cache; behind another write stream it has to wait for that one's write-back
+        # (config 2: 0.088-0.100 ms alone, 0.113 ms in a row; at config 5, 9.2 GB, the two agree: 5.6 TB/s)
+        ctx.synchronize(); ctx.timer_start()
+        for _ in range(8):
+            ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
+        asm_row_ms = ctx.timer_stop() / 8.0
+        chol_warm = []
+        for _ in range(3):
+            ctx._chk(ctx.lib.gpk_assemble(ctx.h, 0, 0, kp, dXd.ptr, Nd, dXb.ptr, Nb, nugget, 2, T2.ptr, T2.ld, ratios))
+            ctx.timer_start(); ctx.potrf(T2); chol_warm.append(ctx.timer_stop())
+        T2.free()
+        asm_kernel_ms, chol_ms = float(np.mean(asm_warm)), min(chol_warm)     # (assembly: the AVERAGE launch duration, as rocprofv3 --stats reports it)
 
     # accuracy half of the metric
     sol = z.download()
@@ -495,24 +518,6 @@ def run_single(args, workload, comm=None, secondary=False, steps=None, warmup=No
                              'sum of the product launches per step; peak is the FULL chip although the launches only get '
                              'cus_available_to_kernel CUs when pipelined (the rest runs the Cholesky panel chain concurrently)',
                      'peak_source': 'datasheet fp64 matrix rate; v_mfma_f64_16x16x4_f64 issue-rate ubench on this chip ~74'},
-        'roofline_assembly': {'bound': 'hbm', 'kernel': 'assemble2_kernel<elliptic> (the Gram evaluator launch itself)',
-                              'achieved': 8.0 * N * N / (asm_kernel_ms * 1e-3) / 1e9,
-                              'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': 8.0 * N * N / (asm_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              'bytes_per_launch': 8.0 * N * N, 'kernel_ms': asm_kernel_ms, 'kernel_ms_min': min(asm_warm), 'kernel_ms_median': float(np.median(asm_warm)),
-                              'sustained_call_ms': asm_row_ms, 'sustained_gbs': 8.0 * N * N / (asm_row_ms * 1e-3) / 1e9,
-                              'kernel_ms_first_launches': asm_cold_ms, 'launches_timed': len(asm_warm),
-                              'store_policy': 'plain global_store_dwordx4 (A/B of nt / sc0 sc1 / sc0 sc1 nt: profiles/r06_assembly_store_ab.json -- nt is 15-20 % slower)',
-                              'call_ms': asm_ms, 'call_gbs': 8.0 * N * N / (asm_ms * 1e-3) / 1e9,
-                              'note': 'achieved = 8 N^2 bytes written / duration of the evaluator launch (HIP events around that launch on its '
-                                      'stream), MEAN over launches_timed launches issued one at a time after the timed steps (kernel_ms_min / _median beside it; sustained_gbs = 8 calls back to back incl. point packing; '
-                                      'kernel_ms_first_launches = the same at process start, clocks and pages cold); call_ms = the whole gpk_assemble call (point packing kernel + launch overheads) by events around the call'},
-        # the factorisation of Theta (north star: "MFMA fp64 utilisation for the factorisation"): N^3/3 flops are what a Cholesky
-        # executes (nothing structural to skip) over the whole gpk_potrf call -- panel kernels, rank-64 updates and the trailing
-        # GEMM updates together, HIP events on the handle's stream
-        'roofline_cholesky_theta': {'bound': 'mfma', 'kernel': 'gpk_potrf(Theta): potrf_panel_mfma_kernel chain + gemm_k64_kernel + gemm_f64_kernel<NT> trailing updates',
-                                    'achieved': N ** 3 / 3.0 / (chol_ms * 1e-3) / 1e12, 'peak': FP64_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                                    'frac': N ** 3 / 3.0 / (chol_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 'flops': N ** 3 / 3.0, 'ms': chol_ms,
-                                    'ms_median': float(np.median(chol_warm)), 'ms_before_the_timed_steps': chol_cold_ms, 'calls_timed': len(chol_warm)},
         'flops_counted_by_library': counted,
         'step_executed': {'flops_per_step': (trsm_flops or 0.0) + syrk_flops + (nz + 1) ** 3 / 3.0,
                           'tflops': ((trsm_flops or 0.0) + syrk_flops + (nz + 1) ** 3 / 3.0) * args.steps / elapsed / 1e12,
@@ -521,6 +526,27 @@ def run_single(args, workload, comm=None, secondary=False, steps=None, warmup=No
     }
     if out['roofline'] is None:                                   # substitution schedule (debug): the SYRK is the measured GEMM then
         out['roofline'] = out['roofline_syrk']
+    if full:                                                      # the warm re-measurements of the one-time phases (above)
+        out['roofline_assembly'] = {'bound': 'hbm', 'kernel': 'assemble2_kernel<elliptic> (the Gram evaluator launch itself)',
+                                    'achieved': 8.0 * N * N / (asm_kernel_ms * 1e-3) / 1e9,
+                                    'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': 8.0 * N * N / (asm_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    'bytes_per_launch': 8.0 * N * N, 'kernel_ms': asm_kernel_ms, 'kernel_ms_min': min(asm_warm), 'kernel_ms_median': float(np.median(asm_warm)),
+                                    'sustained_call_ms': asm_row_ms, 'sustained_gbs': 8.0 * N * N / (asm_row_ms * 1e-3) / 1e9,
+                                    'kernel_ms_first_launches': asm_cold_ms, 'launches_timed': len(asm_warm),
+                                    'store_policy': 'plain global_store_dwordx4 (A/B of nt / sc0 sc1 / sc0 sc1 nt: profiles/r06_assembly_store_ab.json -- nt is 15-20 % slower)',
+                                    'call_ms': asm_ms, 'call_gbs': 8.0 * N * N / (asm_ms * 1e-3) / 1e9,
+                                    'note': 'achieved = 8 N^2 bytes written / duration of the evaluator launch (HIP events around that launch on its '
+                                            'stream), MEAN over launches_timed launches issued one at a time after the timed steps (kernel_ms_min / _median beside it; sustained_gbs = 8 calls back to back incl. point packing; '
+                                            'kernel_ms_first_launches = the same at process start, clocks and pages cold); call_ms = the whole gpk_assemble call (point packing kernel + launch overheads) by events around the call'}
+        # the factorisation of Theta (north star: "MFMA fp64 utilisation for the factorisation"): N^3/3 flops are what a Cholesky
+        # executes (nothing structural to skip) over the whole gpk_potrf call -- panel kernels, rank-64 updates and the trailing
+        # GEMM updates together, HIP events on the handle's stream
+        out['roofline_cholesky_theta'] = {'bound': 'mfma', 'kernel': 'gpk_potrf(Theta): potrf_panel_mfma_kernel chain + gemm_k64_kernel + gemm_f64_kernel<NT> trailing updates',
+                                          'achieved': N ** 3 / 3.0 / (chol_ms * 1e-3) / 1e12, 'peak': FP64_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                                          'frac': N ** 3 / 3.0 / (chol_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 'flops': N ** 3 / 3.0, 'ms': chol_ms,
+                                          'ms_median': float(np.median(chol_warm)), 'ms_before_the_timed_steps': chol_cold_ms, 'calls_timed': len(chol_warm)}
+    if not secondary:                                             # what a caller of the timed path receives (--dump-outputs)
+        out['_outputs'] = {'z': sol, 'loss': np.array(losses, dtype=np.float64), 'u_test': ext}
     if not args.no_structured and world == 1 and not secondary:
         out['structured_step'] = structured_step(args, ctx, gpk, prob, T, Nd, Nb, f, g, z0, sol, Xd)
     if not args.no_cpu_baseline and world == 1:
@@ -857,6 +883,8 @@ def run_system(args, workload, steps=None, warmup=None):
                              'frac_of_peak': executed * steps / elapsed / 1e12 / FP64_MFMA_PEAK_TFLOPS,
                              'cholesky_H_update_flops_counted': upd_fl,
                              'note': 'solve + product (counted) + (n_z+1)^3/3 for the Cholesky of H, over wall time per step'}}
+    # what a caller of the timed path receives (--dump-outputs)
+    out['_outputs'] = dict({'z': sol, 'loss': np.array(losses, dtype=np.float64)}, **({'u_test': ext} if workload == 'c3' else {'u_test': eu, 'a_test': ea}))
     if not args.no_structured:
         # OPTIONAL structured solve of this system (round 6, gpk_gn_structured_prepare; GPK_STRUCTURED=1 in the drivers): A(z) = A1 diag(d(z)) + A2,
         # W1 = L^{-1}A1 and W2 = L^{-1}A2 once per factor, the step forms L^{-1}A(z) in one memory-bound pass and solves only the F column.
@@ -1153,7 +1181,7 @@ def run_sharded(args, workload, steps=None, warmup=None, solo=False):
     # the Cholesky of the bordered matrix alone (one rank only: an input of the multi-GPU model, bench_model.py): its time does not depend
     # on the data, so it is taken on the identity of that order in Hb (free after the last step)
     potrf_hb_ms = None
-    if world == 1:
+    if world == 1 and getattr(args, 'full', True):
         Hb.zero_(); Hb.diagonal().fill_(1.0)
         ops.potrf(Hb, 0, nz + 1)                                  # (warm)
         Hb.zero_(); Hb.diagonal().fill_(1.0)
@@ -1213,6 +1241,7 @@ def run_sharded(args, workload, steps=None, warmup=None, solo=False):
                                         'frac': N ** 3 / 3.0 / (chol_ms * 1e-3) / 1e12 / (FP64_MFMA_PEAK_TFLOPS * world), 'ms': chol_ms},
             'cpu_baseline': None, 'parity': None,
         }
+        out['_outputs'] = {'z': sol, 'loss': np.array(losses, dtype=np.float64), 'u_test': ext.cpu().numpy()}   # (--dump-outputs)
         # CPU oracle on the device's factor (B2 only: the reference operation sequence needs minutes at order 34000), `parity` beside it
         need_gb = 3.2 * 8.0 * N * N / 1e9 + 4.0 * 8.0 * N * (nz + 1) / 1e9
         if not args.no_cpu_baseline and not args.no_sharded_parity and not solo:   # (solo = the 1-GPU point inside an N-rank job: the N-rank run carries the parity)
@@ -1247,7 +1276,18 @@ def main():
     ap.add_argument('--no-sharded-parity', action='store_true', help='skip the CPU oracle step (about a minute, ~40 GB of host memory) behind sharded_config.parity')
     ap.add_argument('--no-replicas', action='store_true', help='N > 1: skip the secondary measurement of N independent config-2 replicas')
     ap.add_argument('--sharded-path', action='store_true', help='use the multi-rank schedule for the primary workload')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure: secondary workloads (n10k, c3, c4, sharded_config; N > 1: replicas_c2 and the '
+                         '1-GPU point), CPU baselines and parity, the structured solve, warm re-measurements of the one-time phases and their '
+                         'rooflines; the --no-* options above switch legs of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float64): the iterate z, the loss '
+                         'history, the solution extended to the test grid')
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, write the outputs, print the line -- nothing else
+        for k in ('no_cpu_baseline', 'no_structured', 'no_sharded_config', 'no_n10k', 'no_c3c4', 'no_sharded_parity', 'no_replicas'):
+            setattr(args, k, True)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # the bare command `python3 bench.py --gpus N ...`: start the N ranks ourselves (bench_launch.py).  This process has made
         # no GPU call and makes none: the ranks are fresh child processes, rank 0's compact line is relayed as our last stdout line.
@@ -1301,6 +1341,13 @@ def main():
         return dict({'metric': 'Gauss-Newton steps/sec + L2 error at N_domain points', 'n_gpus': n_gpus, 'higher_is_better': True,
                      'scaling': scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic'}, **obj)
 
+    def take_outputs(o):
+        """the arrays the timed path computed in its last step (rank 0's result only): off the result object, and written at once
+        (--dump-outputs) -- before any secondary run that could still end the process"""
+        arrays = o.pop('_outputs', None) if o is not None else None
+        if o is not None and args.dump_outputs:
+            dump_outputs(arrays, args.dump_outputs)
+
     if world > 1 and args.workload in ('auto', 'c5') and not args.sharded_path:
         # ---- N > 1 ranks: `value` IS the sharded BASELINE config 5 (the north star's scaling series: fixed total work, strong scaling).
         # The same job also times config 5 on rank 0 ALONE (vs_1gpu: a self-contained strong-scaling point per job) and, as a secondary
@@ -1329,7 +1376,8 @@ def main():
         solo = None
         try:
             out = run_sharded(args, 'c5')
-            if rank == 0:
+            take_outputs(out)
+            if rank == 0 and args.full:
                 try:
                     solo = run_sharded(args, 'c5', steps=min(args.steps, 3), warmup=1, solo=True)
                 except Exception as e:                            # noqa: BLE001 -- reported
@@ -1339,24 +1387,25 @@ def main():
             watch.fail(f'rank {rank}: {type(e).__name__}: {e}')   # does not return (peers may be blocked in a collective)
         watch.stop()
         if out is not None:
-            if solo and 'value' in solo:
-                out['one_gpu_same_job'] = pick(solo)
-                out['vs_1gpu'] = out['value'] / solo['value']
-                out['parallel_efficiency'] = out['vs_1gpu'] / world
-            else:
-                out['one_gpu_same_job'] = solo
-                out['vs_1gpu'] = None
-            # the host model beside the measurement (bench_model.py): what this rank count should have taken, per choice
-            out['predicted'] = prediction(solo, out.get('preflight'), tuple(sorted({2, 4, 8, world})))
-            mine = out['predicted'].get(str(world)) if isinstance(out['predicted'], dict) else None
-            if isinstance(mine, dict):
-                out['predicted_vs_1gpu'] = mine.get('predicted_vs_1gpu')
-                mp = out.get('mode_probe')
-                if isinstance(mp, dict):
-                    for key, src in (('cholesky_theta_ms', 'cholesky_theta_ms'), ('step_ms_by_cholesky_of_Hb', 'cholesky_of_Hb_ms'),
-                                     ('step_ms_by_exchange_of_S', 'exchange_of_S_ms')):
-                        if isinstance(mp.get(key), dict):
-                            mp[key]['expected_ms'] = mine.get(src)
+            if args.full:                                     # the 1-GPU point of the same job and the host model beside it
+                if solo and 'value' in solo:
+                    out['one_gpu_same_job'] = pick(solo)
+                    out['vs_1gpu'] = out['value'] / solo['value']
+                    out['parallel_efficiency'] = out['vs_1gpu'] / world
+                else:
+                    out['one_gpu_same_job'] = solo
+                    out['vs_1gpu'] = None
+                # the host model beside the measurement (bench_model.py): what this rank count should have taken, per choice
+                out['predicted'] = prediction(solo, out.get('preflight'), tuple(sorted({2, 4, 8, world})))
+                mine = out['predicted'].get(str(world)) if isinstance(out['predicted'], dict) else None
+                if isinstance(mine, dict):
+                    out['predicted_vs_1gpu'] = mine.get('predicted_vs_1gpu')
+                    mp = out.get('mode_probe')
+                    if isinstance(mp, dict):
+                        for key, src in (('cholesky_theta_ms', 'cholesky_theta_ms'), ('step_ms_by_cholesky_of_Hb', 'cholesky_of_Hb_ms'),
+                                         ('step_ms_by_exchange_of_S', 'exchange_of_S_ms')):
+                            if isinstance(mp.get(key), dict):
+                                mp[key]['expected_ms'] = mine.get(src)
             out['value_workload'] = 'c5'
             out['scaling_series'] = ('BASELINE config 5, strong scaling: this line\'s `value` at n_gpus > 1; at n_gpus = 1 the default line reports config 2 as '
                                      '`value` (the configuration the metric is quoted on, it fits one GPU) and config 5 on one GPU under `sharded_config`')
@@ -1365,15 +1414,18 @@ def main():
     elif args.sharded_path or args.workload == 'c5':
         out = run_sharded(args, args.workload if args.workload != 'auto' else 'c2')
         if out is not None:
+            take_outputs(out)
             out['value_workload'] = args.workload if args.workload != 'auto' else 'c2'
     elif args.workload in ('c3', 'c4'):
         out = contract_line(run_system(args, args.workload), 1, 'weak')
+        take_outputs(out)
         out['value_workload'] = args.workload
     else:
         workload = args.workload if args.workload != 'auto' else 'c2'
         from gpk.sharded import Comm
         out = run_single(args, workload, Comm() if world > 1 else None)
         if out is not None:
+            take_outputs(out)
             out['value_workload'] = workload
         # GPK_BENCH_SECONDARY_CPU=0: the CPU oracle legs (cpu_baseline + parity) of the SECONDARY workloads are skipped -- the
         # primary workload keeps its own; used by the -m gpu test of the default command, which checks the line, not the CPU
@@ -1392,6 +1444,7 @@ def main():
             for name in ('c3', 'c4'):                             # BASELINE configs 3 and 4 under the same clock
                 try:
                     out[name] = run_system(sec_args, name)
+                    out[name].pop('_outputs', None)
                 except Exception as e:                            # noqa: BLE001 -- reported, the primary value survives
                     out[name] = {'error': f'{type(e).__name__}: {e}'}
         if args.workload == 'auto' and not args.no_sharded_config:

@@ -247,12 +247,35 @@ def make_solves(solver_mod):
     print('solves.npz', len(out))
 
 
+def make_modules():
+    """Outputs of the two reference modules that need numpy / scipy only, run directly (no stand-in): the random and grid samplers
+    (seed 5) and the Cole-Hopf Eikonal truth -> reference_modules.npz (tests/test_host_api.py, tests/test_product_truth_solvers.py)."""
+    sp = load_reference_sampler()
+    spec = importlib.util.spec_from_file_location('ref_cole_hopf', os.path.join(REF, 'reference_solver', 'Cole_Hopf_for_Eikonal.py'))
+    ch = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ch)
+    out = {}
+    for nd, nb, td in [(17, 9, False), (23, 11, True), (900, 124, False)]:
+        dom = np.array([[0, 1], [-1, 1]]) if td else np.array([[0, 1], [0, 1]])
+        name = f'{"time" if td else "static"}_{nd}_{nb}'
+        np.random.seed(5)
+        out[f'rdm_{name}__Xd'], out[f'rdm_{name}__Xb'] = sp.sampled_pts_rdm(nd, nb, dom, time_dependent=td)
+        out[f'grid_{name}__Xd'], out[f'grid_{name}__Xb'] = sp.sampled_pts_grid(nd, nb, dom, time_dependent=td)
+    for n, eps in ((58, 0.1), (40, 1e-2)):
+        for key, arr in zip(('XX', 'YY', 'u'), ch.solve_Eikonal(n, eps)):
+            out[f'cole_hopf_{n}_{eps:g}__{key}'] = np.asarray(arr)
+    np.savez_compressed(os.path.join(GOLDEN, 'reference_modules.npz'), **out)
+    print('reference_modules.npz', len(out))
+
+
 if __name__ == '__main__':
     if not os.path.isdir(REF):
         sys.exit('needs /root/reference (authoring container)')
-    which = set(sys.argv[1:]) or {'sampling', 'theta', 'solves'}
+    which = set(sys.argv[1:]) or {'sampling', 'theta', 'solves', 'modules'}
     if 'sampling' in which:
         make_sampling()
+    if 'modules' in which:
+        make_modules()
     if which & {'theta', 'solves'}:
         Gram, PDEs, IP, solver_mod = import_reference_src()
         if 'theta' in which:

@@ -46,7 +46,7 @@ def test_two_rank_flow_prints_one_line(tmp_path):
             return dict({{k: 1 for k in ('unit', 'steps', 'warmup', 'ms_per_step', 'config', 'l2_error', 'f1_tflops', 'one_time_ms', 'roofline')}},
                         metric='m', value=3.0, n_gpus=2, scaling='strong')
         bench.run_single, bench.run_sharded = fake_single, fake_sharded
-        sys.argv = ['bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1']
+        sys.argv = ['bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1', '--full']
         bench.main()
     '''))
     port = _free_port()
@@ -91,7 +91,7 @@ def test_two_rank_flow_survives_a_one_sided_failure(tmp_path):
             dist.barrier()                                       # rank 0 waits for a peer that never arrives
             return None
         bench.run_single, bench.run_sharded = fake_single, fake_sharded
-        sys.argv = ['bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1']
+        sys.argv = ['bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1', '--full']
         bench.main()
     '''))
     port = _free_port()
@@ -141,7 +141,7 @@ def test_hanging_sharded_run_is_abandoned_at_the_deadline(tmp_path):
         def hang(args, workload, steps=None, warmup=None, solo=False):
             time.sleep(3600)
         bench.run_sharded = hang
-        sys.argv = ['bench.py', '--steps', '4', '--warmup', '1', '--no-n10k', '--no-c3c4']
+        sys.argv = ['bench.py', '--steps', '4', '--warmup', '1', '--no-n10k', '--no-c3c4', '--full']
         bench.main()
     '''))
     env = dict(os.environ, GPK_SHARDED_TIMEOUT='2', GPK_BENCH_DETAIL_DIR=str(tmp_path))
@@ -188,7 +188,7 @@ def test_bare_command_launches_its_own_ranks(tmp_path):
     stubs.write_text(STUBS)
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GPK_BENCH_BACKEND='gloo', GPK_BENCH_COMM='staged', GPK_BENCH_STUBS=str(stubs), GPK_BENCH_DETAIL_DIR=str(tmp_path))
-    r = _bare(['--gpus', '2', '--steps', '1', '--warmup', '0'], env)
+    r = _bare(['--gpus', '2', '--steps', '1', '--warmup', '0', '--full'], env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1 and r.stdout.rstrip().splitlines()[-1] == lines[0]      # ONE line, and it is the last thing on stdout
@@ -216,9 +216,44 @@ def test_bare_command_fails_loudly_without_gpus(tmp_path):
     env.update(GPK_BENCH_DETAIL_DIR=str(tmp_path))
     r = _bare(['--gpus', '2', '--steps', '1', '--warmup', '0'], dict(env, GPK_BENCH_BACKEND='nccl'))
     assert r.returncode == 2 and 'needs 2 visible GPUs' in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith('{')]
-    r = _bare(['--gpus', '2', '--steps', '1', '--warmup', '0', '--no-cpu-baseline'], dict(env, GPK_BENCH_BACKEND='gloo', GPK_BENCH_PEER_GRACE='20'))
+    r = _bare(['--gpus', '2', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--full'],
+              dict(env, GPK_BENCH_BACKEND='gloo', GPK_BENCH_PEER_GRACE='20'))
     assert r.returncode != 0 and 'rank exit codes' in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith('{')]
+
+
+PLAIN_STUBS = '''
+def run_single(args, workload, comm=None, secondary=False, steps=None, warmup=None):
+    assert workload == 'c2' and comm is None and not secondary and steps is None and warmup is None
+    assert args.no_cpu_baseline and args.no_structured and not args.full
+    return {'metric': 'm', 'value': 5.0, 'unit': 'GN steps/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 200.0,
+            'higher_is_better': True, 'dtype': 'f64', '_outputs': {'z': np.arange(4.0), 'loss': np.array([3.0, 2.0, 1.0], dtype=np.float32)}}
+def run_system(*a, **kw):
+    raise AssertionError('a secondary workload in a plain run')
+def run_sharded(*a, **kw):
+    raise AssertionError('the sharded configuration in a plain run')
+'''
+
+
+def test_plain_command_runs_the_headline_only_and_dumps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 0 --dump-outputs DIR` without --full: the primary workload alone (no secondary workload, no CPU
+    leg), the timed path's arrays as DIR/<name>.npy in float64, the line without the secondary objects"""
+    stubs = tmp_path / 'stubs.py'
+    stubs.write_text(PLAIN_STUBS)
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'GPK_FORCE_PG')}
+    env.update(GPK_BENCH_STUBS=str(stubs), GPK_BENCH_DETAIL_DIR=str(tmp_path))
+    r = _bare(['--gpus', '1', '--steps', '2', '--warmup', '0', '--dump-outputs', str(tmp_path / 'out')], env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['value'] == 5.0 and d['steps'] == 2 and d['ms_per_step'] == 200.0 and d['value_workload'] == 'c2'
+    assert not any(k in d for k in ('n10k', 'c3', 'c4', 'sharded_config', '_outputs'))
+    assert '_outputs' not in json.load(open(tmp_path / 'bench_detail.json'))
+    import numpy as np
+    z, loss = np.load(tmp_path / 'out' / 'z.npy'), np.load(tmp_path / 'out' / 'loss.npy')
+    assert z.dtype == np.float64 and loss.dtype == np.float64
+    assert np.array_equal(z, np.arange(4.0)) and np.array_equal(loss, [3.0, 2.0, 1.0])
 
 
 def test_launcher_relays_worst_exit_code_and_ends_stuck_peers(tmp_path):

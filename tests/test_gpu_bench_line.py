@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,10 +32,10 @@ def _run(*flags, env_extra=None, tmp=None):
 
 
 def test_default_command_of_the_driver_prints_a_compact_parseable_line():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- exactly what the driver runs (the CPU oracle legs of the SECONDARY workloads
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the plain command plus every other leg (the CPU oracle legs of the SECONDARY workloads
     switched off, GPK_BENCH_SECONDARY_CPU=0: they are minutes of host time and are not what this test is about; the primary workload keeps
     its cpu_baseline and parity): ONE line, under the cap, roofline / cpu_baseline / parity at the top level, the timed sequence named."""
-    d, full, out = _run('--gpus', '1', '--steps', '20', '--warmup', '5', env_extra={'GPK_BENCH_SECONDARY_CPU': '0'})
+    d, full, out = _run('--gpus', '1', '--steps', '20', '--warmup', '5', '--full', env_extra={'GPK_BENCH_SECONDARY_CPU': '0'})
     tail = out[-8192:]                                             # what survives in the driver's record
     assert tail.rstrip('\n').splitlines()[-1].startswith('{"metric"') and json.loads(tail.rstrip('\n').splitlines()[-1]) == d
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config'):
@@ -55,8 +56,38 @@ def test_default_command_of_the_driver_prints_a_compact_parseable_line():
     assert d['l2_error']['pts_L2_err'] < 1e-6 and d['l2_error']['test_L2_err'] < 1e-6
 
 
+def test_plain_command_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` (no --full): the contract fields and nothing of the secondary
+    legs; --steps is the number of timed steps; the outputs of the timed path (iterate, loss history, extension to the test grid) come out
+    as float64 and are bit for bit the same in a second run with the same arguments (seeded inputs, deterministic step)."""
+    runs = []
+    for i in range(2):
+        d, full, _ = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / f'out{i}'), tmp=str(tmp_path))
+        runs.append((d, full, {n: np.load(tmp_path / f'out{i}' / f'{n}.npy') for n in ('z', 'loss', 'u_test')}))
+    for d, full, o in runs:
+        assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['value_workload'] == 'c2' and d['dtype'] == 'f64'
+        assert d['unit'] == 'GN steps/s' and d['higher_is_better'] is True and d['value'] == pytest.approx(1e3 / d['ms_per_step'], rel=1e-4)
+        for k in ('n10k', 'c3', 'c4', 'sharded_config', 'cpu_baseline', 'parity', 'structured_step', 'roofline_assembly', 'roofline_cholesky_theta'):
+            assert full.get(k) is None, k
+        assert full['l2_error']['gn_steps_run'] == 4
+        assert all(a.dtype == np.float64 for a in o.values())
+        assert o['z'].shape == (4000,) and o['u_test'].shape == (3600,) and o['loss'].shape == (5,)      # J(z0) .. J(z4)
+        assert o['loss'][-1] < o['loss'][0] and o['loss'][-1] == pytest.approx(full['l2_error']['loss_last'], rel=1e-12)
+        assert np.sqrt(np.mean((bench_u_true(4000) - o['z']) ** 2)) == pytest.approx(full['l2_error']['pts_L2_err'], rel=1e-9)
+    for n in ('z', 'loss', 'u_test'):
+        assert np.array_equal(runs[0][2][n], runs[1][2][n]), n
+
+
+def bench_u_true(Nd):
+    """u* at the benchmark's collocation points (bench.synthetic_problem: the same seed and sampler)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    Xd = bench.synthetic_problem(Nd, 400)[0]
+    return bench.u_true(Xd[:, 0], Xd[:, 1])
+
+
 def test_config1_line_has_the_contract_fields_and_parity():
-    line, d, _ = _run('--workload', 'c1', '--steps', '4', '--warmup', '1', '--no-sharded-config', '--no-structured')
+    line, d, _ = _run('--workload', 'c1', '--steps', '4', '--warmup', '1', '--no-sharded-config', '--no-structured', '--full')
     assert line['value'] == pytest.approx(d['value'], rel=1e-5) and line['roofline']['traffic'] is None and line['parity']['ok'] is True
     assert line['value_workload'] == 'c1' and line['cpu_baseline']['kind'] == 'port'
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config'):
@@ -86,7 +117,7 @@ def test_bare_two_rank_command_on_one_gpu():
     on this 1-GPU box both ranks share the device (process group over gloo, the bound collectives staged through the host:
     GPK_BENCH_BACKEND=gloo GPK_BENCH_COMM=staged).  The line is the N > 1 line: `value` = the sharded BASELINE config 5 with the real
     kernels, the same job's 1-GPU point beside it, the preflight of the bound collectives."""
-    d, full, out = _run('--gpus', '2', '--steps', '1', '--warmup', '0', '--no-replicas',
+    d, full, out = _run('--gpus', '2', '--steps', '1', '--warmup', '0', '--no-replicas', '--full',
                         env_extra={'GPK_BENCH_BACKEND': 'gloo', 'GPK_BENCH_COMM': 'staged', 'GPK_SHARDED_TIMEOUT': '1200'})
     assert d['n_gpus'] == 2 and d['value_workload'] == 'c5' and d['scaling'] == 'strong' and d['data'] == 'synthetic'
     assert d['value'] > 0 and abs(d['value'] * d['ms_per_step'] / 1e3 - 1.0) < 1e-4

@@ -5,16 +5,15 @@ rank 2.  Until round 3 only their oracle twins (oracle/truth_solvers.py) were pi
     (reference_solver/Cole_Hopf_for_Eikonal.py:7-36; SURVEY 8f);
   * both product modules against the oracle twins (independently written from the same reference lines) on several sizes,
     coefficient fields and right-hand sides -- agreement to solver round-off;
-  * when /root/reference is mounted (authoring container): the reference's Cole-Hopf module itself, imported and run (it needs
-    numpy/scipy only; FD_for_Darcy_flow.py imports jax.vmap and cannot be imported here -- its oracle twin stands in).
+  * the stored output of the reference's Cole-Hopf module itself (tests/golden/reference_modules.npz; it needs numpy/scipy only;
+    FD_for_Darcy_flow.py imports jax.vmap and cannot be run by the fixture generator -- its oracle twin stands in).
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE
+from conftest import GOLDEN
 from oracle import truth_solvers as TS
 
 
@@ -51,18 +50,17 @@ def test_product_fd_darcy_against_twin():
     assert u.max() == pytest.approx(0.0736713, rel=2e-3)                         # max of the torsion function of the unit square
 
 
-@pytest.mark.reference
 def test_product_cole_hopf_against_the_reference_module():
-    spec = importlib.util.spec_from_file_location('ref_cole_hopf', os.path.join(REFERENCE, 'reference_solver', 'Cole_Hopf_for_Eikonal.py'))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """the reference's Cole-Hopf module's own output (tests/golden/reference_modules.npz, written by running it: tests/golden/gen/
+    make_fixtures.py modules) against the product's"""
     from reference_solver.Cole_Hopf_for_Eikonal import solve_Eikonal
+    d = np.load(os.path.join(GOLDEN, 'reference_modules.npz'))
     for n, eps in ((58, 0.1), (40, 1e-2)):
-        r = ref.solve_Eikonal(n, eps)
+        r = [d[f'cole_hopf_{n}_{eps:g}__{k}'] for k in ('XX', 'YY', 'u')]
         p = solve_Eikonal(n, eps)
         for a, b in zip(r, p):
             np.testing.assert_allclose(np.asarray(b), np.asarray(a), rtol=1e-10, atol=1e-13)
-    assert np.asarray(ref.solve_Eikonal(58, 0.1)[2]).max() == pytest.approx(0.366745974372574, rel=1e-12)
+    assert d['cole_hopf_58_0.1__u'].max() == pytest.approx(0.366745974372574, rel=1e-12)
 
 
 def test_callback_errors_are_not_swallowed():

@@ -9,7 +9,7 @@ case $wl in
 esac
 for v in "$@"; do
   for rep in 1 2; do
-  GPK_DEBUG_SET="$v" GPK_BENCH_DETAIL_DIR=/tmp timeout 300 python3 bench.py --steps 8 --warmup 3 $FLAGS 2>/dev/null | python3 -c "
+  GPK_DEBUG_SET="$v" GPK_BENCH_DETAIL_DIR=/tmp timeout 300 python3 bench.py --steps 8 --warmup 3 --full $FLAGS 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$wl [$v]', round(d['value'],2), 'ms/step', round(d['ms_per_step'],3), d.get('phases_ms'), {k: (round(v, 3) if isinstance(v, float) else v) for k, v in (d.get('one_time_ms') or {}).items()}, flush=True)"
   done

@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/traffic
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp GPK_BENCH_DETAIL_DIR=/tmp
-ONE="--no-sharded-config --no-cpu-baseline --no-structured --no-n10k --no-c3c4"
+ONE="--full --no-sharded-config --no-cpu-baseline --no-structured --no-n10k --no-c3c4"
 i=0
 for v in "$@"; do
     d=$OUT/v$i; mkdir -p $d; echo "$v" > $d/variant.txt
