@@ -37,6 +37,20 @@ int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, const doubl
  * csrc/gpk_gemm_dma_probe.hip, tools/gemm_dma_probe.py. */
 int gpk_debug_gemm_dma(gpk_handle h, int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc);
 
+/* ---- the leading-zero ("staircase") state of a handle, for kernel-level tests of its consumers (csrc/dev/gpk_gn_dev_abi.inc) ---- */
+/* puts a leading-zero state on h as gpk_gn_step / gpk_mg_gn_step do while they run: closed form of slope 1/lead_div (nseg = 0), or a
+ * piecewise profile of nseg <= 4 segments (c1, a, b, sd: nseg ints each, see GpkStair in csrc/gpk_common.h) whose column `base` is
+ * column 0 of the operands; gpk_gemm_lz, gpk_trsm_lz and gpk_trsm_dinv(lead > 0) then consume it.  nseg = 0, lead_div = 1 resets it.
+ * gpk_trsm_dinv moves the product frame while it runs: set the profile again before the next call. */
+int gpk_debug_set_profile(gpk_handle h, int lead_div, int nseg, const int* c1, const int* a, const int* b, const int* sd, int base);
+/* C <- alpha A^T A + beta C on the lower tiles only, A (k x n) with leading zeros (lead, or the profile of gpk_debug_set_profile):
+ * the product that forms Hb = S^T S inside gpk_gn_step */
+int gpk_debug_syrk_lz(gpk_handle h, int n, int k, double alpha, const double* A, int lda, double beta, double* C, int ldc, int lead);
+/* first_row(c) for the n_z columns of [A(z) | F] under the layout gpk_gn_step enters for host_prob -> out_u; Darcy: out_a (may be
+ * null) the a-part's closed form on the columns [N_d, 4 N_d), 3 N_d elsewhere.  Returns the layout (1 elliptic systems, 2 Eikonal,
+ * 3 Burgers, 4 Darcy); a problem on the dense schedule is refused. */
+int gpk_debug_first_rows(gpk_handle h, const gpk_gn_problem* host_prob, int* out_u, int* out_a);
+
 #ifdef __cplusplus
 }
 #endif

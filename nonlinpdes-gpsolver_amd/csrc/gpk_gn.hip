@@ -1061,3 +1061,7 @@ int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, cons
     return 0;
 }
 
+
+#ifdef GPK_DEV
+#include "dev/gpk_gn_dev_abi.inc"        // gpk_debug_set_profile, gpk_debug_syrk_lz, gpk_debug_first_rows (include/gpk_dev.h): development build only
+#endif

@@ -121,6 +121,9 @@ DEV_PROTOTYPES = {
     'gpk_ubench_cu_census': (_i, [_vp, _i, _i, _i, _pi]),
     'gpk_debug_gemm_dma': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i]),
     'gpk_debug_overlap_probe': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _pd]),
+    'gpk_debug_set_profile': (_i, [_vp, _i, _i, _pi, _pi, _pi, _pi, _i]),
+    'gpk_debug_syrk_lz': (_i, [_vp, _i, _i, _d, _vp, _i, _d, _vp, _i, _i]),
+    'gpk_debug_first_rows': (_i, [_vp, _pp, _pi, _pi]),
 }
 
 _lib = None
