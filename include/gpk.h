@@ -93,6 +93,27 @@ int gpk_assemble_test(gpk_handle h, int layout, int kernel, const double* host_k
 int gpk_extend(gpk_handle h, int layout, int kernel, const double* host_kparams,
                const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
                const double* coeff, double* out);
+/* Derivatives of the extension at test points, matrix-free: the rows of Theta_test with the row functional delta replaced by each
+ * requested functional, times coeff = Theta^{-1} sol_vec (gpk_potrs, as for gpk_extend).  fmask: GPK_FN_* bits;
+ * out is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.
+ * The reduction order is fixed: a repeated call gives bit-identical output.  No reference call site (the reference has no derivative
+ * extension; it is built from the kernel derivatives of src/kernels.py the Gram assembly already uses). */
+/* row functionals of the extension (bit mask); for Burgers axis 1 is t, axis 2 is x */
+enum { GPK_FN_VALUE = 1, GPK_FN_D1 = 2, GPK_FN_D2 = 4, GPK_FN_D2D2 = 8, GPK_FN_LAPLACIAN = 16 };
+int gpk_extend_functionals(gpk_handle h, int layout, int kernel, const double* host_kparams,
+                           const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
+                           const double* coeff, int fmask, double* out, int ldo);
+/* Pointwise PDE residual from rows of gpk_extend_functionals: out[t] = r(x_t), rhs[t] = f(x_t).  system = GPK_GN_*.
+ *   fields_u (4 rows, ld ldu >= Nt): value, d1, d2, then d2d2 (BURGERS) or laplacian (all others);
+ *   fields_a (3 rows, ld lda >= Nt): value, d1, d2 of the log-permeability a -- DARCY only, may be NULL otherwise;
+ *   host_params3: the equation's Gauss-Newton parameters (alpha, m) / (alpha, nu) / (eps); not read for DARCY (may be NULL then).
+ * The relations are those the Gauss-Newton systems eliminate (the sol_vec of src/PDEs.py:132-135,338-343,488-498; IP.py:176-186):
+ *   ELLIPTIC(_RELAXED)  r = -Delta u + alpha u^m - f        (v1 = alpha v0^m - f, src/PDEs.py:132)
+ *   BURGERS (t, x)      r = u_t + alpha u u_x - nu u_xx - f   (u_t = nu v3 + f - alpha v0 v2, src/PDEs.py:341)
+ *   EIKONAL             r = |grad u|^2 - f^2 - eps Delta u    (v3 = -(f^2 - v1^2 - v2^2)/eps, src/PDEs.py:491)
+ *   DARCY               r = -e^a (Delta u + grad a . grad u) - f   (v3 = -v1 w1 - v2 w2 - f e^{-w0}, src/InverseProblems.py:185) */
+int gpk_pde_residual(gpk_handle h, int system, const double* host_params3, int Nt,
+                     const double* fields_u, int ldu, const double* fields_a, int lda, const double* rhs, double* out);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the
  * device (the extension already is); one pass, fixed summation order.  Synchronises. */

@@ -25,6 +25,8 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     # type=bool as in the reference: any non-empty string is True; pass --show_figure "" to disable
     parser.add_argument("--print_hist", type=bool, default=True)
     parser.add_argument("--show_figure", type=bool, default=True)
+    # opt-in: also print the PDE residual of the solution on the test grid (no truth solution needed)
+    parser.add_argument("--test_residual", type=bool, default=False)
 
 
 def figures_enabled(cfg):
@@ -83,3 +85,9 @@ def report_test_error(solver, show, XX, YY, X_test, truth):
     solver.get_test_error(truth)
     if show:
         solver.contour_of_test_err(XX, YY)
+
+
+def report_test_residual(cfg, solver, X_test):
+    """--test_residual: the residual of the equation on the driver's test grid (solver_GP.test_residual)"""
+    if cfg.test_residual:
+        solver.test_residual(X_test)

@@ -234,6 +234,125 @@ __global__ __launch_bounds__(256) void extend_kernel(AsmArgs g) {
     if (threadIdx.x == 0) g.out[t] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- multi-functional extension (DESIGN.md §K "Row functionals of the extension") ------------------------------------------------
+// out[k][t] = sum_b sum_q pair_coeff<F_k, f[b]>(h(p1,d1), h(p2,d2)) kappa(d) c[off_b + q], d = x_t - y_q, F_k over the functionals of
+// MASK (bit F = functional F: delta, d1, d2, d2^2, Laplacian; the GPK_FN_* bits of gpk.h).  Every row functional has per-axis order
+// <= 2 and so has every column functional: the pair needs h0..h4 only, and ONE exp + one pair of Hermite evaluations feeds all of them.
+// Mapping: a workgroup owns FN_TT test points (wave-uniform: scalar loads) and its 256 lanes stride over the column points as in
+// extend_kernel; each column point's coordinates and its nb coefficient slices are loaded once and serve all FN_TT test points, and each
+// lane keeps FN_TT x popcount(MASK) accumulators.  Reduction: wave shuffles, then LDS across the 4 waves, in a fixed order (no atomics).
+constexpr int FN_TT = 4;                  // test points per workgroup
+
+struct FnArgs {
+    const double* px; const double* py;   // SoA column points (fill_common)
+    int M;
+    double p1, p2;
+    int off[4]; int size[4];
+    const double* tx; int Nt;
+    const double* coeff;
+    double* out; long ldo;
+};
+
+__host__ __device__ constexpr int fn_popc(int m) { return m ? (m & 1) + fn_popc(m >> 1) : 0; }
+// output row of functional F under MASK: the number of set bits below bit F
+__host__ __device__ constexpr int fn_row(int mask, int f) { return fn_popc(mask & ((1 << f) - 1)); }
+
+// sum_b pair_coeff<F, f[b]> c[b] (c[b] = 0 outside block b, as acc_test in extend_kernel)
+template <int L, int F>
+__device__ __forceinline__ double fn_sum(const double (&a)[5], const double (&b)[5], const double (&c)[4]) {
+    double v = pair_coeff<F, Lay<L>::f[0]>(a, b) * c[0];
+    if (Lay<L>::nb > 1) v += pair_coeff<F, Lay<L>::f[1]>(a, b) * c[1];
+    if (Lay<L>::nb > 2) v += pair_coeff<F, Lay<L>::f[2]>(a, b) * c[2];
+    if (Lay<L>::nb > 3) v += pair_coeff<F, Lay<L>::f[3]>(a, b) * c[3];
+    return v;
+}
+
+template <int L, int MASK, int F>
+__device__ __forceinline__ void fn_acc(double (&s)[fn_popc(MASK)], const double (&a)[5], const double (&b)[5], const double (&c)[4], double e) {
+    if ((MASK >> F) & 1) s[fn_row(MASK, F)] += fn_sum<L, F>(a, b, c) * e;
+}
+
+template <int L, int MASK>
+__global__ __launch_bounds__(256) void extend_fn_kernel(FnArgs g) {
+    constexpr int NF = fn_popc(MASK);
+    __shared__ double red[4][FN_TT * NF];
+    const int t0 = blockIdx.x * FN_TT;
+    double x1[FN_TT], x2[FN_TT];
+#pragma unroll
+    for (int i = 0; i < FN_TT; ++i) {                 // past the end: repeat the last point (computed, never stored)
+        const int t = min(t0 + i, g.Nt - 1);
+        x1[i] = g.tx[2 * t]; x2[i] = g.tx[2 * t + 1];
+    }
+    double s[FN_TT][NF];
+#pragma unroll
+    for (int i = 0; i < FN_TT; ++i)
+#pragma unroll
+        for (int k = 0; k < NF; ++k) s[i][k] = 0.0;
+    for (int q = threadIdx.x; q < g.M; q += 256) {
+        const double y1 = g.px[q], y2 = g.py[q];
+        double c[4];
+#pragma unroll
+        for (int bk = 0; bk < 4; ++bk) c[bk] = (bk < Lay<L>::nb && q < g.size[bk]) ? g.coeff[g.off[bk] + q] : 0.0;
+#pragma unroll
+        for (int i = 0; i < FN_TT; ++i) {
+            const double d1 = x1[i] - y1, d2 = x2[i] - y2;
+            const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
+            double a[5], b[5];
+            hermite(g.p1, d1, a);
+            hermite(g.p2, d2, b);
+            fn_acc<L, MASK, F_DELTA>(s[i], a, b, c, e);
+            fn_acc<L, MASK, F_D1>(s[i], a, b, c, e);
+            fn_acc<L, MASK, F_D2>(s[i], a, b, c, e);
+            fn_acc<L, MASK, F_DD2>(s[i], a, b, c, e);
+            fn_acc<L, MASK, F_LAP>(s[i], a, b, c, e);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < FN_TT; ++i)
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            double v = s[i][k];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i * NF + k] = v;
+        }
+    __syncthreads();
+    if (threadIdx.x < FN_TT * NF) {
+        const int i = threadIdx.x / NF, k = threadIdx.x % NF, t = t0 + i;
+        if (t < g.Nt) g.out[k * g.ldo + t] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    }
+}
+
+// one instantiation per (layout, mask): a functional that is not requested costs nothing
+template <int L, int MASK = 1>
+void launch_extend_fn(int mask, int grid, hipStream_t st, const FnArgs& g) {
+    if constexpr (MASK <= 31) {
+        if (mask == MASK) extend_fn_kernel<L, MASK><<<grid, 256, 0, st>>>(g);
+        else launch_extend_fn<L, MASK + 1>(mask, grid, st, g);
+    }
+}
+
+// r = residual of the equation at each test point from the extension's rows: the relations the Gauss-Newton systems eliminate
+// (reference src/PDEs.py:132 elliptic, :341 Burgers, :491 Eikonal; src/InverseProblems.py:185 Darcy; gpk.h, gpk_pde_residual)
+__global__ __launch_bounds__(256) void pde_residual_kernel(int sys, double p0, double p1, int Nt, const double* __restrict__ u, long ldu,
+                                                           const double* __restrict__ a, long lda, const double* __restrict__ f,
+                                                           double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Nt) return;
+    const double u0 = u[t], u1 = u[ldu + t], u2 = u[2 * ldu + t], u3 = u[3 * ldu + t], ft = f[t];
+    double r;
+    switch (sys) {
+        case GPK_GN_BURGERS:  r = u1 + p0 * u0 * u2 - p1 * u3 - ft; break;                 // u_t + alpha u u_x - nu u_xx - f
+        case GPK_GN_EIKONAL:  r = u1 * u1 + u2 * u2 - ft * ft - p0 * u3; break;            // |grad u|^2 - f^2 - eps Delta u
+        case GPK_GN_DARCY: {                                                                // -e^a (Delta u + grad a . grad u) - f
+            const double a0 = a[t], a1 = a[lda + t], a2 = a[2 * lda + t];
+            r = -exp(a0) * (u3 + a1 * u1 + a2 * u2) - ft;
+            break;
+        }
+        default:              r = -u3 + p0 * pow(u0, p1) - ft; break;                      // -Delta u + alpha u^m - f (also relaxed)
+    }
+    out[t] = r;
+}
+
 template <int L> void fill_layout(AsmArgs& g, int Nd, int Nb) {
     int o = 0;
     for (int b = 0; b < 4; ++b) {
@@ -420,6 +539,46 @@ extern "C" int gpk_extend(gpk_handle h, int layout, int kernel, const double* kp
         case GPK_LAYOUT_EIKONAL:  extend_kernel<GPK_LAYOUT_EIKONAL><<<Nt, 256, 0, h->stream>>>(g); break;
         case GPK_LAYOUT_DARCY_A:  extend_kernel<GPK_LAYOUT_DARCY_A><<<Nt, 256, 0, h->stream>>>(g); break;
     }
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int gpk_extend_functionals(gpk_handle h, int layout, int kernel, const double* kp, const double* Xt, int Nt,
+                                      const double* Xd, int Nd, const double* Xb, int Nb, const double* coeff, int fmask,
+                                      double* out, int ldo) {
+    if (!h) return GPK_ERR_ARG;
+    if (!out || !Xt || !coeff) return gpk_bad_arg(h, "extend_functionals: pointers");
+    if (fmask <= 0 || fmask > 31) return gpk_bad_arg(h, "extend_functionals: fmask must be a non-empty subset of the GPK_FN_* bits");
+    if (Nt <= 0) return gpk_bad_arg(h, "extend_functionals: Nt <= 0");
+    if (ldo < Nt) return gpk_bad_arg(h, "extend_functionals: ldo < Nt");
+    AsmArgs a;
+    GPK_TRY(fill_common(h, a, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    FnArgs g;
+    g.px = a.px; g.py = a.py; g.M = a.M; g.p1 = a.p1; g.p2 = a.p2;
+    for (int b = 0; b < 4; ++b) { g.off[b] = a.off[b]; g.size[b] = a.size[b]; }
+    g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
+    const int grid = gpk_ceil_div(Nt, FN_TT);
+    switch (layout) {
+        case GPK_LAYOUT_ELLIPTIC: launch_extend_fn<GPK_LAYOUT_ELLIPTIC>(fmask, grid, h->stream, g); break;
+        case GPK_LAYOUT_BURGERS:  launch_extend_fn<GPK_LAYOUT_BURGERS>(fmask, grid, h->stream, g); break;
+        case GPK_LAYOUT_EIKONAL:  launch_extend_fn<GPK_LAYOUT_EIKONAL>(fmask, grid, h->stream, g); break;
+        case GPK_LAYOUT_DARCY_A:  launch_extend_fn<GPK_LAYOUT_DARCY_A>(fmask, grid, h->stream, g); break;
+    }
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int gpk_pde_residual(gpk_handle h, int system, const double* params3, int Nt, const double* fields_u, int ldu,
+                                const double* fields_a, int lda, const double* rhs, double* out) {
+    if (!h) return GPK_ERR_ARG;
+    if (system < GPK_GN_ELLIPTIC || system > GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "pde_residual: system id");
+    if (Nt <= 0) return gpk_bad_arg(h, "pde_residual: Nt <= 0");
+    if (!fields_u || !rhs || !out || ldu < Nt) return gpk_bad_arg(h, "pde_residual: fields_u / rhs / out / ldu");
+    if (system == GPK_GN_DARCY && (!fields_a || lda < Nt)) return gpk_bad_arg(h, "pde_residual: Darcy needs fields_a (3 rows, lda >= Nt)");
+    if (system != GPK_GN_DARCY && !params3) return gpk_bad_arg(h, "pde_residual: host_params3");
+    const double p0 = params3 ? params3[0] : 0.0, p1 = params3 ? params3[1] : 0.0;
+    pde_residual_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(system, p0, p1, Nt, fields_u, ldu,
+                                                                      system == GPK_GN_DARCY ? fields_a : nullptr, lda, rhs, out);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

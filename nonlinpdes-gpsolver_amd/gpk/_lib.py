@@ -80,6 +80,8 @@ PROTOTYPES = {
     'gpk_assemble_test': (_i, [_vp, _i, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
     'gpk_extend': (_i, [_vp, _i, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'gpk_error_metrics': (_i, [_vp, _i, _vp, _vp, _vp, _pd, _pd]),
+    'gpk_extend_functionals': (_i, [_vp, _i, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_pde_residual': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'gpk_potrf': (_i, [_vp, _vp, _i, _i, _pi]),
     'gpk_tril': (_i, [_vp, _vp, _i, _i]),
     'gpk_symmetrize_lower': (_i, [_vp, _vp, _i, _i]),

@@ -12,6 +12,7 @@ from ._lib import GNProblemStruct, GpkError, load_library
 LAYOUT = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_u': 2, 'Darcy_a': 3}
 KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1}
 NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
+FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
 
 
@@ -339,6 +340,49 @@ class Context:
         out = DeviceArray(self, Nt)
         self._chk(self.lib.gpk_extend(self.h, LAYOUT[layout], KERNEL[kernel], kernel_params(kernel, kernel_parameter),
                                       dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, out.ptr))
+        self.synchronize()
+        return out
+
+    def extend_functionals(self, layout, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'laplacian')):
+        """Derivatives of the extension at Xt (gpk_extend_functionals): a (len(which), Nt) DeviceArray, row k = functional which[k]
+        (names: FUNCTIONAL; for Burgers d1 = d/dt, d2 = d/dx, d2d2 = d^2/dx^2).  coeff = Theta^{-1} sol_vec, as for extend()."""
+        which = tuple(which)
+        bits = [FUNCTIONAL[w] for w in which]
+        if len(set(bits)) != len(bits):
+            raise ValueError(f'extend_functionals: repeated functional in {which!r}')
+        Xt = np.ascontiguousarray(Xt, dtype=np.float64); Xd = np.ascontiguousarray(Xd, dtype=np.float64)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
+        dXt, dXd, dXb = self.points(Xt), self.points(Xd), self.points(Xb)
+        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
+        mask = sum(bits)
+        full = DeviceArray(self, bin(mask).count('1'), Nt, ld=Nt)           # rows in ascending bit order
+        self._chk(self.lib.gpk_extend_functionals(self.h, LAYOUT[layout], KERNEL[kernel], kernel_params(kernel, kernel_parameter),
+                                                  dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, mask, full.ptr, full.ld))
+        order = sorted(bits)
+        if bits == order:
+            out = full
+        else:                                                             # the caller's order
+            out = DeviceArray(self, len(bits), Nt, ld=Nt)
+            for k, b in enumerate(bits):
+                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
+        self.synchronize()
+        return out
+
+    def pde_residual(self, system, params, fields_u, fields_a, rhs):
+        """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array
+        with rows value, d1, d2, laplacian (Burgers: value, u_t, u_x, u_xx); fields_a: (3, Nt) value, d1, d2 of a (Darcy_flow2d only,
+        else None); params: the equation's _gn_params() (its first two entries are used); rhs: f at the test points."""
+        du = fields_u if isinstance(fields_u, DeviceArray) else self.array(np.atleast_2d(fields_u))
+        da = None
+        if fields_a is not None:
+            da = fields_a if isinstance(fields_a, DeviceArray) else self.array(np.atleast_2d(fields_a))
+        Nt = du.cols
+        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        out = DeviceArray(self, Nt)
+        p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]]) if params is not None else None
+        self._chk(self.lib.gpk_pde_residual(self.h, SYSTEM[system], p, Nt, du.ptr, du.ld, da.ptr if da is not None else None,
+                                            da.ld if da is not None else 0, dr.ptr, out.ptr))
         self.synchronize()
         return out
 

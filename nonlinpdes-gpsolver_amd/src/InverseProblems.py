@@ -139,3 +139,23 @@ class Darcy_flow2d(_GPEquation):
             out[tag] = ctx.extend(layout, self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary, coeff).download()
         self.extended_sol_a = out['a']
         self.extended_sol_u = out['u']
+
+    # ---- derivatives and PDE residual (src/PDEs.py, _GPEquation): both fields, -div(e^a grad u) = f ------------------------------------
+    def _derivative_fields(self, X_test):
+        ctx = get_context()
+        out = {}
+        for tag, layout, Ld, vec, names in (('u', 'Darcy_u', self._dL_u, self.sol_vec_u, self._deriv_names),
+                                            ('a', 'Darcy_a', self._dL_a, self.sol_vec_a, ('value', 'd1', 'd2'))):
+            out[tag] = ctx.extend_functionals(layout, self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                              self._coeff(Ld, vec), which=names)
+        return out
+
+    def extend_derivatives(self, X_test):
+        """{'u': {value, d1, d2, laplacian}, 'a': {value, d1, d2}} at X_test (a = log-permeability; numpy arrays)"""
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        f = self._derivative_fields(X_test)
+        self.extended_derivatives = {'u': self._rows(f['u'], self._deriv_names), 'a': self._rows(f['a'], ('value', 'd1', 'd2'))}
+        return self.extended_derivatives
+
+    def _residual_params(self):
+        return None

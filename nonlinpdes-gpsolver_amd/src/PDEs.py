@@ -222,6 +222,45 @@ class _GPEquation(object):
         self.extended_sol = ctx.extend(self._layout, self.kernel, self.kernel_parameter, X_test, self.X_domain,
                                        self.X_boundary, coeff).download()
 
+    # ---- derivatives and PDE residual of the solution away from the collocation points (gpk_extend_functionals, gpk_pde_residual) --
+    # Both leave every attribute of extend_sol / GN_method as it is; they set extended_derivatives / test_residual only.
+    _deriv_names = ('value', 'd1', 'd2', 'laplacian')           # rows of the u-field handed to gpk_pde_residual
+
+    def _coeff(self, Ld, vec):
+        """Theta^{-1} vec on the device, as extend_sol computes it (L^{-T} L^{-1} vec)"""
+        coeff = get_context().array(vec)
+        get_context().potrs(Ld, coeff, nrhs=1)
+        return coeff
+
+    def _derivative_fields(self, X_test):
+        """{'u': (len(_deriv_names), Nt) DeviceArray}"""
+        coeff = self._coeff(self._dL, self.sol_vec)
+        return {'u': get_context().extend_functionals(self._layout, self.kernel, self.kernel_parameter, X_test, self.X_domain,
+                                                      self.X_boundary, coeff, which=self._deriv_names)}
+
+    @staticmethod
+    def _rows(d, names):
+        a = d.download().reshape(len(names), -1)
+        return {n: a[k].copy() for k, n in enumerate(names)}
+
+    def extend_derivatives(self, X_test):
+        """value, d1, d2 and laplacian (Burgers: value, d1 = u_t, d2 = u_x, d2d2 = u_xx) of the GP solution at X_test (numpy arrays)"""
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        self.extended_derivatives = self._rows(self._derivative_fields(X_test)['u'], self._deriv_names)
+        return self.extended_derivatives
+
+    def _residual_params(self):
+        return self._gn_params()[:2]
+
+    def PDE_residual(self, X_test):
+        """pointwise residual of the equation at X_test from the derivatives of the GP solution (rhs evaluated at X_test)"""
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        fields = self._derivative_fields(X_test)
+        rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
+        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields['u'], fields.get('a'),
+                                                        rhs).download().reshape(-1)
+        return self.test_residual
+
 
 class Nonlinear_elliptic2d(_GPEquation):
     """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208)."""
@@ -306,6 +345,8 @@ class Burgers(_GPEquation):
         self.bdy = bdy
         self.rhs = rhs
         self.domain = domain
+
+    _deriv_names = ('value', 'd1', 'd2', 'd2d2')              # u, u_t, u_x, u_xx
 
     def _gn_params(self):
         return float(self.alpha), float(self.nu), 0.0

@@ -51,6 +51,9 @@ _LOG = {
     'testing': '[Testing...] Number of test points: {n}',
     'test_max': '[Test error] Max error {v}',
     'test_l2': '[Test error] L2 error {v}',
+    'res_n': '[Testing PDE residual...] Number of test points: {n}',
+    'res_max': '[Test residual] Max residual {v}',
+    'res_l2': '[Test residual] L2 residual {v}',
 }
 
 
@@ -144,6 +147,15 @@ class solver_GP(object):
                                                                                                self.eqn.extended_sol)
         _say(print_option, 'test_max', v=self.test_max_err)
         _say(print_option, 'test_l2', v=self.test_L2_err)
+
+    def test_residual(self, X_test, print_option=True):
+        """How well the GP solution satisfies the PDE between the collocation points -- no truth solution needed: the residual of the
+        equation at X_test from the derivatives of the solution (eqn.PDE_residual), reduced like get_test_error against zero."""
+        _say(print_option, 'res_n', n=X_test.shape[0])
+        r = self.eqn.PDE_residual(X_test)
+        _, self.test_res_max, self.test_res_L2 = get_context().error_metrics(onp.zeros(r.size), r)
+        _say(print_option, 'res_max', v=self.test_res_max)
+        _say(print_option, 'res_l2', v=self.test_res_L2)
 
     # ---- figures (cosmetic; need matplotlib only): src/_figures.py ---------------------------------------------------------
     def show_sample(self):
