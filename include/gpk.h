@@ -9,7 +9,10 @@
  *   - every matrix/vector pointer is a DEVICE pointer owned by the caller unless the name says `host`; the library
  *     never frees or keeps them after the call.  Matrices are row-major double with a leading dimension in ELEMENTS;
  *     symmetric outputs are stored full.  Vector loads are 16-byte wide when pointer and leading dimension allow
- *     (even ld, 16-byte aligned base); any alignment is accepted.
+ *     (even ld, 16-byte aligned base); any alignment is accepted (the matrix product then loads element by element; the
+ *     substitution kernels keep their 16-byte loads at 8-byte alignment, which gfx950 global memory serves).  Operands are
+ *     VIEWS: a routine writes its declared output region and nothing else, and triangular routines read only the lower
+ *     triangle of L (tests/test_gpu_dense_views.py checks all three on unaligned views between canaries).
  *   - calls are asynchronous on the handle's stream; functions that return host scalars (info, loss, ratios)
  *     synchronise that stream.  One host thread per handle.  The library has NO process-wide mutable state (round 4): all
  *     state, including the development / tuning switches (gpk_debug.h: gpk_tune(handle, key, value), never called by the
@@ -121,8 +124,10 @@ int gpk_error_metrics(gpk_handle h, int n, const double* truth, const double* ap
                       double* host_max, double* host_l2);
 
 /* ---- dense fp64 linear algebra on the MFMA units --------------------------------------------------------- */
-/* jnp.linalg.cholesky (src/PDEs.py:77,273,413; src/InverseProblems.py:102-103): lower factor in place (strict
- * upper triangle left untouched -- gpk_tril zeroes it).  Non-positive pivot: *host_info = its 1-based index,
+/* jnp.linalg.cholesky (src/PDEs.py:77,273,413; src/InverseProblems.py:102-103): lower factor in place.  Only the lower
+ * triangle of A is read.  The strict upper triangle of the n x n view is UNSPECIFIED on return (the blocked updates write
+ * whole tiles above the diagonal of the diagonal blocks; nothing ever reads them -- gpk_tril zeroes it); nothing outside
+ * the n x n view is written.  Non-positive pivot: *host_info = its 1-based index,
  * NaNs propagate like the reference's JAX path; return value 0 unless a HIP error occurred. */
 int gpk_potrf(gpk_handle h, double* A, int n, int lda, int* host_info);
 int gpk_tril(gpk_handle h, double* A, int n, int lda);

@@ -1051,7 +1051,7 @@ extern "C" int gpk_gemm_lz(gpk_handle h, int ta, int m, int n, int k, double alp
 }
 
 extern "C" int gpk_symmetrize_lower(gpk_handle h, double* A, int n, int lda) {
-    if (!h || !A) return GPK_ERR_ARG;
+    if (!h || !A || lda < n) return GPK_ERR_ARG;
     if (n <= 0) return 0;
     dim3 grid(gpk_ceil_div(n, 64), gpk_ceil_div(n, 4));
     symmetrize_kernel<<<grid, 256, 0, h->stream>>>(A, n, lda);
@@ -1060,7 +1060,7 @@ extern "C" int gpk_symmetrize_lower(gpk_handle h, double* A, int n, int lda) {
 }
 
 extern "C" int gpk_tril(gpk_handle h, double* A, int n, int lda) {
-    if (!h || !A) return GPK_ERR_ARG;
+    if (!h || !A || lda < n) return GPK_ERR_ARG;
     if (n <= 0) return 0;
     dim3 grid(gpk_ceil_div(n, 64), gpk_ceil_div(n, 4));
     tril_kernel<<<grid, 256, 0, h->stream>>>(A, n, lda);
