@@ -75,7 +75,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -117,6 +117,26 @@ int gpk_extend_functionals(gpk_handle h, int layout, int kernel, const double* h
  *   DARCY               r = -e^a (Delta u + grad a . grad u) - f   (v3 = -v1 w1 - v2 w2 - f e^{-w0}, src/InverseProblems.py:185) */
 int gpk_pde_residual(gpk_handle h, int system, const double* host_params3, int Nt,
                      const double* fields_u, int ldu, const double* fields_a, int lda, const double* rhs, double* out);
+/* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
+ *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
+ *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
+ *      Layout ELLIPTIC3D: block 0 = Laplacian on the Nd domain points, block 1 = delta on the Nd+Nb domain+boundary points; Theta is
+ *      N x N, N = 2Nd+Nb -- the same shape as GPK_LAYOUT_ELLIPTIC, so gpk_potrf, the GPK_GN_ELLIPTIC system and gpk_pde_residual apply unchanged.
+ *      host_ratio (one double, may be NULL): trace(block 0) / trace(block 1) = Nd <Lap,Lap>(0) / (Nd+Nb), written for every nugget type.
+ *      Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte stores otherwise); the launch is
+ *      timed like gpk_assemble's when the per-phase timing is on (gpk_prof_read_assembly). */
+int gpk_assemble3d(gpk_handle h, int kernel, const double* host_kparams,
+                   const double* Xd, int Nd, const double* Xb, int Nb,
+                   double nugget, int nugget_type, double* Theta, int ld, double* host_ratio);
+/* Value and derivatives of the 3-D extension at test points Xt (Nt,3), matrix-free, as gpk_extend_functionals: coeff (2Nd+Nb) =
+ * Theta^{-1} sol_vec.  fmask: a non-empty subset of GPK_FN_VALUE, GPK_FN_D1, GPK_FN_D2, GPK_FN_D3, GPK_FN_LAPLACIAN (anything else,
+ * GPK_FN_D2D2 included: -9001); fmask == GPK_FN_VALUE is the plain extension.  out is functional-major, row k (the k-th set bit of
+ * fmask, ascending: value, d1, d2, laplacian, d3) at out + k*ldo, ldo >= Nt; entries past Nt untouched.  Fixed reduction order: a
+ * repeated call gives bit-identical output. */
+#define GPK_FN_D3 32          /* d/dx3: 3-D calls only (bit 5, next to the GPK_FN_* bits above) */
+int gpk_extend_functionals3d(gpk_handle h, int kernel, const double* host_kparams,
+                             const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
+                             const double* coeff, int fmask, double* out, int ldo);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the
  * device (the extension already is); one pass, fixed summation order.  Synchronises. */

@@ -13,6 +13,7 @@ LAYOUT = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_u': 2, 'Da
 KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1}
 NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
+FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
 
 
@@ -43,6 +44,18 @@ def kernel_params(kernel, kernel_parameter):
         return (C.c_double * 2)(float(kernel_parameter), 0.0)
     if kernel == 'anisotropic_Gaussian':
         return (C.c_double * 2)(float(kernel_parameter[0]), float(kernel_parameter[1]))
+    raise ValueError(f'unknown kernel {kernel!r}')
+
+
+def kernel_params3d(kernel, kernel_parameter):
+    """host_kparams of the 3-D calls: Gaussian {sigma}; anisotropic_Gaussian {sigma_1, sigma_2, sigma_3}"""
+    if kernel == 'Gaussian':
+        return (C.c_double * 3)(float(kernel_parameter), 0.0, 0.0)
+    if kernel == 'anisotropic_Gaussian':
+        kp = [float(v) for v in kernel_parameter]
+        if len(kp) != 3:
+            raise ValueError(f'anisotropic_Gaussian in three dimensions needs 3 length scales, got {len(kp)}')
+        return (C.c_double * 3)(*kp)
     raise ValueError(f'unknown kernel {kernel!r}')
 
 
@@ -291,10 +304,10 @@ class Context:
             return DeviceArray(self, a.size).upload(a)
         return DeviceArray(self, a.shape[0], a.shape[1]).upload(a)
 
-    def points(self, X):
-        """(n,2) point set, contiguous (ld = 2) as the C ABI expects"""
-        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 2)
-        return DeviceArray(self, max(X.shape[0], 1), 2, ld=2).upload(X) if X.shape[0] else DeviceArray(self, 1, 2, ld=2)
+    def points(self, X, dim=2):
+        """(n,dim) point set, contiguous (ld = dim) as the C ABI expects (dim = 3: the *3d calls)"""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, dim)
+        return DeviceArray(self, max(X.shape[0], 1), dim, ld=dim).upload(X) if X.shape[0] else DeviceArray(self, 1, dim, ld=dim)
 
     def timer_start(self):
         self._chk(self.lib.gpk_timer_start(self.h))
@@ -359,6 +372,47 @@ class Context:
         full = DeviceArray(self, bin(mask).count('1'), Nt, ld=Nt)           # rows in ascending bit order
         self._chk(self.lib.gpk_extend_functionals(self.h, LAYOUT[layout], KERNEL[kernel], kernel_params(kernel, kernel_parameter),
                                                   dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, mask, full.ptr, full.ld))
+        order = sorted(bits)
+        if bits == order:
+            out = full
+        else:                                                             # the caller's order
+            out = DeviceArray(self, len(bits), Nt, ld=Nt)
+            for k, b in enumerate(bits):
+                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
+        self.synchronize()
+        return out
+
+    # ---- three space dimensions (gpk_assemble3d, gpk_extend_functionals3d) ----
+    def assemble3d(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 3-D elliptic layout (Laplacian on Xd, delta on [Xd; Xb]; points (n,3)): (DeviceArray N x N with
+        N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any leading dimension >= N)."""
+        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 3); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 3)
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 2 * Nd + Nb
+        dXd, dXb = self.points(Xd, 3), self.points(Xb, 3)
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratio = C.c_double()
+        self._chk(self.lib.gpk_assemble3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
+                                          float(nugget), NUGGET[nugget_type], T.ptr, T.ld, C.byref(ratio)))
+        self.synchronize()
+        return T, ratio.value
+
+    def extend_functionals3d(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd3', 'laplacian')):
+        """Value / derivatives of the 3-D extension at Xt (gpk_extend_functionals3d): a (len(which), Nt) DeviceArray, row k = functional
+        which[k] (names: FUNCTIONAL3D).  coeff = Theta^{-1} sol_vec (2 Nd + Nb values).  which = ('value',) is the plain extension."""
+        which = tuple(which)
+        bits = [FUNCTIONAL3D[w] for w in which]
+        if len(set(bits)) != len(bits):
+            raise ValueError(f'extend_functionals3d: repeated functional in {which!r}')
+        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 3); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 3)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 3)
+        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
+        dXt, dXd, dXb = self.points(Xt, 3), self.points(Xd, 3), self.points(Xb, 3)
+        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
+        mask = sum(bits)
+        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
+        self._chk(self.lib.gpk_extend_functionals3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter),
+                                                    dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, mask, full.ptr, full.ld))
         order = sorted(bits)
         if bits == order:
             out = full

@@ -1,4 +1,5 @@
-"""Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal.
+"""Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
+same elliptic equation on a box in three space dimensions (no counterpart in the reference).
 
 Same constructor arguments, methods and attributes; no JAX.  The Gram matrix, its Cholesky factor and the Gauss-Newton
 iterate live in GPU memory (libgpk.so); `Theta`, `L`, ... are materialised as numpy arrays only when read.
@@ -13,7 +14,7 @@ from numpy import random
 import gpk
 
 from ._runtime import eval_callback, get_context
-from .sample_points import sampled_pts_grid, sampled_pts_rdm
+from .sample_points import sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
 
@@ -330,6 +331,118 @@ class Nonlinear_elliptic2d(_GPEquation):
         sol = self._gn_iterate(self._relaxed_problem(pen_lambda), sol, max_iter, step_size, print_hist)
         self.sol_vec = onp.concatenate([sol, self.bdy_g])
         self.sol_sampled_pts = sol[self.N_domain:]
+
+
+class Nonlinear_elliptic3d(_GPEquation):
+    """-Delta u + alpha*u^m = f on a box in R^3, u = g on its six faces.  Same methods and attributes as Nonlinear_elliptic2d (elimination
+    formulation only; the relaxed formulation is not offered); points are (n,3), callbacks take (x1, x2, x3).  The Gram matrix has the
+    2-D elliptic block structure -- Laplacian on the domain points, delta on domain + boundary points, N = 2 N_domain + N_boundary --
+    so the factorisation and the Gauss-Newton system ('Nonlinear_elliptic') are the 2-D ones; only the point-pair evaluator
+    (gpk_assemble3d, gpk_extend_functionals3d) knows about the third coordinate.  GPK_STRUCTURED is ignored here: every step runs the
+    reference's operation sequence."""
+    _layout = 'Nonlinear_elliptic3d'
+    _system = 'Nonlinear_elliptic'
+    _deriv_names = ('value', 'd1', 'd2', 'd3', 'laplacian')
+
+    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]])):
+        self.alpha = alpha
+        self.m = m
+        self.bdy = bdy
+        self.rhs = rhs
+        self.domain = domain
+
+    def get_bd(self, x1, x2, x3):
+        return self.bdy(x1, x2, x3)
+
+    def get_rhs(self, x1, x2, x3):
+        return self.rhs(x1, x2, x3)
+
+    @staticmethod
+    def _pts(X):
+        X = onp.asarray(X, dtype=onp.float64)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f'points must have shape (n, 3), got {X.shape}')
+        return X
+
+    def _set_points(self, X_domain, X_boundary):
+        self.X_domain = self._pts(X_domain)
+        self.N_domain = self.X_domain.shape[0]
+        self.X_boundary = self._pts(X_boundary)
+        self.N_boundary = self.X_boundary.shape[0]
+        self.rhs_f = eval_callback(self.get_rhs, *self.X_domain.T)
+        self.bdy_g = eval_callback(self.get_bd, *self.X_boundary.T)
+        self._drop_device_state()
+
+    def sampled_pts(self, N_domain, N_boundary, sampled_type='random'):
+        if sampled_type == 'random':
+            X_domain, X_boundary = sampled_pts_rdm3d(N_domain, N_boundary, self.domain)
+        elif sampled_type == 'grid':
+            X_domain, X_boundary = sampled_pts_grid3d(N_domain, N_boundary, self.domain)
+        else:
+            raise ValueError(f'sampled_type {sampled_type!r}: random or grid')
+        self._set_points(X_domain, X_boundary)
+
+    def _gn_params(self):
+        return float(self.alpha), float(self.m), 0.0
+
+    def _problem(self):
+        if getattr(self, '_prob', None) is None:
+            if getattr(self, '_dL', None) is None:
+                raise RuntimeError('call Gram_matrix() and Gram_Cholesky() first')
+            p0, p1, lam = self._gn_params()
+            self._prob = gpk.GNProblem(get_context(), self._system, self.N_domain, self.N_boundary, self.rhs_f, self.bdy_g,
+                                       self._dL, p0=p0, p1=p1, pen_lambda=lam, structured=False)
+        return self._prob
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
+        """kernel_parameter: sigma (Gaussian) or three length scales (anisotropic_Gaussian); stores the trace ratio in `ratio`"""
+        if nugget_type not in ('adaptive', 'identity', 'none'):
+            raise AttributeError(f"nugget_type {nugget_type!r}: adaptive, identity or none")
+        ctx = get_context()
+        self._drop_device_state()
+        self.nugget_type = nugget_type
+        self.nugget = nugget
+        self.kernel = kernel
+        self.kernel_parameter = kernel_parameter
+        self._dTheta, self.ratio = ctx.assemble3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+
+    def GN_loss(self, z, z_old):
+        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
+        zz = onp.concatenate([self.alpha * self.m * (z_old ** (self.m - 1)) * (z - z_old), z, self.bdy_g])
+        return self._tri_loss(zz)
+
+    def Hessian_GN(self, z, z_old):
+        return self._hessian(z_old)          # quadratic in z, as in two dimensions
+
+    def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
+        sol = self._initial(initial_sol, self.N_domain)
+        self.init_sol = sol
+        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
+        self.sol_vec = onp.concatenate([self.alpha * (sol ** self.m) - self.rhs_f, sol, self.bdy_g])
+        self.sol_sampled_pts = sol
+
+    def _fields(self, X_test, which):
+        return get_context().extend_functionals3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                  self._coeff(self._dL, self.sol_vec), which=which)
+
+    def extend_sol(self, X_test):
+        X_test = self._pts(X_test)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = self._fields(X_test, ('value',)).download().reshape(-1)
+
+    def extend_derivatives(self, X_test):
+        """value, d1, d2, d3 and laplacian of the GP solution at X_test (numpy arrays)"""
+        self.extended_derivatives = self._rows(self._fields(self._pts(X_test), self._deriv_names), self._deriv_names)
+        return self.extended_derivatives
+
+    def PDE_residual(self, X_test):
+        """pointwise residual -Delta u + alpha u^m - f at X_test from the derivatives of the GP solution (rhs evaluated at X_test)"""
+        X_test = self._pts(X_test)
+        fields = self._fields(X_test, ('value', 'd1', 'd2', 'laplacian'))      # the rows gpk_pde_residual takes; it reads value and laplacian
+        rhs = eval_callback(self.get_rhs, *X_test.T)
+        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields, None, rhs).download().reshape(-1)
+        return self.test_residual
 
 
 class Burgers(_GPEquation):

@@ -17,14 +17,16 @@ def get_context():
     return _ctx
 
 
-def eval_callback(fn, x1, x2):
-    """Evaluate a user callback bdy(x1,x2)/rhs(x1,x2) on point columns.  The reference vmaps a JAX scalar function
+def eval_callback(fn, x1, x2, *more):
+    """Evaluate a user callback bdy(x1,x2)/rhs(x1,x2) on point columns (three-dimensional equations pass a third column: fn(x1,x2,x3)).
+    The reference vmaps a JAX scalar function
     (src/PDEs.py:44-45); here numpy-vectorised callables are used directly and scalar-only callables (Python ints,
     comparisons, math.*) fall back to an element-wise loop -- only on the TypeError / ValueError such callables raise on arrays;
     every other exception of the callback propagates."""
-    x1 = np.asarray(x1, dtype=np.float64); x2 = np.asarray(x2, dtype=np.float64)
+    xs = [np.asarray(x, dtype=np.float64) for x in (x1, x2) + more]
+    x1 = xs[0]
     try:
-        out = np.asarray(fn(x1, x2), dtype=np.float64)
+        out = np.asarray(fn(*xs), dtype=np.float64)
         if out.shape == x1.shape:
             return out
         if out.ndim == 0:
@@ -34,4 +36,4 @@ def eval_callback(fn, x1, x2):
         # `if x1 > 0` -> ValueError ("truth value of an array is ambiguous"), float(array) -> TypeError.  Anything else -- a NameError
         # from a typo, a ZeroDivisionError, an IndexError -- is the user's bug and propagates from this first call, untouched.
         pass
-    return np.array([float(fn(float(a), float(b))) for a, b in zip(x1, x2)], dtype=np.float64).reshape(x1.shape)
+    return np.array([float(fn(*(float(v) for v in row))) for row in zip(*xs)], dtype=np.float64).reshape(x1.shape)

@@ -4,13 +4,17 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d
+from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
 
 # PDE_type -> (factory, header lines printed by set_equation)
 _EQUATIONS = {
     'Nonlinear_elliptic': (
         lambda c, **k: Nonlinear_elliptic2d(alpha=c.alpha, m=c.m, **k),
         lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'],
+        lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
+    'Nonlinear_elliptic3d': (
+        lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, **k),
+        lambda c: ['[Equation type] Nonlinear elliptic equation in three space dimensions', '[Equation form] - \\Delta u + alpha*u^m = f'],
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
     'Burgers': (
         lambda c, **k: Burgers(alpha=c.alpha, nu=c.nu, **k),
@@ -31,6 +35,7 @@ _EQUATIONS = {
 _LOG = {
     'start': '\n Solver started',
     'domain': '[Equation domain] [{d[0][0]},{d[0][1]}]*[{d[1][0]},{d[1][1]}]',
+    'domain3d': '[Equation domain] [{d[0][0]},{d[0][1]}]*[{d[1][0]},{d[1][1]}]*[{d[2][0]},{d[2][1]}]',
     'data': '[Equation data] Right hand side and boundary values set by the user',
     'pts_user': '[Sample points] Collocation points sampled, specified by the user',
     'pts_auto': '[Sample points] Collocation points sampled, type {kind}',
@@ -86,7 +91,7 @@ class solver_GP(object):
             print(_LOG['start'])
             for line in header(self.config):
                 print(line)
-            _say(True, 'domain', d=domain)
+            _say(True, 'domain3d' if len(domain) == 3 else 'domain', d=domain)
             if params is not None:
                 print(params(self.config))
             _say(True, 'data')
@@ -158,7 +163,12 @@ class solver_GP(object):
         _say(print_option, 'res_l2', v=self.test_res_L2)
 
     # ---- figures (cosmetic; need matplotlib only): src/_figures.py ---------------------------------------------------------
+    def _planar_only(self):
+        if self.PDE_type == 'Nonlinear_elliptic3d':
+            raise NotImplementedError('the plot helpers draw planar point sets and contours; not available for Nonlinear_elliptic3d')
+
     def show_sample(self):
+        self._planar_only()
         from . import _figures
         _figures.scatter_points(self.eqn, False, 'Collocation points')
 
@@ -171,6 +181,7 @@ class solver_GP(object):
         _figures.loss_history(self.eqn)
 
     def contour_of_test_err(self, XX, YY):
+        self._planar_only()
         from . import _figures
         self.XX, self.YY = XX, YY
         _figures.error_contour(XX, YY, self.test_err_all)
