@@ -75,7 +75,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -137,6 +137,27 @@ int gpk_assemble3d(gpk_handle h, int kernel, const double* host_kparams,
 int gpk_extend_functionals3d(gpk_handle h, int kernel, const double* host_kparams,
                              const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
                              const double* coeff, int fmask, double* out, int ldo);
+/* ---- boundary functionals for the 2-D elliptic layout: Neumann, Robin and mixed conditions (no reference call site: the reference puts
+ *      delta on every boundary row, Dirichlet data only; the method is the same -- DESIGN.md section K, "Boundary functionals").
+ *      Layout as GPK_LAYOUT_ELLIPTIC -- block 0 = Laplacian on the Nd domain points, block 1 on the Nd+Nb domain+boundary points,
+ *      N = 2Nd+Nb -- but boundary point b carries phi_b = c0 delta + c1 d/dx1 + c2 d/dx2 instead of delta (domain points keep delta):
+ *      Dirichlet (1,0,0), Neumann (0,n1,n2), Robin (beta,n1,n2) with n the outward unit normal.  gpk_potrf, the GPK_GN_ELLIPTIC system
+ *      (bdy_g = the prescribed values of phi_b u), gpk_potrs and gpk_pde_residual apply unchanged.
+ *      bc: device pointer, (Nb,3) row-major doubles (c0, c1, c2) per boundary point; NULL = all (1,0,0), the entries of gpk_assemble.
+ *      host_kparams, Xd, Xb as gpk_assemble.  host_ratio (one double, may be NULL): trace(block 0) / trace(block 1) =
+ *      Nd (3 p1^2 + 2 p1 p2 + 3 p2^2) / (Nd + sum_b (c0_b^2 + p1 c1_b^2 + p2 c2_b^2)), written for every nugget type; the boundary sum is
+ *      taken on the host in index order (bc != NULL: one small device-to-host copy, synchronises).
+ *      Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte stores otherwise; nothing outside
+ *      the N x N view is written); the launch is timed like gpk_assemble's when the per-phase timing is on (gpk_prof_read_assembly). */
+int gpk_assemble_bc(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                    const double* bc, double nugget, int nugget_type, double* Theta, int ld, double* host_ratio);
+/* Value and derivatives of the extension under boundary functionals at test points Xt (Nt,2), matrix-free, as gpk_extend_functionals:
+ * coeff (2Nd+Nb) = Theta^{-1} sol_vec with the Theta of gpk_assemble_bc for the same bc.  fmask: a non-empty subset of the GPK_FN_* bits
+ * (anything else: -9001); out is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries
+ * past Nt untouched.  Fixed reduction order: a repeated call gives bit-identical output.  No reference call site. */
+int gpk_extend_functionals_bc(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                              const double* Xd, int Nd, const double* Xb, int Nb, const double* bc,
+                              const double* coeff, int fmask, double* out, int ldo);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the
  * device (the extension already is); one pass, fixed summation order.  Synchronises. */

@@ -423,6 +423,59 @@ class Context:
         self.synchronize()
         return out
 
+    # ---- boundary functionals: Neumann / Robin / mixed conditions for the 2-D elliptic layout (gpk_assemble_bc, gpk_extend_functionals_bc) ----
+    def _boundary_coeffs(self, bc, Nb):
+        """(Nb,3) coefficients (c0, c1, c2) of the boundary functionals on the device, or None (= NULL: all (1,0,0))"""
+        if bc is None:
+            return None
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        if bc.shape != (Nb, 3):
+            raise ValueError(f'boundary coefficients must have shape ({Nb}, 3): (c0, c1, c2) per boundary point, got {bc.shape}')
+        return DeviceArray(self, max(Nb, 1), 3, ld=3).upload(bc) if Nb else DeviceArray(self, 1, 3, ld=3)
+
+    def assemble_bc(self, kernel, kernel_parameter, Xd, Xb, bc, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 2-D elliptic layout with the functional bc[b] = (c0, c1, c2) -> c0 delta + c1 d/dx1 + c2 d/dx2 at boundary
+        point b (bc = None: delta everywhere): (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to
+        write into (any leading dimension >= N)."""
+        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 2 * Nd + Nb
+        dXd, dXb, dbc = self.points(Xd), self.points(Xb), self._boundary_coeffs(bc, Nb)
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratio = C.c_double()
+        self._chk(self.lib.gpk_assemble_bc(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
+                                           dbc.ptr if dbc is not None else None, float(nugget), NUGGET[nugget_type], T.ptr, T.ld,
+                                           C.byref(ratio)))
+        self.synchronize()
+        return T, ratio.value
+
+    def extend_functionals_bc(self, kernel, kernel_parameter, Xt, Xd, Xb, bc, coeff, which=('value', 'd1', 'd2', 'laplacian')):
+        """Value / derivatives of the extension under the boundary functionals bc at Xt (gpk_extend_functionals_bc): a (len(which), Nt)
+        DeviceArray, row k = functional which[k] (names: FUNCTIONAL).  coeff = Theta^{-1} sol_vec with the Theta of assemble_bc."""
+        which = tuple(which)
+        bits = [FUNCTIONAL[w] for w in which]
+        if len(set(bits)) != len(bits):
+            raise ValueError(f'extend_functionals_bc: repeated functional in {which!r}')
+        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 2); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
+        dXt, dXd, dXb, dbc = self.points(Xt), self.points(Xd), self.points(Xb), self._boundary_coeffs(bc, Nb)
+        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
+        mask = sum(bits)
+        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
+        self._chk(self.lib.gpk_extend_functionals_bc(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
+                                                     dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dbc.ptr if dbc is not None else None,
+                                                     dc.ptr, mask, full.ptr, full.ld))
+        order = sorted(bits)
+        if bits == order:
+            out = full
+        else:                                                             # the caller's order
+            out = DeviceArray(self, len(bits), Nt, ld=Nt)
+            for k, b in enumerate(bits):
+                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
+        self.synchronize()
+        return out
+
     def pde_residual(self, system, params, fields_u, fields_a, rhs):
         """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array
         with rows value, d1, d2, laplacian (Burgers: value, u_t, u_x, u_xx); fields_a: (3, Nt) value, d1, d2 of a (Darcy_flow2d only,

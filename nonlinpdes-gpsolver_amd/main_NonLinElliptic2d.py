@@ -2,7 +2,9 @@
 """Nonlinear elliptic equation -Delta u + alpha*u^m = f on [0,1]^2 with the GP solver on an MI355X.
 Same command line as the reference's main_NonLinElliptic2d.py (README.md:15 of the reference):
     python main_NonLinElliptic2d.py --kernel Gaussian --kernel_parameter 0.2 --nugget 1e-13 --N_domain 900 --N_boundary 124 --GNsteps 4
-The manufactured solution's right-hand side is written out analytically (the reference differentiates u with jax.grad)."""
+The manufactured solution's right-hand side is written out analytically (the reference differentiates u with jax.grad).
+--bc neumann / --bc robin [--robin_beta B] (no counterpart in the reference) prescribe du/dn = g or B u + du/dn = g on the boundary
+instead of u = g, with g formed from the manufactured solution's gradient and the outward normal."""
 import argparse
 
 import numpy as onp
@@ -18,6 +20,8 @@ def parse(argv=None):
     parser.add_argument("--m", type=float, default=3.0)
     add_kernel_and_sampling(parser, 'Gaussian', 0.2, 1e-13, 900, 124)
     parser.add_argument("--pen_lambda", type=float, default=1e-10)      # for the relaxation approach
+    parser.add_argument("--bc", type=str, default='dirichlet', choices=['dirichlet', 'neumann', 'robin'])
+    parser.add_argument("--robin_beta", type=float, default=1.0)        # beta of --bc robin: beta u + du/dn = g
     add_gn_and_logs(parser, 'rdm', 4, method_choices=['elimination', 'relaxation'])
     return parser.parse_args(argv)
 
@@ -35,10 +39,32 @@ def manufactured(alpha, m):
     return u, f
 
 
+def manufactured_gradient(x1, x2):
+    """gradient of u* of manufactured()"""
+    pi = onp.pi
+    return (pi * onp.cos(pi * x1) * onp.sin(pi * x2) + 8 * pi * onp.cos(4 * pi * x1) * onp.sin(4 * pi * x2),
+            pi * onp.sin(pi * x1) * onp.cos(pi * x2) + 8 * pi * onp.sin(4 * pi * x1) * onp.cos(4 * pi * x2))
+
+
+def boundary_data(u, bc, robin_beta, domain=UNIT_SQUARE):
+    """the callback bdy(x1, x2) = value of the boundary operator on u*: u* itself (dirichlet), du*/dn (neumann), beta u* + du*/dn (robin)"""
+    if bc == 'dirichlet':
+        return u
+    from src.sample_points import boundary_normals
+    beta = robin_beta if bc == 'robin' else 0.0
+
+    def g(x1, x2):
+        x1 = onp.asarray(x1, dtype=onp.float64); x2 = onp.asarray(x2, dtype=onp.float64)
+        n = boundary_normals(onp.stack([x1.ravel(), x2.ravel()], axis=1), domain)
+        u1, u2 = manufactured_gradient(x1, x2)
+        return beta * u(x1, x2) + n[:, 0].reshape(x1.shape) * u1 + n[:, 1].reshape(x1.shape) * u2
+    return g
+
+
 def main(argv=None):
     cfg = parse(argv)
     u, f = manufactured(cfg.alpha, cfg.m)
-    solver, show = solve_forward(cfg, "Nonlinear_elliptic", u, f, UNIT_SQUARE,
+    solver, show = solve_forward(cfg, "Nonlinear_elliptic", boundary_data(u, cfg.bc, cfg.robin_beta), f, UNIT_SQUARE,
                                  solve_kwargs={'method': cfg.method, 'pen_lambda': cfg.pen_lambda}, verbose=cfg.print_hist)
     Xd = solver.eqn.X_domain
     solver.collocation_pts_err(u(Xd[:, 0], Xd[:, 1]))                    # error on the collocation points

@@ -14,7 +14,7 @@ from numpy import random
 import gpk
 
 from ._runtime import eval_callback, get_context
-from .sample_points import sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
+from .sample_points import boundary_normals, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
 
@@ -96,9 +96,12 @@ class _GPEquation(object):
         self.nugget = nugget
         self.kernel = kernel
         self.kernel_parameter = kernel_parameter
-        self._dTheta, ratios = ctx.assemble(self._layout, kernel, kernel_parameter, self.X_domain, self.X_boundary,
-                                            nugget, nugget_type)
+        self._dTheta, ratios = self._evaluate_gram(ctx, kernel, kernel_parameter, nugget, nugget_type)
         return ratios
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        """the evaluator call of _assemble: (device matrix, trace ratios)"""
+        return ctx.assemble(self._layout, kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
 
     @property
     def Theta(self):
@@ -268,20 +271,90 @@ class Nonlinear_elliptic2d(_GPEquation):
     _layout = 'Nonlinear_elliptic'
     _system = 'Nonlinear_elliptic'
 
-    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]])):
+    _BC = ('dirichlet', 'neumann', 'robin')
+
+    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0):
+        """bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
+        g = B u is what `bdy(x1, x2)` returns -- 'dirichlet' B u = u; 'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the
+        outward unit normal (sample_points.boundary_normals).  set_boundary_operator() takes an arbitrary first-order operator per
+        boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went."""
+        if bc not in self._BC:
+            raise ValueError(f'bc {bc!r}: one of {self._BC}')
         self.alpha = alpha
         self.m = m
         self.bdy = bdy
         self.rhs = rhs
         self.domain = domain
+        self.bc = bc
+        self.robin_beta = robin_beta
+        self.boundary_coeffs = None
 
     def _gn_params(self):
         return float(self.alpha), float(self.m), 0.0
+
+    # ---- boundary operator: (N_boundary, 3) coefficients (c0, c1, c2) of c0 u + c1 u_x1 + c2 u_x2, or None = Dirichlet, today's path ----
+    def _set_points(self, X_domain, X_boundary):
+        super()._set_points(X_domain, X_boundary)
+        self.boundary_coeffs = None                        # a custom operator belongs to the points it was set for
+        if self.bc != 'dirichlet':
+            n = boundary_normals(self.X_boundary, self.domain)
+            beta = float(self.robin_beta) if self.bc == 'robin' else 0.0
+            self.boundary_coeffs = onp.concatenate([onp.full((self.N_boundary, 1), beta), n], axis=1)
+
+    def set_boundary_operator(self, coeffs):
+        """Row b of coeffs (N_boundary, 3) = (c0, c1, c2): the condition at boundary point b reads c0 u + c1 u_x1 + c2 u_x2 = bdy_g[b].
+        Call after the points are set; dropped when they change.  Discards the Gram matrix and everything derived from it."""
+        coeffs = onp.array(coeffs, dtype=onp.float64)
+        if coeffs.shape != (self.N_boundary, 3):
+            raise ValueError(f'coeffs must have shape ({self.N_boundary}, 3), got {coeffs.shape}')
+        self.boundary_coeffs = coeffs
+        self._drop_device_state()
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        if self.boundary_coeffs is None:
+            return super()._evaluate_gram(ctx, kernel, kernel_parameter, nugget, nugget_type)
+        T, ratio = ctx.assemble_bc(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.boundary_coeffs, nugget, nugget_type)
+        return T, [ratio]
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
         ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
         if nugget_type == 'adaptive':
             self.ratio = ratios[0]
+
+    def _fields_bc(self, X_test, which):
+        return get_context().extend_functionals_bc(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                   self.boundary_coeffs, self._coeff(self._dL, self.sol_vec), which=which)
+
+    def extend_sol(self, X_test):
+        if self.boundary_coeffs is None:
+            return super().extend_sol(X_test)
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = self._fields_bc(X_test, ('value',)).download().reshape(-1)
+
+    def _derivative_fields(self, X_test):
+        if self.boundary_coeffs is None:
+            return super()._derivative_fields(X_test)
+        return {'u': self._fields_bc(X_test, self._deriv_names)}
+
+    def boundary_residual(self, X_bt, coeffs_t, g_t):
+        """c0 u + c1 u_x1 + c2 u_x2 - g of the GP solution at the points X_bt (n,2), with coeffs_t (n,3) = (c0, c1, c2) and g_t (n,) given
+        per point: how well the boundary condition holds between the boundary collocation points (numpy array, also `bdy_residual`)."""
+        X_bt = onp.asarray(X_bt, dtype=onp.float64).reshape(-1, 2)
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64).reshape(-1, 3)
+        g_t = onp.asarray(g_t, dtype=onp.float64).ravel()
+        if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
+            raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
+        names = ('value', 'd1', 'd2')
+        if self.boundary_coeffs is None:
+            d = get_context().extend_functionals(self._layout, self.kernel, self.kernel_parameter, X_bt, self.X_domain, self.X_boundary,
+                                                 self._coeff(self._dL, self.sol_vec), which=names)
+        else:
+            d = self._fields_bc(X_bt, names)
+        r = self._rows(d, names)
+        self.bdy_residual = coeffs_t[:, 0] * r['value'] + coeffs_t[:, 1] * r['d1'] + coeffs_t[:, 2] * r['d2'] - g_t
+        return self.bdy_residual
 
     def GN_loss(self, z, z_old):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)

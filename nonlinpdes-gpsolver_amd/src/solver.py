@@ -6,11 +6,24 @@ from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
 from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
 
+
+def _bc_lines(c):
+    """header line of a non-Dirichlet boundary operator (nothing for Dirichlet: the reference's header)"""
+    bc = getattr(c, 'bc', 'dirichlet')
+    if bc == 'neumann':
+        return ['[Boundary condition] Neumann: du/dn = g']
+    if bc == 'robin':
+        return [f"[Boundary condition] Robin: beta*u + du/dn = g, beta = {getattr(c, 'robin_beta', 1.0)}"]
+    return []
+
+
 # PDE_type -> (factory, header lines printed by set_equation)
 _EQUATIONS = {
     'Nonlinear_elliptic': (
-        lambda c, **k: Nonlinear_elliptic2d(alpha=c.alpha, m=c.m, **k),
-        lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'],
+        # (cfg.bc / cfg.robin_beta: Neumann / Robin boundary operator; configurations without them are Dirichlet, as in the reference)
+        lambda c, **k: Nonlinear_elliptic2d(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'),
+                                            robin_beta=getattr(c, 'robin_beta', 1.0), **k),
+        lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'] + _bc_lines(c),
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
     'Nonlinear_elliptic3d': (
         lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, **k),
