@@ -75,7 +75,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -157,6 +157,37 @@ int gpk_assemble_bc(gpk_handle h, int kernel, const double* host_kparams, const 
  * past Nt untouched.  Fixed reduction order: a repeated call gives bit-identical output.  No reference call site. */
 int gpk_extend_functionals_bc(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                               const double* Xd, int Nd, const double* Xb, int Nb, const double* bc,
+                              const double* coeff, int fmask, double* out, int ldo);
+/* ---- Variable-coefficient operator on the domain points of the 2-D elliptic layout ("Variable-coefficient operator"):
+ *      -psi[u] + alpha u^m = f with psi_i = c0 delta + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2 at domain point i.
+ *      No reference call site (the reference solves -Laplace(u) + alpha u^m = f only).
+ *      op (Nd,6) row-major on the device: row i = (c0, b1, b2, a11, a12, a22) of psi_i; a12 multiplies d_1 d_2 ONCE (a symmetric
+ *      tensor A enters as a12 = 2 A12).  op == NULL: the Laplacian (0,0,0,1,0,1) at every domain point.  bc (Nb,3) / NULL: the
+ *      boundary functionals of gpk_assemble_bc.  Layout as GPK_LAYOUT_ELLIPTIC: block 0 = psi on the Nd domain points, block 1 = delta
+ *      on the domain points and phi_b on the boundary points, N = 2Nd+Nb, Theta N x N with leading dimension ld >= N -- so gpk_potrf,
+ *      the GPK_GN_ELLIPTIC system and gpk_pde_residual apply unchanged (psi[u] takes the place of the Laplacian).
+ *      Nugget as gpk_assemble's.  host_ratio (one double, may be NULL): trace(block 0) / trace(block 1) with the values at d = 0,
+ *        <psi,psi> = c0^2 + p1 b1^2 + p2 b2^2 + 3 p1^2 a11^2 + 3 p2^2 a22^2 + p1 p2 (a12^2 + 2 a11 a22) - 2 c0 (p1 a11 + p2 a22),
+ *        <phi,phi> = c0^2 + p1 c1^2 + p2 c2^2 (1 at a domain point),
+ *      written for every nugget type; both point sums are taken on the host in index order (op / bc != NULL: one small device-to-host
+ *      copy each, synchronises).  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte stores
+ *      otherwise; nothing outside the N x N view is written); the launch is timed like gpk_assemble's when the per-phase timing is on
+ *      (gpk_prof_read_assembly). */
+int gpk_assemble_op(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                    const double* op, const double* bc, double nugget, int nugget_type, double* Theta, int ld, double* host_ratio);
+/* The six monomial derivatives of the extension under op / bc at test points Xt (Nt,2), matrix-free: coeff (2Nd+Nb) = Theta^{-1} sol_vec
+ * with the Theta of gpk_assemble_op for the same op and bc.  fmask: a non-empty subset of the GPK_OPFN_* bits below (anything else:
+ * -9001); out is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.
+ * Fixed reduction order: a repeated call gives bit-identical output, and a row has the same bits whichever other rows are requested.
+ * psi_t[u] at a test point is a combination of the rows, formed by the caller. */
+#define GPK_OPFN_VALUE 1      /* u */
+#define GPK_OPFN_D1    2      /* du/dx1 */
+#define GPK_OPFN_D2    4      /* du/dx2 */
+#define GPK_OPFN_D11   8      /* d^2u/dx1^2 */
+#define GPK_OPFN_D12  16      /* d^2u/dx1dx2 */
+#define GPK_OPFN_D22  32      /* d^2u/dx2^2 */
+int gpk_extend_functionals_op(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                              const double* Xd, int Nd, const double* Xb, int Nb, const double* op, const double* bc,
                               const double* coeff, int fmask, double* out, int ldo);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the

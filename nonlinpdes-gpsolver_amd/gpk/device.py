@@ -14,6 +14,7 @@ KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1}
 NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
+FUNCTIONAL_OP = {'value': 1, 'd1': 2, 'd2': 4, 'd11': 8, 'd12': 16, 'd22': 32}   # GPK_OPFN_* bits of gpk_extend_functionals_op
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
 
 
@@ -466,6 +467,62 @@ class Context:
         self._chk(self.lib.gpk_extend_functionals_bc(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
                                                      dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dbc.ptr if dbc is not None else None,
                                                      dc.ptr, mask, full.ptr, full.ld))
+        order = sorted(bits)
+        if bits == order:
+            out = full
+        else:                                                             # the caller's order
+            out = DeviceArray(self, len(bits), Nt, ld=Nt)
+            for k, b in enumerate(bits):
+                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
+        self.synchronize()
+        return out
+
+    # ---- variable-coefficient operator on the domain points of the 2-D elliptic layout (gpk_assemble_op, gpk_extend_functionals_op) ----
+    def _domain_coeffs(self, op, Nd):
+        """(Nd,6) coefficients (c0, b1, b2, a11, a12, a22) of the domain functionals on the device, or None (= NULL: the Laplacian)"""
+        if op is None:
+            return None
+        op = np.ascontiguousarray(op, dtype=np.float64)
+        if op.shape != (Nd, 6):
+            raise ValueError(f'domain coefficients must have shape ({Nd}, 6): (c0, b1, b2, a11, a12, a22) per domain point, got {op.shape}')
+        return DeviceArray(self, Nd, 6, ld=6).upload(op)
+
+    def assemble_op(self, kernel, kernel_parameter, Xd, Xb, op, bc, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 2-D elliptic layout with the functional op[i] = (c0, b1, b2, a11, a12, a22) -> c0 delta + b1 d/dx1 +
+        b2 d/dx2 + a11 d2/dx1^2 + a12 d2/dx1dx2 + a22 d2/dx2^2 at domain point i (op = None: the Laplacian) and bc[b] at boundary point b
+        as in assemble_bc: (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any
+        leading dimension >= N)."""
+        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 2 * Nd + Nb
+        dXd, dXb, dop, dbc = self.points(Xd), self.points(Xb), self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratio = C.c_double()
+        self._chk(self.lib.gpk_assemble_op(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
+                                           dop.ptr if dop is not None else None, dbc.ptr if dbc is not None else None, float(nugget),
+                                           NUGGET[nugget_type], T.ptr, T.ld, C.byref(ratio)))
+        self.synchronize()
+        return T, ratio.value
+
+    def extend_functionals_op(self, kernel, kernel_parameter, Xt, Xd, Xb, op, bc, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
+        """Value / derivatives up to order two of the extension under the domain functionals op and the boundary functionals bc at Xt
+        (gpk_extend_functionals_op): a (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP).
+        coeff = Theta^{-1} sol_vec with the Theta of assemble_op."""
+        which = tuple(which)
+        bits = [FUNCTIONAL_OP[w] for w in which]
+        if len(set(bits)) != len(bits):
+            raise ValueError(f'extend_functionals_op: repeated functional in {which!r}')
+        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 2); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
+        dXt, dXd, dXb = self.points(Xt), self.points(Xd), self.points(Xb)
+        dop, dbc = self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)
+        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
+        mask = sum(bits)
+        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
+        self._chk(self.lib.gpk_extend_functionals_op(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
+                                                     dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dop.ptr if dop is not None else None,
+                                                     dbc.ptr if dbc is not None else None, dc.ptr, mask, full.ptr, full.ld))
         order = sorted(bits)
         if bits == order:
             out = full

@@ -4,7 +4,10 @@ Same command line as the reference's main_NonLinElliptic2d.py (README.md:15 of t
     python main_NonLinElliptic2d.py --kernel Gaussian --kernel_parameter 0.2 --nugget 1e-13 --N_domain 900 --N_boundary 124 --GNsteps 4
 The manufactured solution's right-hand side is written out analytically (the reference differentiates u with jax.grad).
 --bc neumann / --bc robin [--robin_beta B] (no counterpart in the reference) prescribe du/dn = g or B u + du/dn = g on the boundary
-instead of u = g, with g formed from the manufactured solution's gradient and the outward normal."""
+instead of u = g, with g formed from the manufactured solution's gradient and the outward normal.
+--operator advection_diffusion (no counterpart in the reference either) solves -div(a grad u) + v . grad u + c u + alpha*u^m = f with the
+fields of advection_diffusion_fields() below and the right-hand side that makes the same u* the solution; --operator laplace (the
+default) is the equation above.  --bc works with either."""
 import argparse
 
 import numpy as onp
@@ -22,6 +25,7 @@ def parse(argv=None):
     parser.add_argument("--pen_lambda", type=float, default=1e-10)      # for the relaxation approach
     parser.add_argument("--bc", type=str, default='dirichlet', choices=['dirichlet', 'neumann', 'robin'])
     parser.add_argument("--robin_beta", type=float, default=1.0)        # beta of --bc robin: beta u + du/dn = g
+    parser.add_argument("--operator", type=str, default='laplace', choices=['laplace', 'advection_diffusion'])
     add_gn_and_logs(parser, 'rdm', 4, method_choices=['elimination', 'relaxation'])
     return parser.parse_args(argv)
 
@@ -46,6 +50,37 @@ def manufactured_gradient(x1, x2):
             pi * onp.sin(pi * x1) * onp.cos(pi * x2) + 8 * pi * onp.sin(4 * pi * x1) * onp.cos(4 * pi * x2))
 
 
+def advection_diffusion_fields(x1, x2):
+    """(a, a_x1, a_x2, v1, v2, c) of --operator advection_diffusion: diffusivity a = 2 + sin(pi x1) cos(pi x2) in [1, 3] with its gradient,
+    a rotating velocity v = (1 + x2, 1 - x1) and the reaction coefficient c = 1 + x1^2 >= 1"""
+    pi = onp.pi
+    x1 = onp.asarray(x1, dtype=onp.float64); x2 = onp.asarray(x2, dtype=onp.float64)
+    return (2 + onp.sin(pi * x1) * onp.cos(pi * x2), pi * onp.cos(pi * x1) * onp.cos(pi * x2), -pi * onp.sin(pi * x1) * onp.sin(pi * x2),
+            1 + x2, 1 - x1, 1 + x1 ** 2)
+
+
+def advection_diffusion(x1, x2):
+    """the callable `operator` of Nonlinear_elliptic2d for those fields: six coefficient arrays of psi with -psi[u] = -div(a grad u) + v . grad u + c u"""
+    from src.PDEs import divergence_form
+    return divergence_form(*advection_diffusion_fields(x1, x2))
+
+
+OPERATORS = {'laplace': None, 'advection_diffusion': advection_diffusion}
+
+
+def manufactured_operator_rhs(alpha, m):
+    """f = -div(a grad u*) + v . grad u* + c u* + alpha u*^m for u* of manufactured() and the fields above"""
+    pi = onp.pi
+    u, _ = manufactured(alpha, m)
+
+    def f(x1, x2):
+        a, a1, a2, v1, v2, c = advection_diffusion_fields(x1, x2)
+        u1, u2 = manufactured_gradient(x1, x2)
+        lap = -2 * pi ** 2 * onp.sin(pi * x1) * onp.sin(pi * x2) - 64 * pi ** 2 * onp.sin(4 * pi * x1) * onp.sin(4 * pi * x2)
+        return -(a * lap + a1 * u1 + a2 * u2) + v1 * u1 + v2 * u2 + c * u(x1, x2) + alpha * (u(x1, x2) ** m)
+    return f
+
+
 def boundary_data(u, bc, robin_beta, domain=UNIT_SQUARE):
     """the callback bdy(x1, x2) = value of the boundary operator on u*: u* itself (dirichlet), du*/dn (neumann), beta u* + du*/dn (robin)"""
     if bc == 'dirichlet':
@@ -64,6 +99,9 @@ def boundary_data(u, bc, robin_beta, domain=UNIT_SQUARE):
 def main(argv=None):
     cfg = parse(argv)
     u, f = manufactured(cfg.alpha, cfg.m)
+    if cfg.operator != 'laplace':
+        f = manufactured_operator_rhs(cfg.alpha, cfg.m)
+        cfg.operator = OPERATORS[cfg.operator]                           # the facade takes the callable (or 'laplace' / None: the Laplacian)
     solver, show = solve_forward(cfg, "Nonlinear_elliptic", boundary_data(u, cfg.bc, cfg.robin_beta), f, UNIT_SQUARE,
                                  solve_kwargs={'method': cfg.method, 'pen_lambda': cfg.pen_lambda}, verbose=cfg.print_hist)
     Xd = solver.eqn.X_domain

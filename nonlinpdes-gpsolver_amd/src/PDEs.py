@@ -19,6 +19,14 @@ from .sample_points import boundary_normals, sampled_pts_grid, sampled_pts_grid3
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
 
 
+def divergence_form(a, a_x1, a_x2, v1, v2, c):
+    """The six coefficients (c0, b1, b2, a11, a12, a22) of psi = a Laplace + (grad a - v) . grad - c, for which
+    -psi[u] = -div(a grad u) + v . grad u + c u: scalar diffusivity a with gradient (a_x1, a_x2), velocity (v1, v2), reaction c
+    (arrays over the points, or scalars).  What Nonlinear_elliptic2d(operator=...) returns for an advection-diffusion-reaction operator."""
+    a, a_x1, a_x2, v1, v2, c = onp.broadcast_arrays(*(onp.asarray(t, dtype=onp.float64) for t in (a, a_x1, a_x2, v1, v2, c)))
+    return -c, a_x1 - v1, a_x2 - v2, a, onp.zeros_like(a), a
+
+
 class _GPEquation(object):
     """Machinery shared by the three PDE classes (and by InverseProblems.Darcy_flow2d)."""
     _layout = None              # Gram layout name
@@ -267,17 +275,24 @@ class _GPEquation(object):
 
 
 class Nonlinear_elliptic2d(_GPEquation):
-    """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208)."""
+    """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208); with operator=... / set_domain_operator() the semilinear
+    equation -psi[u] + alpha*u^m = f for any second-order linear operator psi with variable coefficients (no counterpart in the reference)."""
     _layout = 'Nonlinear_elliptic'
     _system = 'Nonlinear_elliptic'
 
     _BC = ('dirichlet', 'neumann', 'robin')
 
-    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0):
+    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
+                 operator=None):
         """bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
         g = B u is what `bdy(x1, x2)` returns -- 'dirichlet' B u = u; 'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the
         outward unit normal (sample_points.boundary_normals).  set_boundary_operator() takes an arbitrary first-order operator per
-        boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went."""
+        boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went.
+        operator (no counterpart in the reference either): a callable operator(x1, x2) returning the six coefficient arrays
+        (c0, b1, b2, a11, a12, a22) of psi = c0 + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2; the equation solved is then
+        -psi[u] + alpha u^m = f (divergence_form() gives the coefficients of -div(a grad u) + v . grad u + c u; a12 multiplies the mixed
+        derivative once).  Evaluated at the domain points when they are set and at the test points by PDE_residual.  None: the
+        Laplacian, and every call goes the way it always went."""
         if bc not in self._BC:
             raise ValueError(f'bc {bc!r}: one of {self._BC}')
         self.alpha = alpha
@@ -288,6 +303,10 @@ class Nonlinear_elliptic2d(_GPEquation):
         self.bc = bc
         self.robin_beta = robin_beta
         self.boundary_coeffs = None
+        if operator is not None and not callable(operator):
+            raise ValueError(f'operator {operator!r}: a callable operator(x1, x2) returning six coefficient arrays, or None')
+        self.operator = operator
+        self.domain_coeffs = None
 
     def _gn_params(self):
         return float(self.alpha), float(self.m), 0.0
@@ -300,6 +319,27 @@ class Nonlinear_elliptic2d(_GPEquation):
             n = boundary_normals(self.X_boundary, self.domain)
             beta = float(self.robin_beta) if self.bc == 'robin' else 0.0
             self.boundary_coeffs = onp.concatenate([onp.full((self.N_boundary, 1), beta), n], axis=1)
+        self.domain_coeffs = None                          # likewise
+        if self.operator is not None:
+            self.domain_coeffs = self._operator_at(self.X_domain)
+
+    # ---- domain operator: (N_domain, 6) coefficients (c0, b1, b2, a11, a12, a22) of psi, or None = the Laplacian, today's path ----
+    def _operator_at(self, X):
+        """the callable `operator` at the points X (n,2) as an (n,6) array"""
+        rows = self.operator(X[:, 0], X[:, 1])
+        if len(rows) != 6:
+            raise ValueError(f'operator must return six coefficient arrays (c0, b1, b2, a11, a12, a22), got {len(rows)}')
+        return onp.stack([onp.broadcast_to(onp.asarray(r, dtype=onp.float64), (X.shape[0],)) for r in rows], axis=1)
+
+    def set_domain_operator(self, coeffs):
+        """Row i of coeffs (N_domain, 6) = (c0, b1, b2, a11, a12, a22): the equation at domain point i reads -psi_i[u] + alpha u^m = rhs_f[i]
+        with psi_i = c0 + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2.  Call after the points are set; dropped when they
+        change.  Discards the Gram matrix and everything derived from it."""
+        coeffs = onp.array(coeffs, dtype=onp.float64)
+        if coeffs.shape != (self.N_domain, 6):
+            raise ValueError(f'coeffs must have shape ({self.N_domain}, 6), got {coeffs.shape}')
+        self.domain_coeffs = coeffs
+        self._drop_device_state()
 
     def set_boundary_operator(self, coeffs):
         """Row b of coeffs (N_boundary, 3) = (c0, c1, c2): the condition at boundary point b reads c0 u + c1 u_x1 + c2 u_x2 = bdy_g[b].
@@ -311,6 +351,10 @@ class Nonlinear_elliptic2d(_GPEquation):
         self._drop_device_state()
 
     def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        if self.domain_coeffs is not None:
+            T, ratio = ctx.assemble_op(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs, self.boundary_coeffs,
+                                       nugget, nugget_type)
+            return T, [ratio]
         if self.boundary_coeffs is None:
             return super()._evaluate_gram(ctx, kernel, kernel_parameter, nugget, nugget_type)
         T, ratio = ctx.assemble_bc(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.boundary_coeffs, nugget, nugget_type)
@@ -325,18 +369,62 @@ class Nonlinear_elliptic2d(_GPEquation):
         return get_context().extend_functionals_bc(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
                                                    self.boundary_coeffs, self._coeff(self._dL, self.sol_vec), which=which)
 
+    _op_names = ('value', 'd1', 'd2', 'd11', 'd12', 'd22')      # rows of gpk_extend_functionals_op
+
+    def _fields_op(self, X_test, which):
+        return get_context().extend_functionals_op(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                   self.domain_coeffs, self.boundary_coeffs, self._coeff(self._dL, self.sol_vec),
+                                                   which=which)
+
     def extend_sol(self, X_test):
-        if self.boundary_coeffs is None:
+        if self.boundary_coeffs is None and self.domain_coeffs is None:
             return super().extend_sol(X_test)
         X_test = onp.asarray(X_test, dtype=onp.float64)
         self.X_test = X_test
         self.N_test = X_test.shape[0]
-        self.extended_sol = self._fields_bc(X_test, ('value',)).download().reshape(-1)
+        fields = self._fields_op if self.domain_coeffs is not None else self._fields_bc
+        self.extended_sol = fields(X_test, ('value',)).download().reshape(-1)
 
-    def _derivative_fields(self, X_test):
+    def _derivative_fields(self, X_test, coeffs_t=None):
+        """with a domain operator: rows value, d1, d2 and psi_t[u] (in the Laplacian's place), psi_t from coeffs_t (Nt,6) or the callable"""
+        if self.domain_coeffs is not None:
+            if coeffs_t is None:
+                if self.operator is None:
+                    raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
+                                     'points as coeffs_t (Nt,6)')
+                coeffs_t = self._operator_at(X_test)
+            coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
+            if coeffs_t.shape != (X_test.shape[0], 6):
+                raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, 6), got {coeffs_t.shape}')
+            rows = self._fields_op(X_test, self._op_names).download().reshape(6, -1)
+            psi = (coeffs_t.T * rows).sum(axis=0)                 # psi_t[u]: a combination of the six rows, per test point
+            return {'u': get_context().array(onp.stack([rows[0], rows[1], rows[2], psi]))}
         if self.boundary_coeffs is None:
             return super()._derivative_fields(X_test)
         return {'u': self._fields_bc(X_test, self._deriv_names)}
+
+    def extend_derivatives(self, X_test):
+        """as the base class; with a domain operator additionally d11, d12, d22 (laplacian = d11 + d22)"""
+        if self.domain_coeffs is None:
+            return super().extend_derivatives(X_test)
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        r = self._rows(self._fields_op(X_test, self._op_names), self._op_names)
+        self.extended_derivatives = {'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'laplacian': r['d11'] + r['d22'],
+                                     'd11': r['d11'], 'd12': r['d12'], 'd22': r['d22']}
+        return self.extended_derivatives
+
+    def PDE_residual(self, X_test, coeffs_t=None):
+        """pointwise residual at X_test; with a domain operator -psi_t[u] + alpha u^m - f, psi_t from the callable `operator` or from
+        coeffs_t (Nt,6) (needed when the operator was set per point; ValueError otherwise)"""
+        if self.domain_coeffs is None:
+            if coeffs_t is not None:
+                raise ValueError('coeffs_t given, but no domain operator is set')
+            return super().PDE_residual(X_test)
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        fields = self._derivative_fields(X_test, coeffs_t)
+        rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
+        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields['u'], None, rhs).download().reshape(-1)
+        return self.test_residual
 
     def boundary_residual(self, X_bt, coeffs_t, g_t):
         """c0 u + c1 u_x1 + c2 u_x2 - g of the GP solution at the points X_bt (n,2), with coeffs_t (n,3) = (c0, c1, c2) and g_t (n,) given
@@ -347,7 +435,9 @@ class Nonlinear_elliptic2d(_GPEquation):
         if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
             raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
         names = ('value', 'd1', 'd2')
-        if self.boundary_coeffs is None:
+        if self.domain_coeffs is not None:
+            d = self._fields_op(X_bt, names)
+        elif self.boundary_coeffs is None:
             d = get_context().extend_functionals(self._layout, self.kernel, self.kernel_parameter, X_bt, self.X_domain, self.X_boundary,
                                                  self._coeff(self._dL, self.sol_vec), which=names)
         else:

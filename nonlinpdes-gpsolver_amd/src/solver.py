@@ -7,6 +7,24 @@ from .InverseProblems import Darcy_flow2d
 from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
 
 
+def _operator_of(c):
+    """cfg.operator as the equation class takes it: a callable operator(x1, x2) -> six coefficient arrays, or None for the Laplacian
+    (absent, None, or the name 'laplace', which is what a driver's command line leaves there by default)"""
+    op = getattr(c, 'operator', None)
+    if op is None or (isinstance(op, str) and op == 'laplace'):
+        return None
+    if not callable(op):
+        raise ValueError(f"cfg.operator {op!r}: a callable operator(x1, x2), None or 'laplace'")
+    return op
+
+
+def _operator_lines(c):
+    """header line of a variable-coefficient domain operator (nothing for the Laplacian: the reference's header)"""
+    if _operator_of(c) is not None:
+        return ['[Domain operator] - psi[u] + alpha*u^m = f, psi a second-order operator with variable coefficients given by the user']
+    return []
+
+
 def _bc_lines(c):
     """header line of a non-Dirichlet boundary operator (nothing for Dirichlet: the reference's header)"""
     bc = getattr(c, 'bc', 'dirichlet')
@@ -20,10 +38,12 @@ def _bc_lines(c):
 # PDE_type -> (factory, header lines printed by set_equation)
 _EQUATIONS = {
     'Nonlinear_elliptic': (
-        # (cfg.bc / cfg.robin_beta: Neumann / Robin boundary operator; configurations without them are Dirichlet, as in the reference)
+        # (cfg.bc / cfg.robin_beta: Neumann / Robin boundary operator; configurations without them are Dirichlet, as in the reference;
+        #  cfg.operator: a callable operator(x1, x2) -> six coefficient arrays, or None / absent = the Laplacian, as in the reference)
         lambda c, **k: Nonlinear_elliptic2d(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'),
-                                            robin_beta=getattr(c, 'robin_beta', 1.0), **k),
-        lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'] + _bc_lines(c),
+                                            robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c), **k),
+        lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'] + _operator_lines(c)
+        + _bc_lines(c),
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
     'Nonlinear_elliptic3d': (
         lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, **k),
