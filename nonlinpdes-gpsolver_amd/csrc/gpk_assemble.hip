@@ -14,17 +14,16 @@
 // fixed (row functional, column functional, row point) the 64 lanes of a wave store 512 contiguous bytes; the row
 // point is wave-uniform (scalar loads, no LDS needed: 16 B per point).  No symmetry trick: the ALU cost per pair
 // (~1 exp + ~60 flops) is >10x below the HBM write time of its 32..128 output bytes.
-#include "gpk_common.h"
+//
+// The functional tables, the Hermite evaluation (hermite_plain), the frame of the extension kernel, the 16-byte store and the host side
+// of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.
+#include "gpk_assemble_common.h"
+
+using namespace gpk_asm;
 
 namespace {
 
-enum { F_DELTA = 0, F_D1 = 1, F_D2 = 2, F_DD2 = 3, F_LAP = 4 };
-
-// multi-index lists of the five functionals
-__host__ __device__ constexpr int f_count(int f) { return f == F_LAP ? 2 : 1; }
-__host__ __device__ constexpr int f_a1(int f, int i) { return f == F_D1 ? 1 : (f == F_LAP && i == 0 ? 2 : 0); }
-__host__ __device__ constexpr int f_a2(int f, int i) { return f == F_D2 ? 1 : (f == F_DD2 ? 2 : (f == F_LAP && i == 1 ? 2 : 0)); }
-
+// plain accumulation: the compiler may contract (gpk_assemble_bc.hip has the explicit-fma form, which rounds differently on purpose)
 template <int FX, int FY>
 __host__ __device__ __forceinline__ double pair_coeff(const double (&a)[5], const double (&b)[5]) {
     double s = 0.0;
@@ -39,16 +38,6 @@ __host__ __device__ __forceinline__ double pair_coeff(const double (&a)[5], cons
         }
     }
     return s;
-}
-
-__host__ __device__ __forceinline__ void hermite(double p, double d, double (&h)[5]) {
-    const double q = p * d;
-    const double q2 = q * q;
-    h[0] = 1.0;
-    h[1] = q;
-    h[2] = q2 - p;
-    h[3] = q * (q2 - 3.0 * p);
-    h[4] = q2 * (q2 - 6.0 * p) + 3.0 * p * p;
 }
 
 // layouts: functional of each Theta block and whether it lives on domain points only (0) or domain+boundary (1)
@@ -68,8 +57,6 @@ struct AsmArgs {
     const double* tx; int Nt;             // test mode: (Nt,2) row-major test points
     const double* coeff;                  // extend mode
 };
-
-constexpr int TP = 32;                    // row points per workgroup
 
 __global__ void pack_points_kernel(const double* __restrict__ Xd, int Nd, const double* __restrict__ Xb, int Nb,
                                    double* __restrict__ px, double* __restrict__ py) {
@@ -99,8 +86,8 @@ __device__ __forceinline__ void store_row(const AsmArgs& g, int p, int q, const 
 
 // Two column points per lane, one 16-byte store per (row functional, column functional, row point): a wave writes 1 KB contiguous
 // per store instruction and issues half as many of them.  Needs every block offset, the leading dimension and the base address to
-// be even multiples of 8 bytes (checked by the launcher; otherwise the one-point-per-lane kernel below runs).
-typedef double asm_d2 __attribute__((ext_vector_type(2)));
+// be even multiples of 8 bytes (checked by the launcher; otherwise the one-point-per-lane kernel below runs).  NT: the store policy of
+// store2 (gpk_tune key 55; all four are instantiated here, see the table at gpk_assemble below).
 
 template <int L, int BI, int BJ, int NT>
 __device__ __forceinline__ void store_block2(const AsmArgs& g, int p, int q, const double (&a0)[5], const double (&b0)[5], double e0,
@@ -109,15 +96,7 @@ __device__ __forceinline__ void store_block2(const AsmArgs& g, int p, int q, con
         double v0 = pair_coeff<Lay<L>::f[BI], Lay<L>::f[BJ]>(a0, b0) * e0;
         double v1 = pair_coeff<Lay<L>::f[BI], Lay<L>::f[BJ]>(a1, b1) * e1;
         if (BI == BJ) { if (p == q) v0 += g.nug[BI]; if (p == q + 1) v1 += g.nug[BI]; }
-        asm_d2* dst = reinterpret_cast<asm_d2*>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q);
-        // NT (gpk_tune key 55): Theta is written once and not read by this kernel -- a non-temporal store (global_store_dwordx4 ... nt)
-        // tells L2 / the Infinity Cache not to keep the line
-        // (2 / 3: write-through scopes sc0 sc1 without / with nt, inline asm -- measured next to it, see the table at gpk_assemble below)
-        const asm_d2 v = (asm_d2){v0, v1};
-        if (NT == 1) __builtin_nontemporal_store(v, dst);
-        else if (NT == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(v) : "memory");
-        else if (NT == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" :: "v"(dst), "v"(v) : "memory");
-        else *dst = v;
+        store2<NT>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q, v0, v1);
     }
 }
 
@@ -147,8 +126,8 @@ __global__ __launch_bounds__(256) void assemble2_kernel(AsmArgs g) {
         const double e0 = exp(-0.5 * (g.p1 * d1a * d1a + g.p2 * d2a * d2a));
         const double e1 = exp(-0.5 * (g.p1 * d1b * d1b + g.p2 * d2b * d2b));
         double a0[5], b0[5], a1[5], b1[5];
-        hermite(g.p1, d1a, a0); hermite(g.p2, d2a, b0);
-        hermite(g.p1, d1b, a1); hermite(g.p2, d2b, b1);
+        hermite_plain(g.p1, d1a, a0); hermite_plain(g.p2, d2a, b0);
+        hermite_plain(g.p1, d1b, a1); hermite_plain(g.p2, d2b, b1);
         store_row2<L, 0, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
         if (Lay<L>::nb > 1) store_row2<L, 1, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
         if (Lay<L>::nb > 2) store_row2<L, 2, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
@@ -169,8 +148,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(AsmArgs g) {
         const double d1 = x1 - y1, d2 = x2 - y2;
         const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
         double a[5], b[5];
-        hermite(g.p1, d1, a);
-        hermite(g.p2, d2, b);
+        hermite_plain(g.p1, d1, a);
+        hermite_plain(g.p2, d2, b);
         store_row<L, 0>(g, p, q, a, b, e);
         if (Lay<L>::nb > 1) store_row<L, 1>(g, p, q, a, b, e);
         if (Lay<L>::nb > 2) store_row<L, 2>(g, p, q, a, b, e);
@@ -195,8 +174,8 @@ __global__ __launch_bounds__(256) void assemble_test_kernel(AsmArgs g) {
         const double d1 = g.tx[2 * t] - y1, d2 = g.tx[2 * t + 1] - y2;
         const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
         double a[5], b[5];
-        hermite(g.p1, d1, a);
-        hermite(g.p2, d2, b);
+        hermite_plain(g.p1, d1, a);
+        hermite_plain(g.p2, d2, b);
         store_test<L, 0>(g, t, q, a, b, e);
         if (Lay<L>::nb > 1) store_test<L, 1>(g, t, q, a, b, e);
         if (Lay<L>::nb > 2) store_test<L, 2>(g, t, q, a, b, e);
@@ -220,8 +199,8 @@ __global__ __launch_bounds__(256) void extend_kernel(AsmArgs g) {
         const double d1 = x1 - g.px[q], d2 = x2 - g.py[q];
         const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
         double a[5], b[5];
-        hermite(g.p1, d1, a);
-        hermite(g.p2, d2, b);
+        hermite_plain(g.p1, d1, a);
+        hermite_plain(g.p2, d2, b);
         double v = acc_test<L, 0>(g, q, a, b);
         if (Lay<L>::nb > 1) v += acc_test<L, 1>(g, q, a, b);
         if (Lay<L>::nb > 2) v += acc_test<L, 2>(g, q, a, b);
@@ -240,9 +219,7 @@ __global__ __launch_bounds__(256) void extend_kernel(AsmArgs g) {
 // <= 2 and so has every column functional: the pair needs h0..h4 only, and ONE exp + one pair of Hermite evaluations feeds all of them.
 // Mapping: a workgroup owns FN_TT test points (wave-uniform: scalar loads) and its 256 lanes stride over the column points as in
 // extend_kernel; each column point's coordinates and its nb coefficient slices are loaded once and serve all FN_TT test points, and each
-// lane keeps FN_TT x popcount(MASK) accumulators.  Reduction: wave shuffles, then LDS across the 4 waves, in a fixed order (no atomics).
-constexpr int FN_TT = 4;                  // test points per workgroup
-
+// lane keeps FN_TT x popcount(MASK) accumulators.  Points, zeroing and reduction: the frame of gpk_assemble_common.h.
 struct FnArgs {
     const double* px; const double* py;   // SoA column points (fill_common)
     int M;
@@ -252,10 +229,6 @@ struct FnArgs {
     const double* coeff;
     double* out; long ldo;
 };
-
-__host__ __device__ constexpr int fn_popc(int m) { return m ? (m & 1) + fn_popc(m >> 1) : 0; }
-// output row of functional F under MASK: the number of set bits below bit F
-__host__ __device__ constexpr int fn_row(int mask, int f) { return fn_popc(mask & ((1 << f) - 1)); }
 
 // sum_b pair_coeff<F, f[b]> c[b] (c[b] = 0 outside block b, as acc_test in extend_kernel)
 template <int L, int F>
@@ -275,19 +248,10 @@ __device__ __forceinline__ void fn_acc(double (&s)[fn_popc(MASK)], const double 
 template <int L, int MASK>
 __global__ __launch_bounds__(256) void extend_fn_kernel(FnArgs g) {
     constexpr int NF = fn_popc(MASK);
-    __shared__ double red[4][FN_TT * NF];
     const int t0 = blockIdx.x * FN_TT;
-    double x1[FN_TT], x2[FN_TT];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i) {                 // past the end: repeat the last point (computed, never stored)
-        const int t = min(t0 + i, g.Nt - 1);
-        x1[i] = g.tx[2 * t]; x2[i] = g.tx[2 * t + 1];
-    }
-    double s[FN_TT][NF];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) s[i][k] = 0.0;
+    double x1[FN_TT], x2[FN_TT], s[FN_TT][NF];
+    GPK_FN_LOAD_POINTS2(x1, x2, g.tx, t0, g.Nt);
+    fn_zero(s);
     for (int q = threadIdx.x; q < g.M; q += 256) {
         const double y1 = g.px[q], y2 = g.py[q];
         double c[4];
@@ -298,8 +262,8 @@ __global__ __launch_bounds__(256) void extend_fn_kernel(FnArgs g) {
             const double d1 = x1[i] - y1, d2 = x2[i] - y2;
             const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
             double a[5], b[5];
-            hermite(g.p1, d1, a);
-            hermite(g.p2, d2, b);
+            hermite_plain(g.p1, d1, a);
+            hermite_plain(g.p2, d2, b);
             fn_acc<L, MASK, F_DELTA>(s[i], a, b, c, e);
             fn_acc<L, MASK, F_D1>(s[i], a, b, c, e);
             fn_acc<L, MASK, F_D2>(s[i], a, b, c, e);
@@ -307,28 +271,13 @@ __global__ __launch_bounds__(256) void extend_fn_kernel(FnArgs g) {
             fn_acc<L, MASK, F_LAP>(s[i], a, b, c, e);
         }
     }
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) {
-            double v = s[i][k];
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i * NF + k] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < FN_TT * NF) {
-        const int i = threadIdx.x / NF, k = threadIdx.x % NF, t = t0 + i;
-        if (t < g.Nt) g.out[k * g.ldo + t] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    }
+    GPK_FN_REDUCE_STORE(s, NF, t0, g.Nt, g.out, g.ldo);
 }
 
-// one instantiation per (layout, mask): a functional that is not requested costs nothing
-template <int L, int MASK = 1>
+// one instantiation per (layout, mask)
+template <int L>
 void launch_extend_fn(int mask, int grid, hipStream_t st, const FnArgs& g) {
-    if constexpr (MASK <= 31) {
-        if (mask == MASK) extend_fn_kernel<L, MASK><<<grid, 256, 0, st>>>(g);
-        else launch_extend_fn<L, MASK + 1>(mask, grid, st, g);
-    }
+    with_mask<31>(mask, [&](auto m) { extend_fn_kernel<L, decltype(m)::value><<<grid, 256, 0, st>>>(g); });
 }
 
 // r = residual of the equation at each test point from the extension's rows: the relations the Gauss-Newton systems eliminate
@@ -353,45 +302,49 @@ __global__ __launch_bounds__(256) void pde_residual_kernel(int sys, double p0, d
     out[t] = r;
 }
 
-template <int L> void fill_layout(AsmArgs& g, int Nd, int Nb) {
-    int o = 0;
-    for (int b = 0; b < 4; ++b) {
-        g.size[b] = b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0;
-        g.off[b] = o;
-        o += g.size[b];
+// f(std::integral_constant<int, L>) for the layout id: the one place that turns it into a template argument; false: not a layout
+template <class F>
+bool with_layout(int layout, F&& f) {
+    switch (layout) {
+        case GPK_LAYOUT_ELLIPTIC: f(std::integral_constant<int, GPK_LAYOUT_ELLIPTIC>{}); return true;
+        case GPK_LAYOUT_BURGERS:  f(std::integral_constant<int, GPK_LAYOUT_BURGERS>{}); return true;
+        case GPK_LAYOUT_EIKONAL:  f(std::integral_constant<int, GPK_LAYOUT_EIKONAL>{}); return true;
+        case GPK_LAYOUT_DARCY_A:  f(std::integral_constant<int, GPK_LAYOUT_DARCY_A>{}); return true;
+        default: return false;
     }
 }
 
-int fill_common(gpk_handle h, AsmArgs& g, int layout, int kernel, const double* kp, const double* Xd, int Nd,
-                const double* Xb, int Nb) {
+template <int L> constexpr int lay_size(int b, int Nd, int Nb) { return b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0; }
+template <int L> constexpr int lay_N(int Nd, int Nb) { return lay_size<L>(0, Nd, Nb) + lay_size<L>(1, Nd, Nb) + lay_size<L>(2, Nd, Nb) + lay_size<L>(3, Nd, Nb); }
+
+// precisions, block offsets / sizes and the packed points: the fields AsmArgs and FnArgs share (the others are the caller's)
+template <class Args>
+int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd) return gpk_bad_arg(h, "assemble: sizes/pointers");
-    if (kernel == GPK_KERNEL_GAUSSIAN) { g.p1 = g.p2 = 1.0 / (kp[0] * kp[0]); }                 // src/kernels.py:12-13
-    else if (kernel == GPK_KERNEL_ANISOTROPIC) { g.p1 = 2.0 / (kp[0] * kp[0]); g.p2 = 2.0 / (kp[1] * kp[1]); }   // :95-99
-    else return gpk_bad_arg(h, "assemble: kernel id");
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: fill_layout<GPK_LAYOUT_ELLIPTIC>(g, Nd, Nb); break;
-        case GPK_LAYOUT_BURGERS:  fill_layout<GPK_LAYOUT_BURGERS>(g, Nd, Nb); break;
-        case GPK_LAYOUT_EIKONAL:  fill_layout<GPK_LAYOUT_EIKONAL>(g, Nd, Nb); break;
-        case GPK_LAYOUT_DARCY_A:  fill_layout<GPK_LAYOUT_DARCY_A>(g, Nd, Nb); break;
-        default: return gpk_bad_arg(h, "assemble: layout id");
-    }
+    double p[2];
+    GPK_TRY(precisions(h, "assemble: kernel id", kernel, kp, 2, p));
+    g.p1 = p[0]; g.p2 = p[1];
+    const bool known = with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        int o = 0;
+        for (int b = 0; b < 4; ++b) { g.size[b] = lay_size<L>(b, Nd, Nb); g.off[b] = o; o += g.size[b]; }
+    });
+    if (!known) return gpk_bad_arg(h, "assemble: layout id");
     const int Mall = Nd + Nb;
     GPK_TRY(gpk_i_ensure_points(h, 2 * (size_t)Mall));
     g.px = h->d_pts; g.py = h->d_pts + Mall;
     pack_points_kernel<<<gpk_ceil_div(Mall, 256), 256, 0, h->stream>>>(Xd, Nd, Xb, Nb, h->d_pts, h->d_pts + Mall);
     GPK_LAUNCH_CHECK(h);
-    g.Nd = Nd;
     g.M = (layout == GPK_LAYOUT_DARCY_A) ? Nd : Mall;
-    for (int b = 0; b < 4; ++b) g.nug[b] = 0.0;
-    g.tx = nullptr; g.Nt = 0; g.coeff = nullptr;
+    if constexpr (std::is_same<Args, AsmArgs>::value) g.Nd = Nd;
     return 0;
 }
 
 // value of <f, f> at d = 0 (SURVEY §8a-K last column): makes the adaptive trace ratios analytic
 template <int L> void diag_values(double p1, double p2, double (&c)[4]) {
     double a[5], b[5];
-    hermite(p1, 0.0, a);
-    hermite(p2, 0.0, b);
+    hermite_plain(p1, 0.0, a);
+    hermite_plain(p2, 0.0, b);
     c[0] = pair_coeff<Lay<L>::f[0], Lay<L>::f[0]>(a, b);
     c[1] = pair_coeff<Lay<L>::f[1], Lay<L>::f[1]>(a, b);
     c[2] = pair_coeff<Lay<L>::f[2], Lay<L>::f[2]>(a, b);
@@ -405,68 +358,38 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
                             const double* Xb, int Nb, double nugget, int nugget_type, double* Theta, int ld,
                             double* ratios) {
     if (!h || !Theta) return GPK_ERR_ARG;
-    AsmArgs g;
+    AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
-    const int nb = (layout == GPK_LAYOUT_ELLIPTIC) ? 2 : (layout == GPK_LAYOUT_DARCY_A ? 3 : 4);
-    const int N = g.off[nb - 1] + g.size[nb - 1];
-    if (ld < N) return gpk_bad_arg(h, "assemble: ld < N");
+    int nb = 0, N = 0;
     double c[4] = {0, 0, 0, 0};
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: diag_values<GPK_LAYOUT_ELLIPTIC>(g.p1, g.p2, c); break;
-        case GPK_LAYOUT_BURGERS:  diag_values<GPK_LAYOUT_BURGERS>(g.p1, g.p2, c); break;
-        case GPK_LAYOUT_EIKONAL:  diag_values<GPK_LAYOUT_EIKONAL>(g.p1, g.p2, c); break;
-        case GPK_LAYOUT_DARCY_A:  diag_values<GPK_LAYOUT_DARCY_A>(g.p1, g.p2, c); break;
-    }
+    with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        nb = Lay<L>::nb; N = lay_N<L>(Nd, Nb);
+        diag_values<L>(g.p1, g.p2, c);
+    });
+    if (ld < N) return gpk_bad_arg(h, "assemble: ld < N");
     // ratio_k = trace(block k) / trace(last block)   (src/PDEs.py:62-66, 256-262, 397-402; IP.py:72-87)
     double r[4] = {0, 0, 0, 1.0};
     const double tr_last = (double)g.size[nb - 1] * c[nb - 1];
     for (int b = 0; b < nb - 1; ++b) r[b] = ((double)g.size[b] * c[b]) / tr_last;
     if (ratios) { ratios[0] = ratios[1] = ratios[2] = 0.0; for (int b = 0; b < nb - 1; ++b) ratios[b] = r[b]; }
-    for (int b = 0; b < nb; ++b) {
-        if (nugget_type == GPK_NUGGET_ADAPTIVE) g.nug[b] = nugget * (b == nb - 1 ? 1.0 : r[b]);
-        else if (nugget_type == GPK_NUGGET_IDENTITY) g.nug[b] = nugget;
-        else if (nugget_type == GPK_NUGGET_NONE) g.nug[b] = 0.0;
-        else return gpk_bad_arg(h, "assemble: nugget_type");
-    }
+    if (!nugget_type_valid(nugget_type)) return gpk_bad_arg(h, "assemble: nugget_type");
+    for (int b = 0; b < nb; ++b) g.nug[b] = block_nugget(nugget_type, nugget, b == nb - 1 ? 1.0 : r[b]);
     g.out = Theta; g.ld = ld;
-    // two column points per lane (16-byte stores) when every pair (q, q + 1) stays inside one block and is 16-byte aligned
-    bool pairs = h->tune.asm_pairs && (ld % 2 == 0) && (((uintptr_t)Theta & 15) == 0) && (g.M % 2 == 0);
-    for (int b = 0; b < nb; ++b) pairs = pairs && (g.off[b] % 2 == 0) && (g.size[b] % 2 == 0);
-    // (per-phase timing on: HIP events around the evaluator launch alone -- the point packing and the host work above stay outside)
-    if (h->prof) {
-        if (!h->asm_ev[0]) for (int i = 0; i < 2; ++i) GPK_HIP(h, hipEventCreate(&h->asm_ev[i]));
-        GPK_HIP(h, hipEventRecord(h->asm_ev[0], h->stream));
-    }
-    struct AsmStop {
-        gpk_handle h; ~AsmStop() { if (h->prof && h->asm_ev[1]) h->asm_timed = hipEventRecord(h->asm_ev[1], h->stream) == hipSuccess; }
-    } asm_stop{h};
-    if (pairs) {
-        dim3 grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
-        auto launch = [&](auto nt_c) {
-            constexpr int NT = decltype(nt_c)::value;
-            switch (layout) {
-                case GPK_LAYOUT_ELLIPTIC: assemble2_kernel<GPK_LAYOUT_ELLIPTIC, NT><<<grid2, 256, 0, h->stream>>>(g); break;
-                case GPK_LAYOUT_BURGERS:  assemble2_kernel<GPK_LAYOUT_BURGERS, NT><<<grid2, 256, 0, h->stream>>>(g); break;
-                case GPK_LAYOUT_EIKONAL:  assemble2_kernel<GPK_LAYOUT_EIKONAL, NT><<<grid2, 256, 0, h->stream>>>(g); break;
-                case GPK_LAYOUT_DARCY_A:  assemble2_kernel<GPK_LAYOUT_DARCY_A, NT><<<grid2, 256, 0, h->stream>>>(g); break;
-            }
-        };
-        switch (h->tune.asm_nt) {
-            case 1: launch(std::integral_constant<int, 1>{}); break;
-            case 2: launch(std::integral_constant<int, 2>{}); break;
-            case 3: launch(std::integral_constant<int, 3>{}); break;
-            default: launch(std::integral_constant<int, 0>{}); break;
+    const bool pairs = pairs_eligible(h, Theta, ld, g.M, g.size[0], g.size[1], g.size[2], g.size[3]);   // (even sizes: even offsets)
+    TimedLaunch timed(h);
+    GPK_TRY(timed.start());
+    with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP)), grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
+        if (!pairs) assemble_kernel<L><<<grid, 256, 0, h->stream>>>(g);
+        else switch (h->tune.asm_nt) {
+            case 1: assemble2_kernel<L, 1><<<grid2, 256, 0, h->stream>>>(g); break;
+            case 2: assemble2_kernel<L, 2><<<grid2, 256, 0, h->stream>>>(g); break;
+            case 3: assemble2_kernel<L, 3><<<grid2, 256, 0, h->stream>>>(g); break;
+            default: assemble2_kernel<L, 0><<<grid2, 256, 0, h->stream>>>(g); break;
         }
-        GPK_LAUNCH_CHECK(h);
-        return 0;
-    }
-    dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP));
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: assemble_kernel<GPK_LAYOUT_ELLIPTIC><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_BURGERS:  assemble_kernel<GPK_LAYOUT_BURGERS><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_EIKONAL:  assemble_kernel<GPK_LAYOUT_EIKONAL><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_DARCY_A:  assemble_kernel<GPK_LAYOUT_DARCY_A><<<grid, 256, 0, h->stream>>>(g); break;
-    }
+    });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -474,16 +397,11 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
 extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const double* kp, const double* Xt, int Nt,
                                  const double* Xd, int Nd, const double* Xb, int Nb, double* out, int ld) {
     if (!h || !out || !Xt || Nt <= 0) return GPK_ERR_ARG;
-    AsmArgs g;
+    AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
-    dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: assemble_test_kernel<GPK_LAYOUT_ELLIPTIC><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_BURGERS:  assemble_test_kernel<GPK_LAYOUT_BURGERS><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_EIKONAL:  assemble_test_kernel<GPK_LAYOUT_EIKONAL><<<grid, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_DARCY_A:  assemble_test_kernel<GPK_LAYOUT_DARCY_A><<<grid, 256, 0, h->stream>>>(g); break;
-    }
+    const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
+    with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -530,15 +448,10 @@ extern "C" int gpk_error_metrics(gpk_handle h, int n, const double* truth, const
 extern "C" int gpk_extend(gpk_handle h, int layout, int kernel, const double* kp, const double* Xt, int Nt,
                           const double* Xd, int Nd, const double* Xb, int Nb, const double* coeff, double* out) {
     if (!h || !out || !Xt || !coeff || Nt <= 0) return GPK_ERR_ARG;
-    AsmArgs g;
+    AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = 0; g.tx = Xt; g.Nt = Nt; g.coeff = coeff;
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: extend_kernel<GPK_LAYOUT_ELLIPTIC><<<Nt, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_BURGERS:  extend_kernel<GPK_LAYOUT_BURGERS><<<Nt, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_EIKONAL:  extend_kernel<GPK_LAYOUT_EIKONAL><<<Nt, 256, 0, h->stream>>>(g); break;
-        case GPK_LAYOUT_DARCY_A:  extend_kernel<GPK_LAYOUT_DARCY_A><<<Nt, 256, 0, h->stream>>>(g); break;
-    }
+    with_layout(layout, [&](auto l) { extend_kernel<decltype(l)::value><<<Nt, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -551,19 +464,10 @@ extern "C" int gpk_extend_functionals(gpk_handle h, int layout, int kernel, cons
     if (fmask <= 0 || fmask > 31) return gpk_bad_arg(h, "extend_functionals: fmask must be a non-empty subset of the GPK_FN_* bits");
     if (Nt <= 0) return gpk_bad_arg(h, "extend_functionals: Nt <= 0");
     if (ldo < Nt) return gpk_bad_arg(h, "extend_functionals: ldo < Nt");
-    AsmArgs a;
-    GPK_TRY(fill_common(h, a, layout, kernel, kp, Xd, Nd, Xb, Nb));
     FnArgs g;
-    g.px = a.px; g.py = a.py; g.M = a.M; g.p1 = a.p1; g.p2 = a.p2;
-    for (int b = 0; b < 4; ++b) { g.off[b] = a.off[b]; g.size[b] = a.size[b]; }
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
-    const int grid = gpk_ceil_div(Nt, FN_TT);
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: launch_extend_fn<GPK_LAYOUT_ELLIPTIC>(fmask, grid, h->stream, g); break;
-        case GPK_LAYOUT_BURGERS:  launch_extend_fn<GPK_LAYOUT_BURGERS>(fmask, grid, h->stream, g); break;
-        case GPK_LAYOUT_EIKONAL:  launch_extend_fn<GPK_LAYOUT_EIKONAL>(fmask, grid, h->stream, g); break;
-        case GPK_LAYOUT_DARCY_A:  launch_extend_fn<GPK_LAYOUT_DARCY_A>(fmask, grid, h->stream, g); break;
-    }
+    with_layout(layout, [&](auto l) { launch_extend_fn<decltype(l)::value>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

@@ -7,14 +7,19 @@
 //
 // Math (DESIGN.md §K "Three dimensions").  kappa = exp(-(p1 d1^2 + p2 d2^2 + p3 d3^2)/2), d = x - y.  With the 1-D Hermite factors
 //   h0 = 1, h1 = p d, h2 = p^2 d^2 - p, h3 = p^3 d^3 - 3 p^2 d, h4 = p^4 d^4 - 6 p^3 d^2 + 3 p^2
-// of gpk_assemble.hip every mixed partial is  d_x^alpha d_y^beta kappa = (-1)^{|alpha|} prod_k h_{alpha_k+beta_k}(p_k, d_k) kappa.
+// (hermite_plain of gpk_assemble_common.h) every mixed partial is  d_x^alpha d_y^beta kappa = (-1)^{|alpha|} prod_k h_{alpha_k+beta_k}(p_k, d_k) kappa.
 // Layout ELLIPTIC3D: block 0 = Laplacian = {(2,0,0), (0,2,0), (0,0,2)} on the Nd domain points, block 1 = delta on the Nd+Nb
 // domain+boundary points, N = 2 Nd + Nb; <Lap, Lap> has nine terms.  One exp and three Hermite evaluations per POINT PAIR feed all
 // four blocks.
 //
 // Mapping to the hardware, as in 2-D: SoA-packed points in the handle's point scratch, a workgroup owns TP row points x 256 column
 // points (two-point variant: x 512), lane <-> column point, the row point is wave-uniform (scalar loads).  No inline assembly.
-#include "gpk_common.h"
+//
+// Shared with the other evaluators (gpk_assemble_common.h): hermite_plain, the frame of the extension kernel, store2 and the host side
+// of a call (precisions, nugget, timing, launch).
+#include "gpk_assemble_common.h"
+
+using namespace gpk_asm;
 
 namespace {
 
@@ -41,16 +46,6 @@ __host__ __device__ __forceinline__ double pair_coeff3(const double (&a)[5], con
     return s;
 }
 
-__host__ __device__ __forceinline__ void hermite(double p, double d, double (&h)[5]) {
-    const double q = p * d;
-    const double q2 = q * q;
-    h[0] = 1.0;
-    h[1] = q;
-    h[2] = q2 - p;
-    h[3] = q * (q2 - 3.0 * p);
-    h[4] = q2 * (q2 - 6.0 * p) + 3.0 * p * p;
-}
-
 __host__ __device__ __forceinline__ double kappa3(double p1, double p2, double p3, double d1, double d2, double d3) {
     return exp(-0.5 * (p1 * d1 * d1 + p2 * d2 * d2 + p3 * d3 * d3));
 }
@@ -66,8 +61,6 @@ struct Asm3Args {
     int off[2]; int size[2];
     double nug[2];
 };
-
-constexpr int TP = 32;                    // row points per workgroup
 
 __global__ void pack_points3_kernel(const double* __restrict__ Xd, int Nd, const double* __restrict__ Xb, int Nb,
                                     double* __restrict__ px, double* __restrict__ py, double* __restrict__ pz) {
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void assemble3d_kernel(Asm3Args g) {
         const double d1 = x1 - y1, d2 = x2 - y2, d3 = x3 - y3;
         const double e = kappa3(g.p1, g.p2, g.p3, d1, d2, d3);
         double a[5], b[5], c[5];
-        hermite(g.p1, d1, a); hermite(g.p2, d2, b); hermite(g.p3, d3, c);
+        hermite_plain(g.p1, d1, a); hermite_plain(g.p2, d2, b); hermite_plain(g.p3, d3, c);
         if (p < g.size[0]) {                                          // wave-uniform
             store_block<0, 0>(g, p, q, a, b, c, e);
             store_block<0, 1>(g, p, q, a, b, c, e);
@@ -111,7 +104,6 @@ __global__ __launch_bounds__(256) void assemble3d_kernel(Asm3Args g) {
 // Two column points per lane, one 16-byte store per (row functional, column functional, row point): a wave writes 1 KB contiguous
 // per store instruction and issues half as many of them.  Needs every block offset and size, the leading dimension and the base
 // address to be even multiples of 8 bytes (checked by the launcher; otherwise the one-point-per-lane kernel above runs).
-typedef double asm3_d2 __attribute__((ext_vector_type(2)));
 
 struct Pair3 { double a[5], b[5], c[5], e; };
 
@@ -121,11 +113,7 @@ __device__ __forceinline__ void store_block2(const Asm3Args& g, int p, int q, co
         double v0 = pair_coeff3<LAY_F[BI], LAY_F[BJ]>(u0.a, u0.b, u0.c) * u0.e;
         double v1 = pair_coeff3<LAY_F[BI], LAY_F[BJ]>(u1.a, u1.b, u1.c) * u1.e;
         if (BI == BJ) { if (p == q) v0 += g.nug[BI]; if (p == q + 1) v1 += g.nug[BI]; }
-        asm3_d2* dst = reinterpret_cast<asm3_d2*>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q);
-        const asm3_d2 v = (asm3_d2){v0, v1};
-        // NT (gpk_tune key 55 = 1): Theta is written once and not read by this kernel -- a non-temporal store
-        if (NT) __builtin_nontemporal_store(v, dst);
-        else *dst = v;
+        store2<NT>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q, v0, v1);   // NT: 0 plain, 1 non-temporal (gpk_tune key 55)
     }
 }
 
@@ -144,12 +132,12 @@ __global__ __launch_bounds__(256) void assemble3d2_kernel(Asm3Args g) {
         {
             const double d1 = x1 - y1a, d2 = x2 - y2a, d3 = x3 - y3a;
             u0.e = kappa3(g.p1, g.p2, g.p3, d1, d2, d3);
-            hermite(g.p1, d1, u0.a); hermite(g.p2, d2, u0.b); hermite(g.p3, d3, u0.c);
+            hermite_plain(g.p1, d1, u0.a); hermite_plain(g.p2, d2, u0.b); hermite_plain(g.p3, d3, u0.c);
         }
         {
             const double d1 = x1 - y1b, d2 = x2 - y2b, d3 = x3 - y3b;
             u1.e = kappa3(g.p1, g.p2, g.p3, d1, d2, d3);
-            hermite(g.p1, d1, u1.a); hermite(g.p2, d2, u1.b); hermite(g.p3, d3, u1.c);
+            hermite_plain(g.p1, d1, u1.a); hermite_plain(g.p2, d2, u1.b); hermite_plain(g.p3, d3, u1.c);
         }
         if (p < g.size[0]) {                                          // wave-uniform
             store_block2<0, 0, NT>(g, p, q, u0, u1);
@@ -163,12 +151,11 @@ __global__ __launch_bounds__(256) void assemble3d2_kernel(Asm3Args g) {
 // ---- multi-functional extension (DESIGN.md §K "Three dimensions") ----------------------------------------------------------------
 // out[k][t] = sum_b sum_q pair_coeff3<F_k, f[b]>(h(p1,d1), h(p2,d2), h(p3,d3)) kappa(d) c[off_b + q], d = x_t - y_q, F_k over the
 // functionals of the mask.  Row and column functionals have per-axis order <= 2: h0..h4 suffice and ONE exp serves every requested
-// functional.  Mapping as extend_fn_kernel of gpk_assemble.hip: a workgroup owns FN_TT test points (wave-uniform), its 256 lanes
+// functional.  Mapping as every extension kernel (the frame of gpk_assemble_common.h): a workgroup owns FN_TT test points (wave-uniform), its 256 lanes
 // stride over the column points, each lane keeps FN_TT x popcount(mask) accumulators; reduction by wave shuffles, then LDS across
 // the 4 waves, in a fixed order (no atomics: a repeated call gives bit-identical output).
 // CM is the COMPACT mask: bit k set = functional k of {delta, d1, d2, Laplacian, d3} -- the GPK_FN_* bits in ascending order with the
 // unused bit GPK_FN_D2D2 squeezed out -- so output row order = ascending GPK_FN_* bit order.
-constexpr int FN_TT = 4;                  // test points per workgroup
 constexpr int CM_F[5] = {G_DELTA, G_D1, G_D2, G_LAP, G_D3};
 
 struct Fn3Args {
@@ -180,9 +167,6 @@ struct Fn3Args {
     double* out; long ldo;
 };
 
-__host__ __device__ constexpr int fn_popc(int m) { return m ? (m & 1) + fn_popc(m >> 1) : 0; }
-__host__ __device__ constexpr int fn_row(int mask, int k) { return fn_popc(mask & ((1 << k) - 1)); }
-
 template <int CM, int K>
 __device__ __forceinline__ void fn_acc(double (&s)[fn_popc(CM)], const double (&a)[5], const double (&b)[5], const double (&c)[5],
                                        double cl, double cd, double e) {
@@ -193,19 +177,10 @@ __device__ __forceinline__ void fn_acc(double (&s)[fn_popc(CM)], const double (&
 template <int CM>
 __global__ __launch_bounds__(256) void extend_fn3d_kernel(Fn3Args g) {
     constexpr int NF = fn_popc(CM);
-    __shared__ double red[4][FN_TT * NF];
     const int t0 = blockIdx.x * FN_TT;
-    double x1[FN_TT], x2[FN_TT], x3[FN_TT];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i) {                 // past the end: repeat the last point (computed, never stored)
-        const int t = min(t0 + i, g.Nt - 1);
-        x1[i] = g.tx[3 * t]; x2[i] = g.tx[3 * t + 1]; x3[i] = g.tx[3 * t + 2];
-    }
-    double s[FN_TT][NF];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) s[i][k] = 0.0;
+    double x1[FN_TT], x2[FN_TT], x3[FN_TT], s[FN_TT][NF];
+    GPK_FN_LOAD_POINTS3(x1, x2, x3, g.tx, t0, g.Nt);
+    fn_zero(s);
     for (int q = threadIdx.x; q < g.M; q += 256) {
         const double y1 = g.px[q], y2 = g.py[q], y3 = g.pz[q];
         const double cl = q < g.Nd ? g.coeff[q] : 0.0;               // Laplacian block: domain points only
@@ -215,7 +190,7 @@ __global__ __launch_bounds__(256) void extend_fn3d_kernel(Fn3Args g) {
             const double d1 = x1[i] - y1, d2 = x2[i] - y2, d3 = x3[i] - y3;
             const double e = kappa3(g.p1, g.p2, g.p3, d1, d2, d3);
             double a[5], b[5], c[5];
-            hermite(g.p1, d1, a); hermite(g.p2, d2, b); hermite(g.p3, d3, c);
+            hermite_plain(g.p1, d1, a); hermite_plain(g.p2, d2, b); hermite_plain(g.p3, d3, c);
             fn_acc<CM, 0>(s[i], a, b, c, cl, cd, e);
             fn_acc<CM, 1>(s[i], a, b, c, cl, cd, e);
             fn_acc<CM, 2>(s[i], a, b, c, cl, cd, e);
@@ -223,37 +198,19 @@ __global__ __launch_bounds__(256) void extend_fn3d_kernel(Fn3Args g) {
             fn_acc<CM, 4>(s[i], a, b, c, cl, cd, e);
         }
     }
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) {
-            double v = s[i][k];
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i * NF + k] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < FN_TT * NF) {
-        const int i = threadIdx.x / NF, k = threadIdx.x % NF, t = t0 + i;
-        if (t < g.Nt) g.out[k * g.ldo + t] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    }
+    GPK_FN_REDUCE_STORE(s, NF, t0, g.Nt, g.out, g.ldo);
 }
 
-// one instantiation per compact mask (31): a functional that is not requested costs nothing
-template <int CM = 1>
+// one instantiation per compact mask (31)
 void launch_extend_fn3d(int cm, int grid, hipStream_t st, const Fn3Args& g) {
-    if constexpr (CM <= 31) {
-        if (cm == CM) extend_fn3d_kernel<CM><<<grid, 256, 0, st>>>(g);
-        else launch_extend_fn3d<CM + 1>(cm, grid, st, g);
-    }
+    with_mask<31>(cm, [&](auto m) { extend_fn3d_kernel<decltype(m)::value><<<grid, 256, 0, st>>>(g); });
 }
 
 // precisions, packed points
 int fill_common3(gpk_handle h, const char* who, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb,
                  double (&p)[3], const double** px, const double** py, const double** pz) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd || (Nb > 0 && !Xb)) return gpk_bad_arg(h, who);
-    if (kernel == GPK_KERNEL_GAUSSIAN) { p[0] = p[1] = p[2] = 1.0 / (kp[0] * kp[0]); }
-    else if (kernel == GPK_KERNEL_ANISOTROPIC) { for (int k = 0; k < 3; ++k) p[k] = 2.0 / (kp[k] * kp[k]); }   // no factor 1/2: the reference's convention
-    else return gpk_bad_arg(h, "assemble3d: kernel id");
+    GPK_TRY(precisions(h, "assemble3d: kernel id", kernel, kp, 3, p));
     const int Mall = Nd + Nb;
     GPK_TRY(gpk_i_ensure_points(h, 3 * (size_t)Mall));
     *px = h->d_pts; *py = h->d_pts + Mall; *pz = h->d_pts + 2 * (size_t)Mall;
@@ -268,8 +225,7 @@ int fill_common3(gpk_handle h, const char* who, int kernel, const double* kp, co
 extern "C" int gpk_assemble3d(gpk_handle h, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb,
                               double nugget, int nugget_type, double* Theta, int ld, double* host_ratio) {
     if (!h || !Theta) return GPK_ERR_ARG;
-    if (nugget_type != GPK_NUGGET_NONE && nugget_type != GPK_NUGGET_IDENTITY && nugget_type != GPK_NUGGET_ADAPTIVE)
-        return gpk_bad_arg(h, "assemble3d: nugget_type");
+    if (!nugget_type_valid(nugget_type)) return gpk_bad_arg(h, "assemble3d: nugget_type");
     if ((long)2 * Nd + Nb > 0x7fffffffL) return gpk_bad_arg(h, "assemble3d: N exceeds int");
     Asm3Args g;
     double p[3];
@@ -285,30 +241,9 @@ extern "C" int gpk_assemble3d(gpk_handle h, int kernel, const double* kp, const 
     const long double c0 = 3.0L * (q1 * q1 + q2 * q2 + q3 * q3) + 2.0L * (q1 * q2 + q1 * q3 + q2 * q3);
     const double r0 = (double)(((long double)g.size[0] * c0) / (long double)g.size[1]);   // trace(block 0) / trace(block 1)
     if (host_ratio) *host_ratio = r0;
-    g.nug[0] = nugget_type == GPK_NUGGET_ADAPTIVE ? nugget * r0 : (nugget_type == GPK_NUGGET_IDENTITY ? nugget : 0.0);
-    g.nug[1] = nugget_type == GPK_NUGGET_NONE ? 0.0 : nugget;
+    two_block_nugget(nugget_type, nugget, r0, g.nug);
     g.out = Theta; g.ld = ld;
-    // two column points per lane (16-byte stores) when every pair (q, q + 1) stays inside one block and is 16-byte aligned
-    const bool pairs = h->tune.asm_pairs && (ld % 2 == 0) && (((uintptr_t)Theta & 15) == 0) && (Nd % 2 == 0) && (Nb % 2 == 0);
-    // (per-phase timing on: HIP events around the evaluator launch alone, as in gpk_assemble -- gpk_prof_read_assembly reads them)
-    if (h->prof) {
-        if (!h->asm_ev[0]) for (int i = 0; i < 2; ++i) GPK_HIP(h, hipEventCreate(&h->asm_ev[i]));
-        GPK_HIP(h, hipEventRecord(h->asm_ev[0], h->stream));
-    }
-    struct AsmStop {
-        gpk_handle h; ~AsmStop() { if (h->prof && h->asm_ev[1]) h->asm_timed = hipEventRecord(h->asm_ev[1], h->stream) == hipSuccess; }
-    } asm_stop{h};
-    if (pairs) {
-        dim3 grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
-        // key 55: 0 plain, 1 non-temporal; the write-through variants 2 / 3 of the 2-D evaluator are inline assembly and not offered here (plain)
-        if (h->tune.asm_nt == 1) assemble3d2_kernel<1><<<grid2, 256, 0, h->stream>>>(g);
-        else assemble3d2_kernel<0><<<grid2, 256, 0, h->stream>>>(g);
-    } else {
-        dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP));
-        assemble3d_kernel<<<grid, 256, 0, h->stream>>>(g);
-    }
-    GPK_LAUNCH_CHECK(h);
-    return 0;
+    return launch_two_block(h, pairs_eligible(h, Theta, ld, Nd, Nb), g, assemble3d_kernel, assemble3d2_kernel<0>, assemble3d2_kernel<1>);
 }
 
 extern "C" int gpk_extend_functionals3d(gpk_handle h, int kernel, const double* kp, const double* Xt, int Nt,
@@ -329,7 +264,7 @@ extern "C" int gpk_extend_functionals3d(gpk_handle h, int kernel, const double* 
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
     // compact mask: value, d1, d2 keep bits 0..2; Laplacian (16) -> bit 3, d3 (32) -> bit 4
     const int cm = (fmask & 7) | ((fmask & GPK_FN_LAPLACIAN) ? 8 : 0) | ((fmask & GPK_FN_D3) ? 16 : 0);
-    launch_extend_fn3d<>(cm, gpk_ceil_div(Nt, FN_TT), h->stream, g);
+    launch_extend_fn3d(cm, gpk_ceil_div(Nt, FN_TT), h->stream, g);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

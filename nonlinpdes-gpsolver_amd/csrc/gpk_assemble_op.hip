@@ -19,9 +19,13 @@
 // Mapping to the hardware, as assemble_bc_kernel / assemble_bc2_kernel: SoA-packed points and coefficients in the handle's point
 // scratch (2 + 3 + 6 arrays of Nd+Nb), a workgroup owns TP row points x 256 column points (two-point variant: x 512), lane <-> column
 // point (its coordinates and nine coefficients stay in registers), the row point and its coefficients are wave-uniform (scalar loads).
-#include "gpk_common.h"
+//
+// Shared with the other evaluators (gpk_assemble_common.h): hermite_compensated and kappa2_fma (with gpk_assemble_bc.hip: the same
+// bits there), the frame of the extension kernel, store2 and the host side of a call (precisions, nugget, boundary trace, timing,
+// launch).
+#include "gpk_assemble_common.h"
 
-#include <vector>
+using namespace gpk_asm;
 
 // One-point and two-point evaluator must give the same bits for the same point pair: explicit fma, no contraction by the compiler
 // (whether it contracts a * b + c depends on the uses of the product after inlining, which differ between the two).  The extension
@@ -34,23 +38,6 @@ namespace {
 __host__ __device__ constexpr int mi(int m1, int m2) { return m1 == 0 ? (m2 == 0 ? 0 : (m2 == 1 ? 2 : 5)) : (m1 == 1 ? (m2 == 0 ? 1 : 4) : 3); }
 __host__ __device__ constexpr int mi_a1(int f) { return f == 1 || f == 4 ? 1 : (f == 3 ? 2 : 0); }
 __host__ __device__ constexpr int mi_a2(int f) { return f == 2 || f == 4 ? 1 : (f == 5 ? 2 : 0); }
-
-// h2 = q^2 - p and h3 = q (q^2 - 3p), q = p d, cancel near q^2 = p and q^2 = 3p; an entry here can consist of one such factor alone
-// (<d11, delta'> = h2 kappa), so both brackets carry the rounding errors of q and q^2 along (explicit fma: exact error of a product),
-// the compensated form of gpk_assemble_bc.hip.  h4 stays plain.
-__host__ __device__ __forceinline__ void hermite(double p, double d, double (&h)[5]) {
-    const double q = p * d;
-    const double qe = __builtin_fma(p, d, -q);                    // p d = q + qe exactly
-    const double q2 = q * q;
-    const double q2e = __builtin_fma(2.0 * q, qe, __builtin_fma(q, q, -q2));   // (p d)^2 = q2 + q2e up to second order
-    const double t = 3.0 * p;
-    const double te = __builtin_fma(3.0, p, -t);                  // 3 p = t + te exactly
-    h[0] = 1.0;
-    h[1] = q;
-    h[2] = (q2 - p) + q2e;
-    h[3] = q * ((q2 - t) + (q2e - te));
-    h[4] = __builtin_fma(q2, q2 - 6.0 * p, 3.0 * p * p);
-}
 
 // C[mi(m1,m2)] = sum_j k_j a[m1 + b1_j] b[m2 + b2_j] for the second-order column functional k (MI order), axis 1 first:
 //   A0[m1] = k0 a[m1] + k1 a[m1+1] + k3 a[m1+2]   (the parts without d_2),  A1[m1] = k2 a[m1] + k4 a[m1+1]  (d_2),  A2[m1] = k5 a[m1]  (d_22)
@@ -99,8 +86,6 @@ struct OpArgs {
     double nug[2];
 };
 
-constexpr int TP = 32;                    // row points per workgroup
-
 // domain point i: phi = (1,0,0), psi = op[6i..6i+5] or the Laplacian (0,0,0,1,0,1) when op == NULL; boundary point b: phi = bc[3b..3b+2]
 // or (1,0,0) when bc == NULL, psi = 0 (never used)
 __global__ void pack_op_kernel(const double* __restrict__ Xd, int Nd, const double* __restrict__ Xb, int Nb, const double* __restrict__ op,
@@ -127,9 +112,9 @@ struct PairOp {
     double cf[6], cp[6], e;               // tables of phi' and of psi' (cp: set when the column is a domain point)
     __device__ __forceinline__ void eval(double p1, double p2, double d1, double d2, const double (&k)[3], const double (&ko)[6], bool dom) {
         double a[5], b[5];
-        e = exp(-0.5 * __builtin_fma(p2 * d2, d2, p1 * d1 * d1));
-        hermite(p1, d1, a);
-        hermite(p2, d2, b);
+        e = kappa2_fma(p1, p2, d1, d2);
+        hermite_compensated(p1, d1, a);
+        hermite_compensated(p2, d2, b);
         table_phi(a, b, k, cf);
         if (dom) table_psi<>(a, b, ko, cp);
     }
@@ -174,15 +159,7 @@ __global__ __launch_bounds__(256) void assemble_op_kernel(OpArgs g) {
 
 // Two column points per lane, one 16-byte store per (row block, column block, row point).  Needs Nd, Nb and the leading dimension
 // even and a 16-byte aligned base (checked by the launcher; otherwise the one-point-per-lane kernel above runs).
-typedef double op_d2 __attribute__((ext_vector_type(2)));
-
-template <int NT>
-__device__ __forceinline__ void store2(double* dst, double v0, double v1) {
-    const op_d2 v = (op_d2){v0, v1};
-    // NT (gpk_tune key 55 = 1): Theta is written once and not read by this kernel -- a non-temporal store
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<op_d2*>(dst));
-    else *reinterpret_cast<op_d2*>(dst) = v;
-}
+// NT: the policy of store2 (0 plain, 1 non-temporal).
 
 template <int NT>
 __global__ __launch_bounds__(256) void assemble_op2_kernel(OpArgs g) {
@@ -227,7 +204,6 @@ __global__ __launch_bounds__(256) void assemble_op2_kernel(OpArgs g) {
 // (-1)^{|alpha_f|} C[f] kappa, the same operations whichever other rows are requested.  Each lane keeps FN_TT x popcount(MASK)
 // accumulators.  Reduction by wave shuffles, then LDS across the 4 waves, in a fixed order (no atomics: a repeated call gives
 // bit-identical output).
-constexpr int FN_TT = 4;                  // test points per workgroup
 
 struct FnOpArgs {
     const double* px; const double* py;
@@ -240,25 +216,13 @@ struct FnOpArgs {
     double* out; long ldo;
 };
 
-__host__ __device__ constexpr int fn_popc(int m) { return m ? (m & 1) + fn_popc(m >> 1) : 0; }
-__host__ __device__ constexpr int fn_row(int mask, int f) { return fn_popc(mask & ((1 << f) - 1)); }
-
 template <int MASK>
 __global__ __launch_bounds__(256) void extend_fn_op_kernel(FnOpArgs g) {
     constexpr int NF = fn_popc(MASK);
-    __shared__ double red[4][FN_TT * NF];
     const int t0 = blockIdx.x * FN_TT;
-    double x1[FN_TT], x2[FN_TT];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i) {                 // past the end: repeat the last point (computed, never stored)
-        const int t = min(t0 + i, g.Nt - 1);
-        x1[i] = g.tx[2 * t]; x2[i] = g.tx[2 * t + 1];
-    }
-    double s[FN_TT][NF];
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) s[i][k] = 0.0;
+    double x1[FN_TT], x2[FN_TT], s[FN_TT][NF];
+    GPK_FN_LOAD_POINTS2(x1, x2, g.tx, t0, g.Nt);
+    fn_zero(s);
     for (int q = threadIdx.x; q < g.M; q += 256) {
         const double y1 = g.px[q], y2 = g.py[q];
         const double cl = q < g.Nd ? g.coeff[q] : 0.0;               // psi block: domain points only (psi is packed as 0 elsewhere)
@@ -273,45 +237,27 @@ __global__ __launch_bounds__(256) void extend_fn_op_kernel(FnOpArgs g) {
             const double d1 = x1[i] - y1, d2 = x2[i] - y2;
             const double e = exp(-0.5 * __builtin_fma(g.p2 * d2, d2, g.p1 * d1 * d1));
             double a[5], b[5], c[6];
-            hermite(g.p1, d1, a);
-            hermite(g.p2, d2, b);
+            hermite_compensated(g.p1, d1, a);
+            hermite_compensated(g.p2, d2, b);
             table_psi<MASK>(a, b, w, c);
 #pragma unroll
             for (int f = 0; f < 6; ++f)
                 if ((MASK >> f) & 1) s[i][fn_row(MASK, f)] = __builtin_fma(((mi_a1(f) + mi_a2(f)) & 1) ? -c[f] : c[f], e, s[i][fn_row(MASK, f)]);
         }
     }
-#pragma unroll
-    for (int i = 0; i < FN_TT; ++i)
-#pragma unroll
-        for (int k = 0; k < NF; ++k) {
-            double v = s[i][k];
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i * NF + k] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < FN_TT * NF) {
-        const int i = threadIdx.x / NF, k = threadIdx.x % NF, t = t0 + i;
-        if (t < g.Nt) g.out[k * g.ldo + t] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    }
+    GPK_FN_REDUCE_STORE(s, NF, t0, g.Nt, g.out, g.ldo);
 }
 
-// one instantiation per mask (63): a functional that is not requested costs nothing
-template <int MASK = 1>
+// one instantiation per mask (63)
 void launch_extend_fn_op(int mask, int grid, hipStream_t st, const FnOpArgs& g) {
-    if constexpr (MASK <= 63) {
-        if (mask == MASK) extend_fn_op_kernel<MASK><<<grid, 256, 0, st>>>(g);
-        else launch_extend_fn_op<MASK + 1>(mask, grid, st, g);
-    }
+    with_mask<63>(mask, [&](auto m) { extend_fn_op_kernel<decltype(m)::value><<<grid, 256, 0, st>>>(g); });
 }
 
 // precisions, packed points and coefficients (the handle's point scratch: 11 arrays of Nd + Nb, re-packed by every call)
 int fill_common_op(gpk_handle h, const char* who, const char* who_kernel, int kernel, const double* kp, const double* Xd, int Nd,
                    const double* Xb, int Nb, const double* op, const double* bc, double (&p)[2], const double* (&arr)[11]) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd || (Nb > 0 && !Xb)) return gpk_bad_arg(h, who);
-    if (kernel == GPK_KERNEL_GAUSSIAN) { p[0] = p[1] = 1.0 / (kp[0] * kp[0]); }
-    else if (kernel == GPK_KERNEL_ANISOTROPIC) { p[0] = 2.0 / (kp[0] * kp[0]); p[1] = 2.0 / (kp[1] * kp[1]); }   // no factor 1/2: the reference's convention
-    else return gpk_bad_arg(h, who_kernel);
+    GPK_TRY(precisions(h, who_kernel, kernel, kp, 2, p));
     const size_t Mall = (size_t)Nd + (size_t)Nb;
     GPK_TRY(gpk_i_ensure_points(h, 11 * Mall));
     double* s = h->d_pts;
@@ -335,8 +281,7 @@ extern "C" int gpk_assemble_op(gpk_handle h, int kernel, const double* kp, const
                                const double* op, const double* bc, double nugget, int nugget_type, double* Theta, int ld,
                                double* host_ratio) {
     if (!h || !Theta) return GPK_ERR_ARG;
-    if (nugget_type != GPK_NUGGET_NONE && nugget_type != GPK_NUGGET_IDENTITY && nugget_type != GPK_NUGGET_ADAPTIVE)
-        return gpk_bad_arg(h, "assemble_op: nugget_type");
+    if (!nugget_type_valid(nugget_type)) return gpk_bad_arg(h, "assemble_op: nugget_type");
     if ((long)2 * Nd + Nb > 0x7fffffffL) return gpk_bad_arg(h, "assemble_op: N exceeds int");
     if (Nd > 0 && Nb >= 0 && ld < 2 * Nd + Nb) return gpk_bad_arg(h, "assemble_op: ld < N");
     OpArgs g;
@@ -352,7 +297,7 @@ extern "C" int gpk_assemble_op(gpk_handle h, int kernel, const double* kp, const
     // Both traces are point sums taken on the host from the coefficient arrays, in index order and in long double, so that the
     // returned ratio is the analytic value to an ulp and the same on every call.
     const long double q1 = p[0], q2 = p[1];
-    long double tr0, tr1 = (long double)Nd;
+    long double tr0;
     if (op) {
         std::vector<double> ho(6 * (size_t)Nd);
         GPK_HIP(h, hipMemcpyAsync(ho.data(), op, ho.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -367,45 +312,13 @@ extern "C" int gpk_assemble_op(gpk_handle h, int kernel, const double* kp, const
     } else {
         tr0 = (long double)Nd * (3.0L * (q1 * q1 + q2 * q2) + 2.0L * q1 * q2);
     }
-    if (bc && Nb > 0) {
-        std::vector<double> hb(3 * (size_t)Nb);
-        GPK_HIP(h, hipMemcpyAsync(hb.data(), bc, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        GPK_HIP(h, hipStreamSynchronize(h->stream));
-        long double sb = 0.0L;
-        for (int b = 0; b < Nb; ++b) {
-            const long double b0 = hb[3 * (size_t)b], b1 = hb[3 * (size_t)b + 1], b2 = hb[3 * (size_t)b + 2];
-            sb += b0 * b0 + q1 * b1 * b1 + q2 * b2 * b2;
-        }
-        tr1 += sb;
-    } else {
-        tr1 += (long double)Nb;
-    }
-    const double r0 = (double)(tr0 / tr1);                       // trace(block 0) / trace(block 1)
+    long double trb;
+    GPK_TRY(boundary_trace(h, bc, Nb, q1, q2, &trb));
+    const double r0 = (double)(tr0 / ((long double)Nd + trb));   // trace(block 0) / trace(block 1)
     if (host_ratio) *host_ratio = r0;
-    g.nug[0] = nugget_type == GPK_NUGGET_ADAPTIVE ? nugget * r0 : (nugget_type == GPK_NUGGET_IDENTITY ? nugget : 0.0);
-    g.nug[1] = nugget_type == GPK_NUGGET_NONE ? 0.0 : nugget;
+    two_block_nugget(nugget_type, nugget, r0, g.nug);
     g.out = Theta; g.ld = ld;
-    // two column points per lane (16-byte stores) when every pair (q, q + 1) stays inside one block and is 16-byte aligned
-    const bool pairs = h->tune.asm_pairs && (ld % 2 == 0) && (((uintptr_t)Theta & 15) == 0) && (Nd % 2 == 0) && (Nb % 2 == 0);
-    // (per-phase timing on: HIP events around the evaluator launch alone, as in gpk_assemble -- gpk_prof_read_assembly reads them)
-    if (h->prof) {
-        if (!h->asm_ev[0]) for (int i = 0; i < 2; ++i) GPK_HIP(h, hipEventCreate(&h->asm_ev[i]));
-        GPK_HIP(h, hipEventRecord(h->asm_ev[0], h->stream));
-    }
-    struct AsmStop {
-        gpk_handle h; ~AsmStop() { if (h->prof && h->asm_ev[1]) h->asm_timed = hipEventRecord(h->asm_ev[1], h->stream) == hipSuccess; }
-    } asm_stop{h};
-    if (pairs) {
-        dim3 grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
-        // key 55: 0 plain, 1 non-temporal (the write-through variants 2 / 3 of gpk_assemble are not offered here: plain)
-        if (h->tune.asm_nt == 1) assemble_op2_kernel<1><<<grid2, 256, 0, h->stream>>>(g);
-        else assemble_op2_kernel<0><<<grid2, 256, 0, h->stream>>>(g);
-    } else {
-        dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP));
-        assemble_op_kernel<<<grid, 256, 0, h->stream>>>(g);
-    }
-    GPK_LAUNCH_CHECK(h);
-    return 0;
+    return launch_two_block(h, pairs_eligible(h, Theta, ld, Nd, Nb), g, assemble_op_kernel, assemble_op2_kernel<0>, assemble_op2_kernel<1>);
 }
 
 extern "C" int gpk_extend_functionals_op(gpk_handle h, int kernel, const double* kp, const double* Xt, int Nt,
@@ -425,7 +338,7 @@ extern "C" int gpk_extend_functionals_op(gpk_handle h, int kernel, const double*
     g.p1 = p[0]; g.p2 = p[1];
     g.Nd = Nd; g.M = Nd + Nb;
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
-    launch_extend_fn_op<>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g);
+    launch_extend_fn_op(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

@@ -360,19 +360,27 @@ class Context:
     def extend_functionals(self, layout, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'laplacian')):
         """Derivatives of the extension at Xt (gpk_extend_functionals): a (len(which), Nt) DeviceArray, row k = functional which[k]
         (names: FUNCTIONAL; for Burgers d1 = d/dt, d2 = d/dx, d2d2 = d^2/dx^2).  coeff = Theta^{-1} sol_vec, as for extend()."""
+        return self._extend_functionals('extend_functionals', FUNCTIONAL, 2, self.lib.gpk_extend_functionals, (LAYOUT[layout],),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
+
+    def _extend_functionals(self, name, table, dim, entry, lead, kernel, kernel_parameter, Xt, Xd, Xb, coeffs, coeff, which):
+        """The four extend_functionals* calls: functional names `which` through `table` to the mask, points (n, dim) and the expansion
+        coefficients to the device, the library `entry` (its arguments: handle, `lead`, kernel, points, the device arrays or None of
+        coeffs(Nd, Nb), expansion coefficients, mask, output), then the rows from ascending bit order into the caller's order."""
         which = tuple(which)
-        bits = [FUNCTIONAL[w] for w in which]
+        bits = [table[w] for w in which]
         if len(set(bits)) != len(bits):
-            raise ValueError(f'extend_functionals: repeated functional in {which!r}')
-        Xt = np.ascontiguousarray(Xt, dtype=np.float64); Xd = np.ascontiguousarray(Xd, dtype=np.float64)
-        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+            raise ValueError(f'{name}: repeated functional in {which!r}')
+        Xt, Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, dim) for X in (Xt, Xd, Xb))
         Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
-        dXt, dXd, dXb = self.points(Xt), self.points(Xd), self.points(Xb)
+        dXt, dXd, dXb = self.points(Xt, dim), self.points(Xd, dim), self.points(Xb, dim)
+        held = coeffs(Nd, Nb) if coeffs else ()                               # (kept alive until the call has been issued)
+        extra = [a.ptr if a is not None else None for a in held]
         dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
         mask = sum(bits)
-        full = DeviceArray(self, bin(mask).count('1'), Nt, ld=Nt)           # rows in ascending bit order
-        self._chk(self.lib.gpk_extend_functionals(self.h, LAYOUT[layout], KERNEL[kernel], kernel_params(kernel, kernel_parameter),
-                                                  dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, mask, full.ptr, full.ld))
+        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
+        kp = (kernel_params3d if dim == 3 else kernel_params)(kernel, kernel_parameter)
+        self._chk(entry(self.h, *lead, KERNEL[kernel], kp, dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, *extra, dc.ptr, mask, full.ptr, full.ld))
         order = sorted(bits)
         if bits == order:
             out = full
@@ -382,47 +390,35 @@ class Context:
                 self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
         self.synchronize()
         return out
+
+    def _assemble_two_block(self, entry, dim, kernel, kernel_parameter, Xd, Xb, coeffs, nugget, nugget_type, out):
+        """The two-block Gram calls (assemble3d / assemble_bc / assemble_op): points (n, dim) to the device, the library `entry` (its
+        arguments: handle, kernel, points, the device arrays or None of coeffs(Nd, Nb), nugget, Theta, ratio) -> (Theta, trace ratio)."""
+        Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, dim) for X in (Xd, Xb))
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 2 * Nd + Nb
+        dXd, dXb = self.points(Xd, dim), self.points(Xb, dim)
+        held = coeffs(Nd, Nb) if coeffs else ()                               # (kept alive until the call has been issued)
+        extra = [a.ptr if a is not None else None for a in held]
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratio = C.c_double()
+        kp = (kernel_params3d if dim == 3 else kernel_params)(kernel, kernel_parameter)
+        self._chk(entry(self.h, KERNEL[kernel], kp, dXd.ptr, Nd, dXb.ptr, Nb, *extra, float(nugget), NUGGET[nugget_type], T.ptr, T.ld,
+                        C.byref(ratio)))
+        self.synchronize()
+        return T, ratio.value
 
     # ---- three space dimensions (gpk_assemble3d, gpk_extend_functionals3d) ----
     def assemble3d(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
         """Gram matrix of the 3-D elliptic layout (Laplacian on Xd, delta on [Xd; Xb]; points (n,3)): (DeviceArray N x N with
         N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any leading dimension >= N)."""
-        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 3); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 3)
-        Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 2 * Nd + Nb
-        dXd, dXb = self.points(Xd, 3), self.points(Xb, 3)
-        T = out if out is not None else DeviceArray(self, N, N)
-        ratio = C.c_double()
-        self._chk(self.lib.gpk_assemble3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
-                                          float(nugget), NUGGET[nugget_type], T.ptr, T.ld, C.byref(ratio)))
-        self.synchronize()
-        return T, ratio.value
+        return self._assemble_two_block(self.lib.gpk_assemble3d, 3, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out)
 
     def extend_functionals3d(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd3', 'laplacian')):
         """Value / derivatives of the 3-D extension at Xt (gpk_extend_functionals3d): a (len(which), Nt) DeviceArray, row k = functional
         which[k] (names: FUNCTIONAL3D).  coeff = Theta^{-1} sol_vec (2 Nd + Nb values).  which = ('value',) is the plain extension."""
-        which = tuple(which)
-        bits = [FUNCTIONAL3D[w] for w in which]
-        if len(set(bits)) != len(bits):
-            raise ValueError(f'extend_functionals3d: repeated functional in {which!r}')
-        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 3); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 3)
-        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 3)
-        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
-        dXt, dXd, dXb = self.points(Xt, 3), self.points(Xd, 3), self.points(Xb, 3)
-        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
-        mask = sum(bits)
-        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
-        self._chk(self.lib.gpk_extend_functionals3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter),
-                                                    dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dc.ptr, mask, full.ptr, full.ld))
-        order = sorted(bits)
-        if bits == order:
-            out = full
-        else:                                                             # the caller's order
-            out = DeviceArray(self, len(bits), Nt, ld=Nt)
-            for k, b in enumerate(bits):
-                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
-        self.synchronize()
-        return out
+        return self._extend_functionals('extend_functionals3d', FUNCTIONAL3D, 3, self.lib.gpk_extend_functionals3d, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
 
     # ---- boundary functionals: Neumann / Robin / mixed conditions for the 2-D elliptic layout (gpk_assemble_bc, gpk_extend_functionals_bc) ----
     def _boundary_coeffs(self, bc, Nb):
@@ -438,44 +434,14 @@ class Context:
         """Gram matrix of the 2-D elliptic layout with the functional bc[b] = (c0, c1, c2) -> c0 delta + c1 d/dx1 + c2 d/dx2 at boundary
         point b (bc = None: delta everywhere): (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to
         write into (any leading dimension >= N)."""
-        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
-        Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 2 * Nd + Nb
-        dXd, dXb, dbc = self.points(Xd), self.points(Xb), self._boundary_coeffs(bc, Nb)
-        T = out if out is not None else DeviceArray(self, N, N)
-        ratio = C.c_double()
-        self._chk(self.lib.gpk_assemble_bc(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
-                                           dbc.ptr if dbc is not None else None, float(nugget), NUGGET[nugget_type], T.ptr, T.ld,
-                                           C.byref(ratio)))
-        self.synchronize()
-        return T, ratio.value
+        return self._assemble_two_block(self.lib.gpk_assemble_bc, 2, kernel, kernel_parameter, Xd, Xb,
+                                        lambda Nd, Nb: (self._boundary_coeffs(bc, Nb),), nugget, nugget_type, out)
 
     def extend_functionals_bc(self, kernel, kernel_parameter, Xt, Xd, Xb, bc, coeff, which=('value', 'd1', 'd2', 'laplacian')):
         """Value / derivatives of the extension under the boundary functionals bc at Xt (gpk_extend_functionals_bc): a (len(which), Nt)
         DeviceArray, row k = functional which[k] (names: FUNCTIONAL).  coeff = Theta^{-1} sol_vec with the Theta of assemble_bc."""
-        which = tuple(which)
-        bits = [FUNCTIONAL[w] for w in which]
-        if len(set(bits)) != len(bits):
-            raise ValueError(f'extend_functionals_bc: repeated functional in {which!r}')
-        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 2); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2)
-        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
-        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
-        dXt, dXd, dXb, dbc = self.points(Xt), self.points(Xd), self.points(Xb), self._boundary_coeffs(bc, Nb)
-        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
-        mask = sum(bits)
-        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
-        self._chk(self.lib.gpk_extend_functionals_bc(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
-                                                     dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dbc.ptr if dbc is not None else None,
-                                                     dc.ptr, mask, full.ptr, full.ld))
-        order = sorted(bits)
-        if bits == order:
-            out = full
-        else:                                                             # the caller's order
-            out = DeviceArray(self, len(bits), Nt, ld=Nt)
-            for k, b in enumerate(bits):
-                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
-        self.synchronize()
-        return out
+        return self._extend_functionals('extend_functionals_bc', FUNCTIONAL, 2, self.lib.gpk_extend_functionals_bc, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, lambda Nd, Nb: (self._boundary_coeffs(bc, Nb),), coeff, which)
 
     # ---- variable-coefficient operator on the domain points of the 2-D elliptic layout (gpk_assemble_op, gpk_extend_functionals_op) ----
     def _domain_coeffs(self, op, Nd):
@@ -492,46 +458,16 @@ class Context:
         b2 d/dx2 + a11 d2/dx1^2 + a12 d2/dx1dx2 + a22 d2/dx2^2 at domain point i (op = None: the Laplacian) and bc[b] at boundary point b
         as in assemble_bc: (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any
         leading dimension >= N)."""
-        Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2); Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
-        Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 2 * Nd + Nb
-        dXd, dXb, dop, dbc = self.points(Xd), self.points(Xb), self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)
-        T = out if out is not None else DeviceArray(self, N, N)
-        ratio = C.c_double()
-        self._chk(self.lib.gpk_assemble_op(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
-                                           dop.ptr if dop is not None else None, dbc.ptr if dbc is not None else None, float(nugget),
-                                           NUGGET[nugget_type], T.ptr, T.ld, C.byref(ratio)))
-        self.synchronize()
-        return T, ratio.value
+        return self._assemble_two_block(self.lib.gpk_assemble_op, 2, kernel, kernel_parameter, Xd, Xb,
+                                        lambda Nd, Nb: (self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)), nugget, nugget_type, out)
 
     def extend_functionals_op(self, kernel, kernel_parameter, Xt, Xd, Xb, op, bc, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
         """Value / derivatives up to order two of the extension under the domain functionals op and the boundary functionals bc at Xt
         (gpk_extend_functionals_op): a (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP).
         coeff = Theta^{-1} sol_vec with the Theta of assemble_op."""
-        which = tuple(which)
-        bits = [FUNCTIONAL_OP[w] for w in which]
-        if len(set(bits)) != len(bits):
-            raise ValueError(f'extend_functionals_op: repeated functional in {which!r}')
-        Xt = np.ascontiguousarray(Xt, dtype=np.float64).reshape(-1, 2); Xd = np.ascontiguousarray(Xd, dtype=np.float64).reshape(-1, 2)
-        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
-        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
-        dXt, dXd, dXb = self.points(Xt), self.points(Xd), self.points(Xb)
-        dop, dbc = self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)
-        dc = coeff if isinstance(coeff, DeviceArray) else self.array(coeff)
-        mask = sum(bits)
-        full = DeviceArray(self, len(bits), Nt, ld=Nt)                      # rows in ascending bit order
-        self._chk(self.lib.gpk_extend_functionals_op(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
-                                                     dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, dop.ptr if dop is not None else None,
-                                                     dbc.ptr if dbc is not None else None, dc.ptr, mask, full.ptr, full.ld))
-        order = sorted(bits)
-        if bits == order:
-            out = full
-        else:                                                             # the caller's order
-            out = DeviceArray(self, len(bits), Nt, ld=Nt)
-            for k, b in enumerate(bits):
-                self._chk(self.lib.gpk_memcpy_d2d(self.h, out.at(k), full.at(order.index(b)), Nt * 8))
-        self.synchronize()
-        return out
+        return self._extend_functionals('extend_functionals_op', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_op, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb,
+                                        lambda Nd, Nb: (self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)), coeff, which)
 
     def pde_residual(self, system, params, fields_u, fields_a, rhs):
         """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array
