@@ -75,7 +75,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -189,6 +189,45 @@ int gpk_assemble_op(gpk_handle h, int kernel, const double* host_kparams, const 
 int gpk_extend_functionals_op(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                               const double* Xd, int Nd, const double* Xb, int Nb, const double* op, const double* bc,
                               const double* coeff, int fmask, double* out, int ldo);
+/* ---- Operator and boundary functionals in three dimensions ("Operator and boundary functionals in three dimensions"):
+ *      -psi[u] + alpha u^m = f on a box in R^3 with psi_i = c0 delta + sum_k b_k d_k + sum_{k<=l} a_kl d_k d_l at domain point i -- 3-D
+ *      advection-diffusion-reaction, and with axis 3 as time psi = nu (d_1 d_1 + d_2 d_2) - d_3: u_t - nu Laplace_x u + alpha u^m = f in two
+ *      space dimensions by space-time collocation.  No reference call site.
+ *      op3 (Nd,10) row-major on the device: row i = (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) of psi_i; a mixed coefficient
+ *      multiplies its mixed derivative ONCE (a symmetric tensor A enters as a12 = 2 A12).  op3 == NULL: the Laplacian
+ *      (0,0,0,0,1,0,0,1,0,1) at every domain point.  bc3 (Nb,4) row-major on the device: row b = (c0, c1, c2, c3) of
+ *      phi_b = c0 delta + c1 d_1 + c2 d_2 + c3 d_3 (Dirichlet (1,0,0,0), Neumann (0,n), Robin (beta,n)); bc3 == NULL: (1,0,0,0).
+ *      Points (n,3) row-major, host_kparams and precisions as gpk_assemble3d.  Layout as ELLIPTIC3D: block 0 = psi on the Nd domain
+ *      points, block 1 = delta on the domain points and phi_b on the boundary points, N = 2Nd+Nb, Theta N x N with leading dimension
+ *      ld >= N -- so gpk_potrf, the GPK_GN_ELLIPTIC system, gpk_potrs and gpk_pde_residual apply unchanged (psi[u] takes the place of
+ *      the Laplacian).  Nugget as gpk_assemble's.  host_ratio (one double, may be NULL): trace(block 0) / trace(block 1) with
+ *        <psi,psi> = c0^2 + sum_k p_k b_k^2 + 3 sum_k p_k^2 a_kk^2 + sum_{k<l} p_k p_l (a_kl^2 + 2 a_kk a_ll) - 2 c0 sum_k p_k a_kk,
+ *        <phi,phi> = c0^2 + sum_k p_k c_k^2 (1 at a domain point)
+ *      at d = 0, written for every nugget type; both point sums are taken on the host in index order (op3 / bc3 != NULL: one small
+ *      device-to-host copy each, synchronises).  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb
+ *      allow; 8-byte stores otherwise, with the same values; nothing outside the N x N view is written); the launch is timed like
+ *      gpk_assemble's when the per-phase timing is on (gpk_prof_read_assembly).  Bad arguments: -9001, named in gpk_last_error. */
+int gpk_assemble_op3d(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                      const double* op3, const double* bc3, double nugget, int nugget_type, double* Theta, int ld, double* host_ratio);
+/* The ten monomial derivatives of the extension under op3 / bc3 at test points Xt (Nt,3), matrix-free: coeff (2Nd+Nb) = Theta^{-1} sol_vec
+ * with the Theta of gpk_assemble_op3d for the same op3 and bc3.  fmask: a non-empty subset of the GPK_OP3FN_* bits below, bit j =
+ * monomial j of op3 (anything else: -9001); out is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo,
+ * ldo >= Nt; entries past Nt untouched.  Three kernel instantiations serve every mask (value; value and gradient; all ten), the
+ * smallest that contains the request.  Fixed reduction order: a repeated call gives bit-identical output, and a row has the same bits
+ * whichever other rows are requested.  psi_t[u] at a test point is a combination of the rows, formed by the caller. */
+#define GPK_OP3FN_VALUE 1     /* u */
+#define GPK_OP3FN_D1    2     /* du/dx1 */
+#define GPK_OP3FN_D2    4     /* du/dx2 */
+#define GPK_OP3FN_D3    8     /* du/dx3 */
+#define GPK_OP3FN_D11  16     /* d^2u/dx1^2 */
+#define GPK_OP3FN_D12  32     /* d^2u/dx1dx2 */
+#define GPK_OP3FN_D13  64     /* d^2u/dx1dx3 */
+#define GPK_OP3FN_D22 128     /* d^2u/dx2^2 */
+#define GPK_OP3FN_D23 256     /* d^2u/dx2dx3 */
+#define GPK_OP3FN_D33 512     /* d^2u/dx3^2 */
+int gpk_extend_functionals_op3d(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                                const double* Xd, int Nd, const double* Xb, int Nb, const double* op3, const double* bc3,
+                                const double* coeff, int fmask, double* out, int ldo);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the
  * device (the extension already is); one pass, fixed summation order.  Synchronises. */

@@ -1,5 +1,6 @@
-// gpk_assemble_common.h -- what the four Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts,
-// gpk_assemble3d.hip, gpk_assemble_bc.hip: Neumann / Robin, gpk_assemble_op.hip: variable-coefficient operator).  The kernels and the
+// gpk_assemble_common.h -- what the five Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts,
+// gpk_assemble3d.hip, gpk_assemble_bc.hip: Neumann / Robin, gpk_assemble_op.hip: variable-coefficient operator, gpk_assemble_op3d.hip:
+// the operator and the boundary functionals in three dimensions).  The kernels and the
 // per-pair arithmetic that differs between them (pair_coeff in its two roundings, pair_coeff3, the tables of the operator) stay in
 // those files; here is the scaffolding around them, each piece once: functional tables, the two Hermite evaluations, the frame of
 // the extension kernels, the 16-byte store, and the host side of an evaluator call (precisions, nugget, trace, timing, launch).
@@ -177,6 +178,23 @@ inline int boundary_trace(gpk_handle h, const double* bc, int Nb, long double p1
     for (int b = 0; b < Nb; ++b) {
         const long double b0 = hb[3 * (size_t)b], b1 = hb[3 * (size_t)b + 1], b2 = hb[3 * (size_t)b + 2];
         sb += b0 * b0 + p1 * b1 * b1 + p2 * b2 * b2;
+    }
+    *tr = sb;
+    return 0;
+}
+
+// the same in three dimensions: bc (device, (Nb,4)) rows (c0, c1, c2, c3), *tr = sum_b (c0_b^2 + sum_k p_k ck_b^2); Nb when bc == NULL
+inline int boundary_trace3(gpk_handle h, const double* bc, int Nb, const long double (&p)[3], long double* tr) {
+    *tr = (long double)Nb;
+    if (!bc || Nb <= 0) return 0;
+    std::vector<double> hb(4 * (size_t)Nb);
+    GPK_HIP(h, hipMemcpyAsync(hb.data(), bc, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipStreamSynchronize(h->stream));
+    long double sb = 0.0L;
+    for (int b = 0; b < Nb; ++b) {
+        const double* c = hb.data() + 4 * (size_t)b;
+        const long double b0 = c[0], b1 = c[1], b2 = c[2], b3 = c[3];
+        sb += b0 * b0 + p[0] * b1 * b1 + p[1] * b2 * b2 + p[2] * b3 * b3;
     }
     *tr = sb;
     return 0;

@@ -87,6 +87,8 @@ PROTOTYPES = {
     'gpk_extend_functionals_bc': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     'gpk_assemble_op': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _vp, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_op': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
+    'gpk_assemble_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _vp, _d, _i, _vp, _i, _pd]),
+    'gpk_extend_functionals_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     'gpk_pde_residual': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'gpk_potrf': (_i, [_vp, _vp, _i, _i, _pi]),
     'gpk_tril': (_i, [_vp, _vp, _i, _i]),

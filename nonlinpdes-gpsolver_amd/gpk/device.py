@@ -15,6 +15,8 @@ NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
 FUNCTIONAL_OP = {'value': 1, 'd1': 2, 'd2': 4, 'd11': 8, 'd12': 16, 'd22': 32}   # GPK_OPFN_* bits of gpk_extend_functionals_op
+OP3_NAMES = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')   # the monomials of op3, in its order
+FUNCTIONAL_OP3 = {n: 1 << k for k, n in enumerate(OP3_NAMES)}                    # GPK_OP3FN_* bits of gpk_extend_functionals_op3d
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
 
 
@@ -468,6 +470,35 @@ class Context:
         return self._extend_functionals('extend_functionals_op', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_op, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb,
                                         lambda Nd, Nb: (self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)), coeff, which)
+
+    # ---- operator and boundary functionals in three dimensions (gpk_assemble_op3d, gpk_extend_functionals_op3d) ----
+    def _coeff_rows(self, c, n, width, what):
+        """(n, width) coefficient rows on the device, or None (= NULL: the library's default functional)"""
+        if c is None:
+            return None
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        if c.shape != (n, width):
+            raise ValueError(f'{what} must have shape ({n}, {width}), got {c.shape}')
+        return DeviceArray(self, n, width, ld=width).upload(c) if n else DeviceArray(self, 1, width, ld=width)
+
+    def _coeffs3(self, op3, bc3):
+        return lambda Nd, Nb: (self._coeff_rows(op3, Nd, 10, 'domain coefficients (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33)'),
+                               self._coeff_rows(bc3, Nb, 4, 'boundary coefficients (c0, c1, c2, c3)'))
+
+    def assemble_op3d(self, kernel, kernel_parameter, Xd, Xb, op3, bc3, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 3-D elliptic layout with the functional op3[i] = (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) at domain
+        point i (op3 = None: the Laplacian) and bc3[b] = (c0, c1, c2, c3) -> c0 delta + c . grad at boundary point b (None: delta):
+        (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  A mixed coefficient multiplies its mixed derivative once.
+        out: a DeviceArray to write into (any leading dimension >= N)."""
+        return self._assemble_two_block(self.lib.gpk_assemble_op3d, 3, kernel, kernel_parameter, Xd, Xb, self._coeffs3(op3, bc3),
+                                        nugget, nugget_type, out)
+
+    def extend_functionals_op3d(self, kernel, kernel_parameter, Xt, Xd, Xb, op3, bc3, coeff, which=OP3_NAMES):
+        """Value / derivatives up to order two of the 3-D extension under op3 and bc3 at Xt (gpk_extend_functionals_op3d): a
+        (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP3).  coeff = Theta^{-1} sol_vec with the Theta
+        of assemble_op3d."""
+        return self._extend_functionals('extend_functionals_op3d', FUNCTIONAL_OP3, 3, self.lib.gpk_extend_functionals_op3d, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, self._coeffs3(op3, bc3), coeff, which)
 
     def pde_residual(self, system, params, fields_u, fields_a, rhs):
         """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array

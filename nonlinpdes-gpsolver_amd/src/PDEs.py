@@ -14,7 +14,7 @@ from numpy import random
 import gpk
 
 from ._runtime import eval_callback, get_context
-from .sample_points import boundary_normals, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
+from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
 
@@ -25,6 +25,25 @@ def divergence_form(a, a_x1, a_x2, v1, v2, c):
     (arrays over the points, or scalars).  What Nonlinear_elliptic2d(operator=...) returns for an advection-diffusion-reaction operator."""
     a, a_x1, a_x2, v1, v2, c = onp.broadcast_arrays(*(onp.asarray(t, dtype=onp.float64) for t in (a, a_x1, a_x2, v1, v2, c)))
     return -c, a_x1 - v1, a_x2 - v2, a, onp.zeros_like(a), a
+
+
+def divergence_form3d(a, a_x1, a_x2, a_x3, v1, v2, v3, c):
+    """The ten coefficients (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) of psi = a Laplace + (grad a - v) . grad - c in three
+    dimensions, for which -psi[u] = -div(a grad u) + v . grad u + c u (arrays over the points, or scalars).  What
+    Nonlinear_elliptic3d(operator=...) returns for an advection-diffusion-reaction operator."""
+    a, a_x1, a_x2, a_x3, v1, v2, v3, c = onp.broadcast_arrays(*(onp.asarray(t, dtype=onp.float64) for t in (a, a_x1, a_x2, a_x3, v1, v2, v3, c)))
+    z = onp.zeros_like(a)
+    return -c, a_x1 - v1, a_x2 - v2, a_x3 - v3, a, z, z, a, z, a
+
+
+def parabolic_form(nu, v1=0.0, v2=0.0, c=0.0):
+    """A callable operator(x1, x2, t) for Nonlinear_elliptic3d with axis 3 as time: the ten coefficients of
+    psi = nu Laplace_x - v . grad_x - c - d_t, for which -psi[u] = u_t - nu Laplace_x u + v . grad_x u + c u (constant nu, v1, v2, c)."""
+    def operator(x1, x2, t):
+        one = onp.ones(onp.shape(onp.asarray(x1, dtype=onp.float64)))
+        z = 0.0 * one
+        return -c * one, -v1 * one, -v2 * one, -one, nu * one, z, z, nu * one, z, z
+    return operator
 
 
 class _GPEquation(object):
@@ -502,17 +521,38 @@ class Nonlinear_elliptic3d(_GPEquation):
     2-D elliptic block structure -- Laplacian on the domain points, delta on domain + boundary points, N = 2 N_domain + N_boundary --
     so the factorisation and the Gauss-Newton system ('Nonlinear_elliptic') are the 2-D ones; only the point-pair evaluator
     (gpk_assemble3d, gpk_extend_functionals3d) knows about the third coordinate.  GPK_STRUCTURED is ignored here: every step runs the
-    reference's operation sequence."""
+    reference's operation sequence.
+    With operator=... / set_domain_operator() the equation is -psi[u] + alpha*u^m = f for any second-order linear operator psi with
+    variable coefficients, and with bc='neumann' / 'robin' / set_boundary_operator() the boundary rows are first-order functionals
+    (gpk_assemble_op3d, gpk_extend_functionals_op3d).  With axis 3 as time this covers u_t - nu Laplace_x u + alpha u^m = f in two space
+    dimensions (parabolic_form(), sampled_pts(time_dependent=True))."""
     _layout = 'Nonlinear_elliptic3d'
     _system = 'Nonlinear_elliptic'
     _deriv_names = ('value', 'd1', 'd2', 'd3', 'laplacian')
+    _BC = ('dirichlet', 'neumann', 'robin')
+    _op_names = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')    # rows of gpk_extend_functionals_op3d
 
-    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]])):
+    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
+                 operator=None):
+        """bc: the operator B on the boundary, whose prescribed value g = B u is what `bdy(x1, x2, x3)` returns -- 'dirichlet' B u = u;
+        'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the outward unit normal (sample_points.boundary_normals3d).
+        operator: a callable operator(x1, x2, x3) returning the ten coefficient arrays (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) of
+        psi; the equation solved is then -psi[u] + alpha u^m = f (divergence_form3d(), parabolic_form(); a mixed coefficient multiplies
+        its mixed derivative once).  With 'dirichlet' and None every call goes the way it always went."""
+        if bc not in self._BC:
+            raise ValueError(f'bc {bc!r}: one of {self._BC}')
+        if operator is not None and not callable(operator):
+            raise ValueError(f'operator {operator!r}: a callable operator(x1, x2, x3) returning ten coefficient arrays, or None')
         self.alpha = alpha
         self.m = m
         self.bdy = bdy
         self.rhs = rhs
         self.domain = domain
+        self.bc = bc
+        self.robin_beta = robin_beta
+        self.operator = operator
+        self.boundary_coeffs = None
+        self.domain_coeffs = None
 
     def get_bd(self, x1, x2, x3):
         return self.bdy(x1, x2, x3)
@@ -535,15 +575,56 @@ class Nonlinear_elliptic3d(_GPEquation):
         self.rhs_f = eval_callback(self.get_rhs, *self.X_domain.T)
         self.bdy_g = eval_callback(self.get_bd, *self.X_boundary.T)
         self._drop_device_state()
+        self.boundary_coeffs = None                        # custom operators belong to the points they were set for
+        if self.bc != 'dirichlet':
+            n = boundary_normals3d(self.X_boundary, self.domain)
+            beta = float(self.robin_beta) if self.bc == 'robin' else 0.0
+            self.boundary_coeffs = onp.concatenate([onp.full((self.N_boundary, 1), beta), n], axis=1)
+        self.domain_coeffs = None
+        if self.operator is not None:
+            self.domain_coeffs = self._operator_at(self.X_domain)
 
-    def sampled_pts(self, N_domain, N_boundary, sampled_type='random'):
+    def sampled_pts(self, N_domain, N_boundary, sampled_type='random', time_dependent=False):
+        """time_dependent: axis 3 is time -- no boundary points on the face x3 = max (sample_points.sampled_pts_rdm3d)"""
+        kw = {'time_dependent': True} if time_dependent else {}
         if sampled_type == 'random':
-            X_domain, X_boundary = sampled_pts_rdm3d(N_domain, N_boundary, self.domain)
+            X_domain, X_boundary = sampled_pts_rdm3d(N_domain, N_boundary, self.domain, **kw)
         elif sampled_type == 'grid':
-            X_domain, X_boundary = sampled_pts_grid3d(N_domain, N_boundary, self.domain)
+            X_domain, X_boundary = sampled_pts_grid3d(N_domain, N_boundary, self.domain, **kw)
         else:
             raise ValueError(f'sampled_type {sampled_type!r}: random or grid')
         self._set_points(X_domain, X_boundary)
+
+    # ---- domain operator (N_domain, 10) and boundary operator (N_boundary, 4), or None = the Laplacian / Dirichlet: today's path ----
+    def _operator_at(self, X):
+        """the callable `operator` at the points X (n,3) as an (n,10) array"""
+        rows = self.operator(X[:, 0], X[:, 1], X[:, 2])
+        if len(rows) != 10:
+            raise ValueError(f'operator must return ten coefficient arrays (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33), got {len(rows)}')
+        return onp.stack([onp.broadcast_to(onp.asarray(r, dtype=onp.float64), (X.shape[0],)) for r in rows], axis=1)
+
+    def set_domain_operator(self, coeffs):
+        """Row i of coeffs (N_domain, 10) = (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33): the equation at domain point i reads
+        -psi_i[u] + alpha u^m = rhs_f[i].  Call after the points are set; dropped when they change.  Discards the Gram matrix and
+        everything derived from it."""
+        coeffs = onp.array(coeffs, dtype=onp.float64)
+        if coeffs.shape != (self.N_domain, 10):
+            raise ValueError(f'coeffs must have shape ({self.N_domain}, 10), got {coeffs.shape}')
+        self.domain_coeffs = coeffs
+        self._drop_device_state()
+
+    def set_boundary_operator(self, coeffs):
+        """Row b of coeffs (N_boundary, 4) = (c0, c1, c2, c3): the condition at boundary point b reads c0 u + c . grad u = bdy_g[b].
+        Call after the points are set; dropped when they change.  Discards the Gram matrix and everything derived from it."""
+        coeffs = onp.array(coeffs, dtype=onp.float64)
+        if coeffs.shape != (self.N_boundary, 4):
+            raise ValueError(f'coeffs must have shape ({self.N_boundary}, 4), got {coeffs.shape}')
+        self.boundary_coeffs = coeffs
+        self._drop_device_state()
+
+    def _general(self):
+        """an operator or a non-Dirichlet condition is set: the calls go to gpk_assemble_op3d / gpk_extend_functionals_op3d"""
+        return self.domain_coeffs is not None or self.boundary_coeffs is not None
 
     def _gn_params(self):
         return float(self.alpha), float(self.m), 0.0
@@ -567,7 +648,11 @@ class Nonlinear_elliptic3d(_GPEquation):
         self.nugget = nugget
         self.kernel = kernel
         self.kernel_parameter = kernel_parameter
-        self._dTheta, self.ratio = ctx.assemble3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+        if self._general():
+            self._dTheta, self.ratio = ctx.assemble_op3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs,
+                                                         self.boundary_coeffs, nugget, nugget_type)
+        else:
+            self._dTheta, self.ratio = ctx.assemble3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
 
     def GN_loss(self, z, z_old):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
@@ -588,24 +673,80 @@ class Nonlinear_elliptic3d(_GPEquation):
         return get_context().extend_functionals3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
                                                   self._coeff(self._dL, self.sol_vec), which=which)
 
+    def _fields_op(self, X_test, which):
+        return get_context().extend_functionals_op3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                     self.domain_coeffs, self.boundary_coeffs, self._coeff(self._dL, self.sol_vec),
+                                                     which=which)
+
     def extend_sol(self, X_test):
         X_test = self._pts(X_test)
         self.X_test = X_test
         self.N_test = X_test.shape[0]
-        self.extended_sol = self._fields(X_test, ('value',)).download().reshape(-1)
+        fields = self._fields_op if self._general() else self._fields
+        self.extended_sol = fields(X_test, ('value',)).download().reshape(-1)
 
     def extend_derivatives(self, X_test):
-        """value, d1, d2, d3 and laplacian of the GP solution at X_test (numpy arrays)"""
-        self.extended_derivatives = self._rows(self._fields(self._pts(X_test), self._deriv_names), self._deriv_names)
+        """value, d1, d2, d3 and laplacian of the GP solution at X_test (numpy arrays); with a domain operator additionally the six
+        second derivatives d11 .. d33 (laplacian = d11 + d22 + d33)"""
+        X_test = self._pts(X_test)
+        if self.domain_coeffs is not None:
+            r = self._rows(self._fields_op(X_test, self._op_names), self._op_names)
+            self.extended_derivatives = dict({'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'd3': r['d3'],
+                                              'laplacian': r['d11'] + r['d22'] + r['d33']}, **{n: r[n] for n in self._op_names[4:]})
+        elif self._general():
+            names = ('value', 'd1', 'd2', 'd3', 'd11', 'd22', 'd33')
+            r = self._rows(self._fields_op(X_test, names), names)
+            self.extended_derivatives = {'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'd3': r['d3'],
+                                         'laplacian': r['d11'] + r['d22'] + r['d33']}
+        else:
+            self.extended_derivatives = self._rows(self._fields(X_test, self._deriv_names), self._deriv_names)
         return self.extended_derivatives
 
-    def PDE_residual(self, X_test):
-        """pointwise residual -Delta u + alpha u^m - f at X_test from the derivatives of the GP solution (rhs evaluated at X_test)"""
+    def _psi_fields(self, X_test, coeffs_t):
+        """rows value, d1, d2 and psi_t[u] (in the Laplacian's place) for gpk_pde_residual, psi_t from coeffs_t (Nt,10), the callable, or
+        the Laplacian when only the boundary condition is general"""
+        if coeffs_t is None:
+            if self.domain_coeffs is None:
+                coeffs_t = onp.tile((0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 1.0), (X_test.shape[0], 1))
+            elif self.operator is None:
+                raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
+                                 'points as coeffs_t (Nt,10)')
+            else:
+                coeffs_t = self._operator_at(X_test)
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
+        if coeffs_t.shape != (X_test.shape[0], 10):
+            raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, 10), got {coeffs_t.shape}')
+        rows = self._fields_op(X_test, self._op_names).download().reshape(10, -1)
+        psi = (coeffs_t.T * rows).sum(axis=0)                     # psi_t[u]: a combination of the ten rows, per test point
+        return get_context().array(onp.stack([rows[0], rows[1], rows[2], psi]))
+
+    def PDE_residual(self, X_test, coeffs_t=None):
+        """pointwise residual -Delta u + alpha u^m - f at X_test from the derivatives of the GP solution (rhs evaluated at X_test); with
+        a domain operator -psi_t[u] + alpha u^m - f, psi_t from the callable `operator` or from coeffs_t (Nt,10) (needed when the
+        operator was set per point; ValueError otherwise)"""
         X_test = self._pts(X_test)
-        fields = self._fields(X_test, ('value', 'd1', 'd2', 'laplacian'))      # the rows gpk_pde_residual takes; it reads value and laplacian
+        if self.domain_coeffs is None and coeffs_t is not None:
+            raise ValueError('coeffs_t given, but no domain operator is set')
+        if self._general():
+            fields = self._psi_fields(X_test, coeffs_t)
+        else:
+            fields = self._fields(X_test, ('value', 'd1', 'd2', 'laplacian'))  # the rows gpk_pde_residual takes; it reads value and laplacian
         rhs = eval_callback(self.get_rhs, *X_test.T)
         self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields, None, rhs).download().reshape(-1)
         return self.test_residual
+
+    def boundary_residual(self, X_bt, coeffs_t, g_t):
+        """c0 u + c . grad u - g of the GP solution at the points X_bt (n,3), with coeffs_t (n,4) = (c0, c1, c2, c3) and g_t (n,) given
+        per point: how well the boundary condition holds between the boundary collocation points (numpy array, also `bdy_residual`)."""
+        X_bt = self._pts(onp.asarray(X_bt, dtype=onp.float64).reshape(-1, 3))
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64).reshape(-1, 4)
+        g_t = onp.asarray(g_t, dtype=onp.float64).ravel()
+        if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
+            raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
+        names = ('value', 'd1', 'd2', 'd3')
+        r = self._rows((self._fields_op if self._general() else self._fields)(X_bt, names), names)
+        self.bdy_residual = coeffs_t[:, 0] * r['value'] + coeffs_t[:, 1] * r['d1'] + coeffs_t[:, 2] * r['d2'] + coeffs_t[:, 3] * r['d3'] - g_t
+        return self.bdy_residual
 
 
 class Burgers(_GPEquation):

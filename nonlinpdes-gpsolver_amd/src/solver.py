@@ -8,13 +8,14 @@ from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
 
 
 def _operator_of(c):
-    """cfg.operator as the equation class takes it: a callable operator(x1, x2) -> six coefficient arrays, or None for the Laplacian
-    (absent, None, or the name 'laplace', which is what a driver's command line leaves there by default)"""
+    """cfg.operator as the equation class takes it: a callable -- operator(x1, x2) -> six coefficient arrays in two dimensions,
+    operator(x1, x2, x3) -> ten in three -- or None for the Laplacian (absent, None, or the name 'laplace', which is what a driver's
+    command line leaves there by default)"""
     op = getattr(c, 'operator', None)
     if op is None or (isinstance(op, str) and op == 'laplace'):
         return None
     if not callable(op):
-        raise ValueError(f"cfg.operator {op!r}: a callable operator(x1, x2), None or 'laplace'")
+        raise ValueError(f"cfg.operator {op!r}: a callable operator(x1, x2) / operator(x1, x2, x3), None or 'laplace'")
     return op
 
 
@@ -22,6 +23,13 @@ def _operator_lines(c):
     """header line of a variable-coefficient domain operator (nothing for the Laplacian: the reference's header)"""
     if _operator_of(c) is not None:
         return ['[Domain operator] - psi[u] + alpha*u^m = f, psi a second-order operator with variable coefficients given by the user']
+    return []
+
+
+def _time_lines(c):
+    """header line of a space-time problem in the 3-D class (cfg.time_dependent: axis 3 is time)"""
+    if getattr(c, 'time_dependent', False):
+        return ['[Time axis] x3 is time: no collocation data on the face x3 = max']
     return []
 
 
@@ -46,8 +54,13 @@ _EQUATIONS = {
         + _bc_lines(c),
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
     'Nonlinear_elliptic3d': (
-        lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, **k),
-        lambda c: ['[Equation type] Nonlinear elliptic equation in three space dimensions', '[Equation form] - \\Delta u + alpha*u^m = f'],
+        # (cfg.bc / cfg.robin_beta / cfg.operator as for two dimensions, the callable taking (x1, x2, x3) and returning ten arrays;
+        #  cfg.time_dependent: axis 3 is time, auto_sample() places no boundary points on the face x3 = max)
+        lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'),
+                                            robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c), **k),
+        lambda c: ['[Equation type] Nonlinear elliptic equation in three space dimensions',
+                   '[Equation form] - \\Delta u + alpha*u^m = f' if _operator_of(c) is None else '[Equation form] - psi[u] + alpha*u^m = f']
+        + _operator_lines(c) + _time_lines(c) + _bc_lines(c),
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
     'Burgers': (
         lambda c, **k: Burgers(alpha=c.alpha, nu=c.nu, **k),
@@ -136,7 +149,10 @@ class solver_GP(object):
         _say(print_option, 'pts_user', 'pts_n', e=self.eqn)
 
     def auto_sample(self, N_domain, N_boundary, sampled_type='random', print_option=True):
-        self.eqn.sampled_pts(N_domain, N_boundary, sampled_type=sampled_type)
+        if self.PDE_type == 'Nonlinear_elliptic3d' and getattr(self.config, 'time_dependent', False):
+            self.eqn.sampled_pts(N_domain, N_boundary, sampled_type=sampled_type, time_dependent=True)
+        else:
+            self.eqn.sampled_pts(N_domain, N_boundary, sampled_type=sampled_type)
         _say(print_option, 'pts_auto', 'pts_n', e=self.eqn, kind=sampled_type)
 
     def get_sample_IP(self, X_domain, X_boundary, X_data, print_option=True):
