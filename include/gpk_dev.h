@@ -37,12 +37,13 @@ int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, const doubl
  * csrc/gpk_gemm_dma_probe.hip, tools/gemm_dma_probe.py. */
 int gpk_debug_gemm_dma(gpk_handle h, int m, int n, int k, const double* A, int lda, const double* B, int ldb, double* C, int ldc);
 
-/* ---- the leading-zero ("staircase") state of a handle, for kernel-level tests of its consumers (csrc/dev/gpk_gn_dev_abi.inc) ---- */
-/* puts a leading-zero state on h as gpk_gn_step / gpk_mg_gn_step do while they run: closed form of slope 1/lead_div (nseg = 0), or a
- * piecewise profile of nseg <= 4 segments (c1, a, b, sd: nseg ints each, see GpkStair in csrc/gpk_common.h) whose column `base` is
- * column 0 of the operands; gpk_gemm_lz, gpk_trsm_lz and gpk_trsm_dinv(lead > 0) then consume it.  nseg = 0, lead_div = 1 resets it.
- * gpk_trsm_dinv moves the product frame while it runs: set the profile again before the next call. */
-int gpk_debug_set_profile(gpk_handle h, int lead_div, int nseg, const int* c1, const int* a, const int* b, const int* sd, int base);
+/* ---- leading-zero ("staircase") profiles, for kernel-level tests of their consumers (csrc/dev/gpk_gn_dev_abi.inc) ---- */
+/* Inside the library a profile is an ARGUMENT of the building blocks (GpkLz in csrc/gpk_common.h), never handle state.  The entry points
+ * below and gpk_gemm_lz, gpk_trsm_lz, gpk_trsm_dinv take a bare `lead`; in this build they complete it with the profile given here:
+ * closed form of slope 1/slope_div (nseg = 0), or a piecewise profile of nseg <= 4 segments (c1, a, b, sd: nseg ints each, see GpkStair)
+ * whose column `base` is column 0 of the operands, used whenever lead > 0.  nseg = 0, slope_div = 1 resets it.  A call never changes
+ * it: it holds until the next gpk_debug_set_profile. */
+int gpk_debug_set_profile(gpk_handle h, int slope_div, int nseg, const int* c1, const int* a, const int* b, const int* sd, int base);
 /* C <- alpha A^T A + beta C on the lower tiles only, A (k x n) with leading zeros (lead, or the profile of gpk_debug_set_profile):
  * the product that forms Hb = S^T S inside gpk_gn_step */
 int gpk_debug_syrk_lz(gpk_handle h, int n, int k, double alpha, const double* A, int lda, double beta, double* C, int ldc, int lead);

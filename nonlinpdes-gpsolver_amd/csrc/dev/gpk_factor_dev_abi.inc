@@ -15,7 +15,8 @@ extern "C" int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, 
                                        double* host_ms3) {
     if (!h || !H || !S || !C2 || !host_ms3) return GPK_ERR_ARG;
     hipStream_t side = nullptr, main_s = h->stream, chain = nullptr;
-    const hipStream_t restore = h->stream;
+    GpkStreamScope scope(h);                                         // (the handle's stream goes back on every way out; the workspace flag stays as it is)
+    const bool owner = h->ws_owner;
     int lo = 0, hi = 0;
     GPK_HIP(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
     if (h->tune.probe_chain_cus > 0) {
@@ -27,7 +28,7 @@ extern "C" int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, 
         GPK_HIP(h, hipExtStreamCreateWithCUMask(&chain, 8, ma));
         GPK_HIP(h, hipExtStreamCreateWithCUMask(&side, 8, mb));
         main_s = chain;
-        h->stream = chain;
+        scope.use(chain, owner);
     } else
     GPK_HIP(h, hipStreamCreateWithPriority(&side, hipStreamNonBlocking, lo));
     hipEvent_t e0, e1, ef;
@@ -41,9 +42,9 @@ extern "C" int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, 
         GPK_HIP(h, hipEventRecord(e0, main_s));
         if (mode == 1 || mode == 2) {
             GPK_HIP(h, hipStreamWaitEvent(side, e0, 0));
-            h->stream = side;
+            scope.use(side, owner);
             int rc = gpk_i_gemm(h, true, false, n, n, k, 1.0, S, lds, S, lds, 0.0, C2, ldc, true);
-            h->stream = main_s;
+            scope.use(main_s, owner);
             if (rc) return rc;
             GPK_HIP(h, hipEventRecord(ef, side));
         }
@@ -55,7 +56,6 @@ extern "C" int gpk_debug_overlap_probe(gpk_handle h, double* H, int n, int ldh, 
         host_ms3[mode] = ms;
     }
     GPK_HIP(h, hipFree(Hc));
-    h->stream = restore;
     if (chain) GPK_HIP(h, hipStreamDestroy(chain));
     GPK_HIP(h, hipStreamDestroy(side));
     GPK_HIP(h, hipEventDestroy(e0)); GPK_HIP(h, hipEventDestroy(e1)); GPK_HIP(h, hipEventDestroy(ef));

@@ -21,7 +21,7 @@ constexpr int GPK_MAX_TRSV_BLOCKS = 4096;
 // Piecewise-linear leading-zero profile ("staircase") of a block of right-hand sides: column c (storage order) is known to be zero
 // above row first_row(c).  Segment s covers the columns [c1[s-1], c1[s]) (c1[-1] = 0) with first_row(c) = a[s] + (b[s] - c) / sd[s]
 // (b[s] >= every c of the segment; sd huge = a flat step); columns from c1[nseg-1] on are dense.  The elliptic, Eikonal and Burgers
-// systems have ONE segment and keep the closed form (lead, lead_div) of gpk_i_gemm; the Darcy system's u-part has three (round 4):
+// systems have ONE segment and keep the closed form of GpkLz (below); the Darcy system's u-part has three (round 4):
 // slope 1 over the v1, v2 columns, flat over w1, w2, slope 1 over w0, v0 (gpk_gn.hip).  nseg = 0: no profile.
 struct GpkStair {
     int nseg = 0;
@@ -54,6 +54,46 @@ inline int gpk_stair_first_col(const GpkStair& st, int rows_end, int ncols) {
     }
     return lo;
 }
+
+// The leading-zero profile of a block of right-hand sides (the operand B of a product, stored [k][n]) as a VALUE: every building block that
+// exploits leading zeros takes one as an argument, and nothing keeps one on the handle.  It is one of three things, and says which:
+//   dense      (the default)     nothing is known to be zero;
+//   closed     lead > 0          column c < lead is zero above row (lead - 1 - c) / div, columns >= lead are dense (div 1: the elliptic systems
+//                                and the conservative Eikonal form; 3: Burgers);
+//   piecewise  pw.nseg > 0       a GpkStair in whose frame the block's column 0 is column col0 and its row 0 is row row0 (Eikonal, Darcy u-part).
+// sub() is the same profile seen from a sub-block; the closed form folds the offsets into `lead`, so col0 / row0 stay 0 there.
+struct GpkLz {
+    int lead = 0, div = 1;
+    GpkStair pw;
+    int col0 = 0, row0 = 0;
+    static GpkLz closed(int lead, int div = 1) {
+        GpkLz z;
+        if (lead > 0) { z.lead = lead; z.div = div > 0 ? div : 1; }
+        return z;
+    }
+    static GpkLz piecewise(const GpkStair& st) { GpkLz z; z.pw = st; return z; }
+    bool is_piecewise() const { return pw.nseg > 0; }
+    bool is_dense() const { return lead <= 0 && pw.nseg == 0; }
+    // first row of the block's column c that can be non-zero
+    int first_row(int c) const {
+        if (is_piecewise()) { const int r = gpk_stair_min(pw, col0 + c, col0 + c + 1) - row0; return r > 0 ? r : 0; }
+        return c < lead ? (lead - 1 - c) / div : 0;
+    }
+    // the block's rows [0, rows_end) are zero left of this column (of its ncols columns; the closed form is not clamped: <= 0 = none)
+    int first_col(int rows_end, int ncols) const {
+        if (is_piecewise()) return gpk_stair_first_col(pw, row0 + rows_end, col0 + ncols) - col0;
+        return lead - div * rows_end;
+    }
+    // the profile of the sub-block that starts dc columns to the right and dr rows below (dense once no column of a staircase is left)
+    GpkLz sub(int dc, int dr) const {
+        if (is_piecewise()) {
+            GpkLz z = *this;
+            z.col0 += dc; z.row0 += dr;
+            return z.col0 < pw.c1[pw.nseg - 1] ? z : GpkLz();
+        }
+        return closed(lead - dc - div * dr, div);
+    }
+};
 
 // Development / tuning switches of ONE handle (round 4: they used to be process-wide globals).  Defaults are the measured choices;
 // gpk_tune(handle, key, value) (include/gpk_debug.h) changes one -- tests force every kernel variant through it, A/B measurements
@@ -158,29 +198,22 @@ struct gpk_ctx {
     int pipe_tev_used = 0;
     double prof_syrk_ms = 0;                // accumulated duration of the SYRK launches on the GEMM stream (pipelined mode)
     int prof_pipelined = 0;
-    // split-K GEMM launches (gpk_gemm.hip, GemmArgs::splitk): requested chunk count for the NEXT gpk_i_gemm calls (0/1 = off; set and
-    // cleared by the caller around its launches), the partial-sum workspace and the per-tile arrival counters.  One workspace: only
-    // one stream at a time may issue split launches (the GEMM stream of the pipeline does)
-    int splitk_req = 0;
-    int tile_req = 0;               // 64 / 128: the NEXT gpk_i_gemm calls use 64 x 64 / 128 x 64 tiles whatever the tile count (the caller gets its
-                                    // parallelism from split-K); 0 = automatic
+    // split-K GEMM launches (gpk_gemm.hip, GemmArgs::splitk; the caller asks for them with the `splitk` argument of gpk_i_gemm): the
+    // partial-sum workspace and the per-tile arrival counters.  One workspace: only one stream at a time may issue launches that use it
     double* d_splitk_ws = nullptr;
     size_t splitk_ws_cap = 0;       // bytes
     unsigned* d_splitk_cnt = nullptr;
     int splitk_cnt_cap = 0;         // counters
     void* sk_cache = nullptr;       // tile-list ("stream-K") plans of the GEMM launches, by launch shape (gpk_gemm.hip)
-    int no_sk = 0;                  // != 0: the NEXT gpk_i_gemm calls must not use tile lists (their partial-sum workspace and counters are
-                                    // the split-K ones: one stream of a handle at a time -- set around launches on secondary streams)
+    bool ws_owner = true;           // launches on `stream` may use tile lists (their partial-sum workspace and counters are the split-K ones: one
+                                    // stream of a handle at a time).  Written by GpkStreamScope only, together with `stream`
     double* d_pts = nullptr;        // packed collocation points (SoA), grown on demand
     size_t pts_cap = 0;
     int num_cu = 256;
-    GpkStair stair;                 // piecewise staircase of the step being issued (nseg > 0: it replaces the closed form (lead, lead_div) in every
-                                    // launch that is given a non-zero `lead`); stair_col0 / stair_row0: global column of the launch's column 0 and
-                                    // global row of its k = 0, set by the caller around each gpk_i_gemm call
-    int stair_col0 = 0, stair_row0 = 0;
-    int stair_base = 0;             // gpk_i_trsm_left_dinv with a piecewise profile: global column of ITS column 0 (a column shard of the sharded step)
-    int lead_div = 1;               // slope of the leading-zero staircase while a Gauss-Newton step is being issued: column c of the
-                                    // right-hand side is zero above row (lead-1-c) / lead_div (1: elliptic, Eikonal; 3: Burgers)
+#ifdef GPK_DEV
+    GpkLz debug_profile;            // development build only: the profile last given to gpk_debug_set_profile (`lead` not set).  Read by the
+                                    // extern "C" wrappers alone (gpk_debug_lz), never by a gpk_i_* function
+#endif
     hipStream_t side[3] = {nullptr, nullptr, nullptr};   // column-group streams of the multi-RHS triangular solve
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     // per-phase HIP-event timing of gpk_gn_step (bench.py roofline): 0 TRSM, 1 SYRK launch, 2 POTRF, 3 TRSV+update
@@ -211,28 +244,57 @@ int gpk_bad_arg(gpk_handle h, const char* what);
     } while (0)
 #define GPK_LAUNCH_CHECK(h) GPK_HIP((h), hipGetLastError())
 
+// Which stream the building blocks issue on, and whether launches on it may use the tile-list / split-K workspace, for the lifetime of the
+// scope: use() switches both, the destructor puts both back on every way out.  Apart from gpk_create / gpk_set_stream nothing else
+// assigns gpk_ctx::stream, and nothing else writes gpk_ctx::ws_owner.
+class GpkStreamScope {
+    gpk_handle h;
+    const hipStream_t stream0;
+    const bool owner0;
+public:
+    explicit GpkStreamScope(gpk_handle hh) : h(hh), stream0(hh->stream), owner0(hh->ws_owner) {}
+    ~GpkStreamScope() { h->stream = stream0; h->ws_owner = owner0; }
+    GpkStreamScope(const GpkStreamScope&) = delete;
+    GpkStreamScope& operator=(const GpkStreamScope&) = delete;
+    void use(hipStream_t s, bool ws_owner) { h->stream = s; h->ws_owner = ws_owner; }
+    void back() { use(stream0, owner0); }
+};
+
+#ifdef GPK_DEV
+// development build only: the argument the extern "C" entry points that take a bare `lead` (gpk_gemm_lz, gpk_trsm_lz, gpk_trsm_dinv,
+// gpk_debug_syrk_lz) make of it and of the profile last given to gpk_debug_set_profile
+inline GpkLz gpk_debug_lz(gpk_handle h, int lead) {
+    if (lead <= 0) return GpkLz();
+    return h->debug_profile.is_piecewise() ? h->debug_profile : GpkLz::closed(lead, h->debug_profile.div);
+}
+#else
+inline GpkLz gpk_debug_lz(gpk_handle, int lead) { return GpkLz::closed(lead); }
+#endif
+
 // ---- internal (stream-ordered, no host sync) building blocks -------------------------------------------------
-// C <- alpha*op(A)*op(B) + beta*C.  lower_only: skip tiles strictly above the diagonal (square C).
+// C <- alpha*op(A)*op(B) + beta*C.  lower_only: skip tiles strictly above the diagonal (square C).  lz: leading zeros of B (tb = false;
+// with lower_only only for the product A^T A).  splitk: split-K factor asked for (0 / 1 = none); tile: 64 / 128 = 64 x 64 / 128 x 64 tiles
+// whatever the tile count (the caller gets its parallelism from split-K), 0 = automatic
 int gpk_i_gemm(gpk_handle h, bool ta, bool tb, int m, int n, int k, double alpha, const double* A, int lda,
-               const double* B, int ldb, double beta, double* C, int ldc, bool lower_only, int lead = 0, bool tri_a = false,
-               bool skip_upper = false);
+               const double* B, int ldb, double beta, double* C, int ldc, bool lower_only, const GpkLz& lz = GpkLz(), bool tri_a = false,
+               bool skip_upper = false, int splitk = 0, int tile = 0);
 int gpk_i_potrf(gpk_handle h, double* A, int n, int lda, int pivot_base);               // info -> h->d_info
 int gpk_i_potrf_panel(gpk_handle h, double* A, int nrows, int ob, int lda, int pivot_base, bool left_looking = false,
                       void* ev_wait_p1 = nullptr, void* ev_rec_pre = nullptr);   // (hipEvent_t; see gpk_factor.hip)
-// Hb <- chol(W^T W) (lower, nc x nc; W is rows x nc with the leading-zero shape `lead` of gpk_i_gemm), the product and the
+// Hb <- chol(W^T W) (lower, nc x nc; W is rows x nc with the leading-zero profile lz), the product and the
 // factorisation pipelined by 512-column blocks on two CU partitions (gpk_factor.hip); d_loss (device, may be null) receives
 // the unfactored last diagonal entry (W^T W)[nc-1][nc-1]
-int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, int lead, double* Hb, int ldh, double* d_loss);
+int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, const GpkLz& lz, double* Hb, int ldh, double* d_loss);
 int gpk_i_trsm_left(gpk_handle h, bool trans, const double* L, int n, int ldl, double* B, int nrhs, int ldb);
 // forward solve exploiting leading zeros of the right-hand side columns (see gpk_factor.hip)
-int gpk_i_trsm_left_lz(gpk_handle h, const double* L, int n, int ldl, double* B, int nrhs, int ldb, int lead, int row0);
+int gpk_i_trsm_left_lz(gpk_handle h, const double* L, int n, int ldl, double* B, int nrhs, int ldb, const GpkLz& lz);
 // same, right-hand sides split into independent column groups that run on concurrent streams
 int gpk_i_trsm_left_mt(gpk_handle h, bool trans, const double* L, int n, int ldl, double* B, int nrhs, int ldb);
 // explicit inverses of the db x db diagonal blocks of L (Dinv: n x db, ld db; db = 256, 512 or 1024) and the all-GEMM forward
 // solve built on them: X <- L^{-1} B out of place, B is scratch afterwards (see gpk_factor.hip)
 int gpk_i_trtri_diag(gpk_handle h, const double* L, int n, int ldl, double* Dinv, int db);
 int gpk_i_trsm_left_dinv(gpk_handle h, const double* L, const double* Dinv, int db, int n, int ldl, double* B, int ldb,
-                         double* X, int ldx, int nrhs, int lead, int row0);
+                         double* X, int ldx, int nrhs, const GpkLz& lz);
 int gpk_i_pipe_streams(gpk_handle h);                                                   // the two CU-masked streams of the pipeline (gpk_factor.hip); called by gpk_create
 void gpk_i_sk_free(gpk_handle h);                                                      // tile-list plans (gpk_gemm.hip)
 int gpk_i_splitk_reserve(gpk_handle h);                                                 // workspace + counters of the split-K launches
@@ -243,14 +305,12 @@ int gpk_i_dot(gpk_handle h, const double* x, const double* y, int n, double* d_o
 int gpk_i_ensure_points(gpk_handle h, size_t doubles);
 // pieces of the Gauss-Newton step used by the multi-GPU schedule (gpk_gn.hip)
 int gpk_i_gn_dims(gpk_handle h, const gpk_gn_problem* p, int* nz, int* rows);
-// the column layout gpk_gn_step runs a system in (1 elliptic, 2 Eikonal, 3 Burgers, 4 Darcy, 0 dense) and the handle state that goes with it for
-// one call (Eikonal: its two-segment profile in gpk_ctx::stair; Burgers: lead_div = 3); leave resets it.  first_row: the first row of column c
-// (storage order, c < nz) that can be non-zero under the layout entered
+// the column layout gpk_gn_step runs a system in (1 elliptic, 2 Eikonal, 3 Burgers, 4 Darcy, 0 dense) and the leading-zero profile of
+// [A(z) | F] (storage order) under it: Eikonal its two-segment profile on the GEMM-only solve path, Burgers the closed form of slope 1/3;
+// dense for the layouts 0 and 4 (Darcy's two factors have a profile each: the u-part's is gpk_i_gn_darcy_u_profile)
 int gpk_i_gn_layout(gpk_handle h, const gpk_gn_problem* p);
-void gpk_i_gn_layout_enter(gpk_handle h, const gpk_gn_problem* p, int rev);
-void gpk_i_gn_layout_leave(gpk_handle h);
-int gpk_i_gn_first_row(gpk_handle h, int nz, int c);
-void gpk_i_gn_darcy_profile(gpk_handle h, int Nd);                   // the Darcy u-part's profile into gpk_ctx::stair (sharded step)
+GpkLz gpk_i_gn_profile(gpk_handle h, const gpk_gn_problem* p, int rev);
+GpkLz gpk_i_gn_darcy_u_profile(int Nd);
 int gpk_i_gn_darcy_add_a(gpk_handle h, const gpk_gn_problem* p, double* Hb, int ldh, int r0, int r1, const double* aF, int ldaf);
 int gpk_i_gn_exact_loss(gpk_handle h, const gpk_gn_problem* p, const double* z, double** d_out);   // gpk_tune key 52: loss(z) by substitution on h->stream
 int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, const double* Hb, int ldh, double* scratch, double* delta,

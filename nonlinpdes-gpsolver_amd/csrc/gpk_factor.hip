@@ -1044,15 +1044,15 @@ int gpk_i_trsm_left(gpk_handle h, bool trans, const double* L, int n, int ldl, d
     return 0;
 }
 
-// Forward solve L X = B when column c of B (c < lead) is known to be zero in the rows above (lead - 1 - c): the
-// Gauss-Newton right-hand side [A(z) | F] with the unknowns stored in REVERSE order has exactly this shape (column j of
-// A is zero above row j).  For the sub-problem on rows [row0, row0 + n) only the columns
-// c >= lead - (row0 + n) can be non-zero, so every recursive solve, update GEMM and diagonal solve is restricted to
-// that contiguous range (rounded down to 64 columns to keep tiles and vector loads aligned).  Columns >= lead are dense.
-int gpk_i_trsm_left_lz(gpk_handle h, const double* L, int n, int ldl, double* B, int nrhs, int ldb, int lead, int row0) {
+// Forward solve L X = B when column c of B is known to be zero above row lz.first_row(c) (closed form: c < lead is zero in the
+// rows above (lead - 1 - c) / div): the Gauss-Newton right-hand side [A(z) | F] with the unknowns stored in REVERSE order has
+// exactly this shape (column j of A is zero above row j).  In the first n rows only the columns
+// c >= lz.first_col(n) can be non-zero, so every recursive solve, update GEMM and diagonal solve is restricted to
+// that contiguous range (rounded down to 64 columns to keep tiles and vector loads aligned); the recursion hands every
+// sub-block its own view of the profile (GpkLz::sub).
+int gpk_i_trsm_left_lz(gpk_handle h, const double* L, int n, int ldl, double* B, int nrhs, int ldb, const GpkLz& lz) {
     if (n <= 0 || nrhs <= 0) return 0;
-    const int sd = h->lead_div > 0 ? h->lead_div : 1;                // staircase slope 1/sd: column c is zero above row (lead-1-c)/sd
-    int clo = lead - sd * (row0 + n);
+    int clo = lz.first_col(n, nrhs);
     clo = clo > 0 ? (clo / NB) * NB : 0;
     if (clo >= nrhs) return 0;
     if (h->tune.strip && n <= SB && (n & 15) == 0) {
@@ -1068,14 +1068,12 @@ int gpk_i_trsm_left_lz(gpk_handle h, const double* L, int n, int ldl, double* B,
     const int n1 = split(n, (h->tune.strip && n > SB) ? SB : NB), n2 = n - n1;
     const double* L21 = L + (long)n1 * ldl;
     double* B2 = B + (long)n1 * ldb;
-    GPK_TRY(gpk_i_trsm_left_lz(h, L, n1, ldl, B, nrhs, ldb, lead, row0));
-    int c1 = lead - sd * (row0 + n1);                                // X[rows of part 1] is zero left of this column
+    GPK_TRY(gpk_i_trsm_left_lz(h, L, n1, ldl, B, nrhs, ldb, lz));
+    int c1 = lz.first_col(n1, nrhs);                                 // X[rows of part 1] is zero left of this column
     c1 = c1 > 0 ? (c1 / NB) * NB : 0;
-    if (c1 < nrhs) {                                                 // X1[k][c] is zero for row0 + k < (lead-1-c)/sd: late K start per tile
-        const int lz = lead - sd * row0 - c1;
-        GPK_TRY(gpk_i_gemm(h, false, false, n2, nrhs - c1, n1, -1.0, L21, ldl, B + c1, ldb, 1.0, B2 + c1, ldb, false, lz > 0 ? lz : 0));
-    }
-    GPK_TRY(gpk_i_trsm_left_lz(h, L21 + n1, n2, ldl, B2, nrhs, ldb, lead, row0 + n1));
+    if (c1 < nrhs)                                                   // X1[k][c] is zero for k < first_row(c): late K start per tile
+        GPK_TRY(gpk_i_gemm(h, false, false, n2, nrhs - c1, n1, -1.0, L21, ldl, B + c1, ldb, 1.0, B2 + c1, ldb, false, lz.sub(c1, 0)));
+    GPK_TRY(gpk_i_trsm_left_lz(h, L21 + n1, n2, ldl, B2, nrhs, ldb, lz.sub(0, n1)));
     return 0;
 }
 
@@ -1116,32 +1114,25 @@ int gpk_i_trtri_diag(gpk_handle h, const double* L, int n, int ldl, double* Dinv
 }
 
 int gpk_i_trsm_left_dinv(gpk_handle h, const double* L, const double* Dinv, int db, int n, int ldl, double* B, int ldb,
-                         double* X, int ldx, int nrhs, int lead, int row0) {
+                         double* X, int ldx, int nrhs, const GpkLz& lz) {
     if (n <= 0 || nrhs <= 0) return 0;
-    const int sd = h->lead_div > 0 ? h->lead_div : 1;                // staircase slope 1/sd: column c is zero above row (lead-1-c)/sd
-    // piecewise profile (gpk_ctx::stair, Darcy): columns and rows are those of this call's top level (column 0 of B, row 0 of L); every
-    // product below is told where its column 0 / its k = 0 lie in that frame, and `lead` only says "there is a profile"
-    const bool pw = lead > 0 && h->stair.nseg > 0;
-    const int base = pw ? h->stair_base : 0;                         // (round 6: B's column 0 is column `base` of the profile's frame -- a column shard)
-    int clo = pw ? gpk_stair_first_col(h->stair, row0 + n, base + nrhs) - base : lead - sd * (row0 + n);   // (lead = 0: dense right-hand sides)
+    // lz: the leading zeros of B, whose column 0 and row 0 are those of this call (a column shard of the sharded step hands in the
+    // profile already shifted to its first column); every product below and both halves of the recursion get the profile as seen
+    // from their own sub-block (GpkLz::sub).  Dinv is advanced with L, so every level indexes both from 0
+    int clo = lz.first_col(n, nrhs);                                 // (dense right-hand sides: 0)
     clo = clo > 0 ? (clo / NB) * NB : 0;
     if (clo >= nrhs) return 0;
-    if (n <= db) {
-        const int lz = pw ? 1 : lead - sd * row0 - clo;
-        h->stair_col0 = base + clo; h->stair_row0 = row0;
-        return gpk_i_gemm(h, false, false, n, nrhs - clo, n, 1.0, Dinv + (long)row0 * db, db, B + clo, ldb, 0.0, X + clo, ldx,
-                          false, lz > 0 ? lz : 0, true);
-    }
+    if (n <= db)
+        return gpk_i_gemm(h, false, false, n, nrhs - clo, n, 1.0, Dinv, db, B + clo, ldb, 0.0, X + clo, ldx, false, lz.sub(clo, 0), true);
     int n1 = ((n / 2 + db - 1) / db) * db;                           // first part: about half, a multiple of the block size
     if (n1 >= n) n1 = db;
     const int n2 = n - n1;
     const double* L21 = L + (long)n1 * ldl;
-    GPK_TRY(gpk_i_trsm_left_dinv(h, L, Dinv, db, n1, ldl, B, ldb, X, ldx, nrhs, lead, row0));
-    int c1 = pw ? gpk_stair_first_col(h->stair, row0 + n1, base + nrhs) - base : lead - sd * (row0 + n1);   // X[rows of part 1] is zero left of this column
+    GPK_TRY(gpk_i_trsm_left_dinv(h, L, Dinv, db, n1, ldl, B, ldb, X, ldx, nrhs, lz));
+    int c1 = lz.first_col(n1, nrhs);                                 // X[rows of part 1] is zero left of this column
     c1 = c1 > 0 ? (c1 / NB) * NB : 0;
     if (c1 < nrhs) {
-        const int lz = pw ? 1 : lead - sd * row0 - c1;
-        h->stair_col0 = base + c1; h->stair_row0 = row0;
+        int splitk = 0;
         if (h->tune.solve_splitk && gpk_i_splitk_reserve(h) == 0) {
             // launches that fill the chip badly (a fraction of a wave, or 1.2 waves): more, shorter workgroups (split-K)
             const long t64 = (long)gpk_ceil_div(n2, 64) * gpk_ceil_div(nrhs - c1, 64);
@@ -1153,14 +1144,13 @@ int gpk_i_trsm_left_dinv(gpk_handle h, const double* L, const double* Dinv, int 
                 const double c = (double)((tiles * s2 + slots - 1) / slots) / s2 + 0.04 * (s2 - 1);
                 if (c < bc - 1e-9) { bc = c; best = s2; }
             }
-            h->splitk_req = best;
+            splitk = best;
         }
-        const int rc = gpk_i_gemm(h, false, false, n2, nrhs - c1, n1, -1.0, L21, ldl, X + c1, ldx, 1.0, B + (long)n1 * ldb + c1, ldb,
-                                  false, lz > 0 ? lz : 0);
-        h->splitk_req = 0;
-        GPK_TRY(rc);
+        GPK_TRY(gpk_i_gemm(h, false, false, n2, nrhs - c1, n1, -1.0, L21, ldl, X + c1, ldx, 1.0, B + (long)n1 * ldb + c1, ldb,
+                           false, lz.sub(c1, 0), false, false, splitk));
     }
-    return gpk_i_trsm_left_dinv(h, L21 + n1, Dinv, db, n2, ldl, B + (long)n1 * ldb, ldb, X + (long)n1 * ldx, ldx, nrhs, lead, row0 + n1);
+    return gpk_i_trsm_left_dinv(h, L21 + n1, Dinv + (long)n1 * db, db, n2, ldl, B + (long)n1 * ldb, ldb, X + (long)n1 * ldx, ldx, nrhs,
+                                lz.sub(0, n1));
 }
 
 // The 64-row diagonal solves of a multi-RHS TRSM keep only nrhs/64 waves busy and sit on the critical path between
@@ -1182,25 +1172,26 @@ int gpk_i_trsm_left_mt(gpk_handle h, bool trans, const double* L, int n, int ldl
     const int per = ((nrhs / G + 127) / 128) * 128;                  // group width, multiple of 128 columns
     hipStream_t main_stream = h->stream;
     GPK_HIP(h, hipEventRecord(h->ev_fork, main_stream));
+    GpkStreamScope scope(h);                                         // (the workspace stays with whichever stream had it: as before)
+    const bool owner = h->ws_owner;
     int rc = 0;
     for (int g = 0; g < G && rc == 0; ++g) {
         const int c0 = g * per;
         if (c0 >= nrhs) break;
         const int w = (nrhs - c0 < per || g == G - 1) ? nrhs - c0 : per;
         if (g > 0) {
-            h->stream = h->side[g - 1];
+            scope.use(h->side[g - 1], owner);
             hipError_t e = hipStreamWaitEvent(h->stream, h->ev_fork, 0);
-            if (e != hipSuccess) { h->stream = main_stream; return gpk_fail(h, e, "hipStreamWaitEvent", __FILE__, __LINE__); }
+            if (e != hipSuccess) return gpk_fail(h, e, "hipStreamWaitEvent", __FILE__, __LINE__);
         }
         rc = gpk_i_trsm_left(h, trans, L, n, ldl, B + c0, w, ldb);
         if (g > 0) {
             hipError_t e = hipEventRecord(h->ev_join[g - 1], h->stream);
-            h->stream = main_stream;
+            scope.back();
             if (e == hipSuccess) e = hipStreamWaitEvent(main_stream, h->ev_join[g - 1], 0);
             if (e != hipSuccess) return gpk_fail(h, e, "join", __FILE__, __LINE__);
         }
     }
-    h->stream = main_stream;
     return rc;
 }
 
@@ -1317,7 +1308,7 @@ int gpk_i_potrf_panel(gpk_handle h, double* A, int nrows, int ob, int lda, int p
     return 0;
 }
 
-static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int nc, int lead, double* Hb, int ldh, double* d_loss,
+static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int nc, const GpkLz& lz, double* Hb, int ldh, double* d_loss,
                            int pivot_base);
 
 static int potrf_seq(gpk_handle h, double* A, int n, int lda, int pivot_base) {
@@ -1359,8 +1350,7 @@ static int potrf_lookahead(gpk_handle h, double* A, int n, int lda, int pivot_ba
     hipEvent_t* ev_col = h->pipe_ev.data();                          // [J]: block column j carries every update of the blocks before it
     hipEvent_t* ev_chain = h->pipe_ev.data() + J;                    // [J]: block column j is factored
     hipEvent_t ev_fork = h->pipe_ev[2 * J];
-    auto fail = [&](hipError_t e, const char* what) {
-        h->stream = main_s; h->no_sk = 0;
+    auto fail = [&](hipError_t e, const char* what) {               // drain both side streams before reporting
         (void)hipStreamSynchronize(G); (void)hipStreamSynchronize(C);
         return gpk_fail(h, e, what, __FILE__, __LINE__);
     };
@@ -1371,23 +1361,23 @@ static int potrf_lookahead(gpk_handle h, double* A, int n, int lda, int pivot_ba
     LA_HIP(hipEventRecord(ev_fork, main_s));
     LA_HIP(hipStreamWaitEvent(G, ev_fork, 0));
     LA_HIP(hipStreamWaitEvent(C, ev_fork, 0));
+    GpkStreamScope scope(h);                                         // (the tile-list workspace belongs to the GEMM stream while both run)
     for (int j = 0; j < J && rc == 0; ++j) {
         const int k0 = j * OB, ob = std::min(OB, n - k0), k1 = k0 + ob, rest = n - k1;
         if (j > 0) {                                                 // chain of block column j on the chain partition
-            h->stream = C; h->no_sk = 1;
+            scope.use(C, false);
             LA_HIP(hipStreamWaitEvent(C, ev_col[j], 0));
             rc = gpk_i_potrf_panel(h, A + (long)k0 * lda + k0, n - k0, ob, lda, pivot_base + k0);
-            h->no_sk = 0;
             if (rc) break;
             LA_HIP(hipEventRecord(ev_chain[j], C));
         }
         if (rest <= 0) break;
-        h->stream = G;
+        scope.use(G, true);
         if (j > 0) LA_HIP(hipStreamWaitEvent(G, ev_chain[j], 0));
         const double* P = A + (long)k1 * lda + k0;                   // rows k1.. of the factored block column j
         const int ob1 = std::min(OB, rest);
         // the next block column first (its top square is a diagonal block: tiles above the diagonal are not computed) ...
-        rc = gpk_i_gemm(h, false, true, rest, ob1, ob, -1.0, P, lda, P, lda, 1.0, A + (long)k1 * lda + k1, lda, false, 0, false, true);
+        rc = gpk_i_gemm(h, false, true, rest, ob1, ob, -1.0, P, lda, P, lda, 1.0, A + (long)k1 * lda + k1, lda, false, GpkLz(), false, true);
         if (rc) break;
         LA_HIP(hipEventRecord(ev_col[j + 1], G));
         // ... then everything to its right, next to the chain of block column j + 1
@@ -1398,7 +1388,6 @@ static int potrf_lookahead(gpk_handle h, double* A, int n, int lda, int pivot_ba
             if (rc) break;
         }
     }
-    h->stream = main_s; h->no_sk = 0;
     if (rc) { (void)hipStreamSynchronize(G); (void)hipStreamSynchronize(C); return rc; }
     LA_HIP(hipEventRecord(ev_fork, G));                              // (re-used: everything the GEMM partition was given)
     LA_HIP(hipStreamWaitEvent(main_s, ev_fork, 0));
@@ -1415,7 +1404,7 @@ int gpk_i_potrf(gpk_handle h, double* A, int n, int lda, int pivot_base) {
 #ifdef GPK_DEV
         if (h->tune.potrf_lookahead) return potrf_lookahead(h, A, n, lda, pivot_base);
 #endif
-        return potrf_pipelined(h, nullptr, 0, 0, n, 0, A, lda, nullptr, pivot_base);
+        return potrf_pipelined(h, nullptr, 0, 0, n, GpkLz(), A, lda, nullptr, pivot_base);
     }
     return potrf_seq(h, A, n, lda, pivot_base);
 }
@@ -1487,7 +1476,7 @@ static int pipe_setup(gpk_handle h, size_t nev, size_t ntev, bool reserve = true
     return 0;
 }
 
-int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, int lead, double* Hb, int ldh, double* d_loss) {
+int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, const GpkLz& lz, double* Hb, int ldh, double* d_loss) {
     const int J = gpk_ceil_div(nc, 512) < 3 ? 0 : (int)pipe_blocks(h, nc).size() - 1;   // (orders below 1025: nothing to overlap)
     h->pipe_tev_used = 0;
     h->prof_pipelined = 0;
@@ -1504,15 +1493,14 @@ int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, i
         }
         const int ph = h->prof_phase;
         h->prof_phase = 2;                                           // (flop accounting: the product, apart from the factorisation's updates)
-        h->stair_col0 = 0; h->stair_row0 = 0;                        // (a piecewise profile set by the caller, gpk_ctx::stair, is in W's own frame)
-        const int rcp = gpk_i_gemm(h, true, false, nc, nc, rows, 1.0, W, ldw, W, ldw, 0.0, Hb, ldh, true, lead);
+        const int rcp = gpk_i_gemm(h, true, false, nc, nc, rows, 1.0, W, ldw, W, ldw, 0.0, Hb, ldh, true, lz);
         h->prof_phase = ph;
         GPK_TRY(rcp);
         if (h->prof) { GPK_HIP(h, hipEventRecord(h->pipe_tev[1], h->stream)); h->pipe_tev_used = 2; }
         if (d_loss) GPK_HIP(h, hipMemcpyAsync(d_loss, Hb + (long)(nc - 1) * ldh + (nc - 1), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         return gpk_i_potrf(h, Hb, nc, ldh, 0);
     }
-    GPK_TRY(potrf_pipelined(h, W, ldw, rows, nc, lead, Hb, ldh, d_loss, 0));
+    GPK_TRY(potrf_pipelined(h, W, ldw, rows, nc, lz, Hb, ldh, d_loss, 0));
     h->prof_pipelined = 1;
     return 0;
 }
@@ -1520,7 +1508,7 @@ int gpk_i_syrk_potrf(gpk_handle h, const double* W, int ldw, int rows, int nc, i
 // W != nullptr: Hb <- chol(W^T W), the product pipelined with the factorisation (Gauss-Newton step).  W == nullptr: Hb holds a
 // symmetric positive definite matrix (lower triangle) and is factored in place -- the same two-partition schedule without the
 // products: left-looking 512-column block updates on the GEMM partition, panel chains on the chain partition.
-static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int nc, int lead, double* Hb, int ldh, double* d_loss,
+static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int nc, const GpkLz& lz, double* Hb, int ldh, double* d_loss,
                            int pivot_base) {
     const std::vector<int> bnd = pipe_blocks(h, nc);
     const int J = (int)bnd.size() - 1;
@@ -1533,13 +1521,10 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
         // few tiles, long K: split K so that the launch has about h->tune.pipeline_units workgroups (see GemmArgs::splitk)
         const int th = h->tune.pipeline_tile == 128 ? 128 : h->tune.pipeline_tile == 64 ? 64 : 32;
         const long tiles = (long)gpk_ceil_div(nc - j0, th) * gpk_ceil_div(j1 - j0, 64);
-        h->splitk_req = h->tune.pipeline_units > 0 ? (int)((h->tune.pipeline_units + tiles / 2) / tiles) : 0;
-        h->tile_req = jb > 0 ? h->tune.pipeline_tile : 0;
-        h->stair_col0 = j0; h->stair_row0 = 0;                       // (piecewise profile of the caller: this product's column 0 is W's column j0)
-        const int r = gpk_i_gemm(h, true, false, nc - j0, j1 - j0, rows, 1.0, W + j0, ldw, W + j0, ldw, 0.0, Hb + (long)j0 * ldh + j0, ldh, false,
-                                 lead > j0 ? lead - j0 : 0, false, true);
-        h->splitk_req = 0; h->tile_req = 0;
-        return r;
+        const int splitk = h->tune.pipeline_units > 0 ? (int)((h->tune.pipeline_units + tiles / 2) / tiles) : 0;
+        // (this product's column 0 is W's column j0)
+        return gpk_i_gemm(h, true, false, nc - j0, j1 - j0, rows, 1.0, W + j0, ldw, W + j0, ldw, 0.0, Hb + (long)j0 * ldh + j0, ldh, false,
+                          lz.sub(j0, 0), false, true, splitk, jb > 0 ? h->tune.pipeline_tile : 0);
     };
     hipEvent_t* ev_ready = h->pipe_ev.data();                        // [J]
     hipEvent_t* ev_chain = h->pipe_ev.data() + J;                    // [J]
@@ -1547,8 +1532,7 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
     hipEvent_t* ev_ready2 = h->pipe_ev.data() + 2 * J + 1;           // [J] (lookahead only)
     hipEvent_t* ev_pre = h->pipe_ev.data() + 3 * J + 1;              // [J] (lookahead only)
     int rc = 0, ntev = 0;
-    auto fail = [&](hipError_t e, const char* what) {               // restore the handle's stream and drain both side streams before reporting
-        h->stream = main_s; h->no_sk = 0;
+    auto fail = [&](hipError_t e, const char* what) {               // drain both side streams before reporting
         (void)hipStreamSynchronize(G); (void)hipStreamSynchronize(C);
         return gpk_fail(h, e, what, __FILE__, __LINE__);
     };
@@ -1582,18 +1566,18 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
     PIPE_HIP(hipEventRecord(ev_fork, main_s));
     PIPE_HIP(hipStreamWaitEvent(G, ev_fork, 0));
     PIPE_HIP(hipStreamWaitEvent(C, ev_fork, 0));
+    GpkStreamScope scope(h);                                         // (the handle's stream and the workspace go back on every way out)
     for (int j = 0; j < J && rc == 0; ++j) {
         const int j0 = bnd[j], ob = bnd[j + 1] - j0, m = nc - j0;
         const int pb0 = j > 0 ? bnd[j - 1] : 0, pob = j0 - pb0;      // the previous block: first column, width
         double* Hjj = Hb + (long)j0 * ldh + j0;
-        h->stream = G;
+        scope.use(G, true);
         if (j > 0) {
             const double* Lrow = Hb + (long)j0 * ldh;                // rows j0.. of the factored panels, columns 0..j0
             if (j > 1) {                                             // panels 0..j-2: their chain finished an iteration ago
                 const long tiles = (long)gpk_ceil_div(m, 32) * gpk_ceil_div(ob, 64);
-                h->splitk_req = h->tune.pipeline_units > 0 ? (int)((h->tune.pipeline_units + tiles / 2) / tiles) : 0;
-                rc = gpk_i_gemm(h, false, true, m, ob, pb0, -1.0, Lrow, ldh, Lrow, ldh, 1.0, Hjj, ldh, false, 0, false, true);
-                h->splitk_req = 0;
+                const int splitk = h->tune.pipeline_units > 0 ? (int)((h->tune.pipeline_units + tiles / 2) / tiles) : 0;
+                rc = gpk_i_gemm(h, false, true, m, ob, pb0, -1.0, Lrow, ldh, Lrow, ldh, 1.0, Hjj, ldh, false, GpkLz(), false, true, splitk);
                 if (rc) break;
             }
             // ... then block j-1, whose chain is still running: its first seven panels as soon as they are final (ev_pre), the last
@@ -1604,7 +1588,7 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
             const int k1 = (h->tune.pipeline_lookahead && pob > NB) ? pob - NB : 0;
             if (k1 > 0) {
                 PIPE_HIP(hipStreamWaitEvent(G, ev_pre[j - 1], 0));
-                rc = gpk_i_gemm(h, false, true, m, ob, k1, -1.0, Lb, ldh, Lb, ldh, 1.0, Hjj, ldh, false, 0, false, true);
+                rc = gpk_i_gemm(h, false, true, m, ob, k1, -1.0, Lb, ldh, Lb, ldh, 1.0, Hjj, ldh, false, GpkLz(), false, true);
                 if (rc) break;
             }
             PIPE_HIP(hipStreamWaitEvent(G, ev_chain[j - 1], 0));
@@ -1619,7 +1603,7 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
                 }
                 PIPE_HIP(hipEventRecord(ev_ready2[j], G));
             } else {
-                rc = gpk_i_gemm(h, false, true, m, ob, pob, -1.0, Lb, ldh, Lb, ldh, 1.0, Hjj, ldh, false, 0, false, true);
+                rc = gpk_i_gemm(h, false, true, m, ob, pob, -1.0, Lb, ldh, Lb, ldh, 1.0, Hjj, ldh, false, GpkLz(), false, true);
                 if (rc) break;
             }
         }
@@ -1628,17 +1612,13 @@ static int potrf_pipelined(gpk_handle h, const double* W, int ldw, int rows, int
             rc = timed_product(G, j + pre, j + pre + 1);
             if (rc) break;
         }
-        h->stream = C;
-        h->no_sk = 1;                                                // (the tile-list workspace belongs to the GEMM stream while both run)
+        scope.use(C, false);                                         // (the tile-list workspace belongs to the GEMM stream while both run)
         PIPE_HIP(hipStreamWaitEvent(C, ev_ready[j], 0));
         rc = gpk_i_potrf_panel(h, Hjj, m, ob, ldh, pivot_base + j0, h->tune.left_looking_panels != 0,
                                (h->tune.pipeline_lookahead && j > 0) ? ev_ready2[j] : nullptr, (h->tune.pipeline_lookahead && j + 1 < J && ob > NB) ? ev_pre[j] : nullptr);
-        h->no_sk = 0;
         if (rc) break;
         PIPE_HIP(hipEventRecord(ev_chain[j], C));
     }
-    h->stream = main_s;
-    h->no_sk = 0;
     if (rc) {                                                        // drain both side streams before reporting
         (void)hipStreamSynchronize(G); (void)hipStreamSynchronize(C);
         return rc;
@@ -1744,7 +1724,7 @@ extern "C" int gpk_trsm(gpk_handle h, int trans, const double* L, int n, int ldl
 extern "C" int gpk_trsm_lz(gpk_handle h, const double* L, int n, int ldl, double* B, int nrhs, int ldb, int lead) {
     if (!h || !L || !B || n < 0 || nrhs < 0 || ldl < n || ldb < nrhs) return GPK_ERR_ARG;
     if (lead <= 0) return gpk_i_trsm_left_mt(h, false, L, n, ldl, B, nrhs, ldb);
-    return gpk_i_trsm_left_lz(h, L, n, ldl, B, nrhs, ldb, lead, 0);
+    return gpk_i_trsm_left_lz(h, L, n, ldl, B, nrhs, ldb, gpk_debug_lz(h, lead));
 }
 
 extern "C" int gpk_trtri_diag(gpk_handle h, const double* L, int n, int ldl, double* Dinv, int block) {
@@ -1757,7 +1737,7 @@ extern "C" int gpk_trsm_dinv(gpk_handle h, const double* L, const double* Dinv, 
     if (!h || !L || !Dinv || !B || !X || n < 0 || nrhs < 0 || ldl < n || ldb < nrhs || ldx < nrhs) return GPK_ERR_ARG;
     if (!dinv_block_ok(block)) return gpk_bad_arg(h, "trsm_dinv: block size must be 256, 512, 1024 or 2048");
     if (B == X) return gpk_bad_arg(h, "trsm_dinv: X must not alias B");
-    return gpk_i_trsm_left_dinv(h, L, Dinv, block, n, ldl, B, ldb, X, ldx, nrhs, lead > 0 ? lead : 0, 0);
+    return gpk_i_trsm_left_dinv(h, L, Dinv, block, n, ldl, B, ldb, X, ldx, nrhs, gpk_debug_lz(h, lead));
 }
 
 extern "C" int gpk_trsm_right_lt(gpk_handle h, const double* L, int n, int ldl, double* X, int m, int ldx) {

@@ -48,12 +48,12 @@ struct GemmArgs {
     const double* B; long ldb;
     double* C; long ldc;
     int lower_only;
-    int lead_div;      // ... or, with a staircase of slope 1/lead_div, for k < (lead-1-n) / lead_div (gpk_ctx::lead_div)
+    int lz_div;        // ... or, with a staircase of slope 1/lz_div, for k < (lead-1-n) / lz_div (GpkLz::div)
     int lead;          // operand B (stored [k][n]) has column n zero for k < lead-1-n: the tile with columns [n0, n0+BN)
                        // gets no contribution from k < lead - (n0 + BN), so its K loop starts there.  (SYRK S^T S,
                        // lower tiles: the A tile's columns are further right, i.e. non-zero even earlier.)
-    GpkStair stair;    // nseg > 0 (and lead > 0): the piecewise profile replaces the closed form -- the tile with columns [n0, n0+BN) starts at
-    int stair_col0, stair_row0;   // row gpk_stair_min(stair, stair_col0 + n0, stair_col0 + min(n0+BN, N)) - stair_row0 (Darcy system, gpk_gn.hip)
+    GpkStair lz_stair; // nseg > 0 (and lead > 0): the piecewise profile replaces the closed form -- the tile with columns [n0, n0+BN) starts at
+    int lz_col0, lz_row0;         // row gpk_stair_min(lz_stair, lz_col0 + n0, lz_col0 + min(n0+BN, N)) - lz_row0 (GpkLz::pw, col0, row0)
     int skip_upper;    // C is a block column whose top square is a diagonal block of a symmetric matrix: tiles entirely above
                        // that diagonal (m0 + BM <= n0) are not computed (their content is never read)
     int stagger;       // experiment, see the kernel
@@ -312,9 +312,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, ((BM / WM) * (BN / WN) 
         // zeros extra), so that the 32 tiles walk K in step and share operand slabs in L2
         const int nlast = g.nsuper > 0 ? min((tn / SG_W) * SG_W + SG_W - 1, g.ntn - 1) * BN : n0;
         const int z = g.lead - (nlast + BN);
-        kt0 = z > 0 ? (z / g.lead_div) / BK : 0;
-        if (g.stair.nseg > 0) {                                       // piecewise profile (wave-uniform: scalar ALU)
-            const int fr = gpk_stair_min(g.stair, g.stair_col0 + n0, g.stair_col0 + min(n0 + BN, g.N)) - g.stair_row0;
+        kt0 = z > 0 ? (z / g.lz_div) / BK : 0;
+        if (g.lz_stair.nseg > 0) {                                       // piecewise profile (wave-uniform: scalar ALU)
+            const int fr = gpk_stair_min(g.lz_stair, g.lz_col0 + n0, g.lz_col0 + min(n0 + BN, g.N)) - g.lz_row0;
             kt0 = fr > 0 ? fr / BK : 0;
         }
         if (kt0 > nk) kt0 = nk;
@@ -506,7 +506,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, ((BM / WM) * (BN / WN) 
             GemmArgs g;
 #define GPK_CP(f) g.f = gp->f;
             GPK_CP(M) GPK_CP(N) GPK_CP(K) GPK_CP(alpha) GPK_CP(beta) GPK_CP(A) GPK_CP(lda) GPK_CP(B) GPK_CP(ldb) GPK_CP(C) GPK_CP(ldc)
-            GPK_CP(lower_only) GPK_CP(lead_div) GPK_CP(lead) GPK_CP(skip_upper) GPK_CP(stagger) GPK_CP(rev_k) GPK_CP(tri_a) GPK_CP(vecA) GPK_CP(vecB)
+            GPK_CP(lower_only) GPK_CP(lz_div) GPK_CP(lead) GPK_CP(skip_upper) GPK_CP(stagger) GPK_CP(rev_k) GPK_CP(tri_a) GPK_CP(vecA) GPK_CP(vecB)
             GPK_CP(ntm) GPK_CP(ntn) GPK_CP(ntiles) GPK_CP(ntm_full) GPK_CP(band) GPK_CP(nsuper) GPK_CP(splitk) GPK_CP(ws) GPK_CP(cnt)
             GPK_CP(sk_segs) GPK_CP(sk_off) GPK_CP(row_order)
 #undef GPK_CP
@@ -622,9 +622,9 @@ void prof_count(gpk_handle h, const GemmArgs& g, int BM, int BN) {
         int k0 = 0;
         if (g.lead > 0) {
             const int z = g.lead - (n0 + BN);
-            k0 = z > 0 ? ((z / g.lead_div) / BK) * BK : 0;
-            if (g.stair.nseg > 0) {
-                const int fr = gpk_stair_min(g.stair, g.stair_col0 + n0, g.stair_col0 + std::min(n0 + BN, g.N)) - g.stair_row0;
+            k0 = z > 0 ? ((z / g.lz_div) / BK) * BK : 0;
+            if (g.lz_stair.nseg > 0) {
+                const int fr = gpk_stair_min(g.lz_stair, g.lz_col0 + n0, g.lz_col0 + std::min(n0 + BN, g.N)) - g.lz_row0;
                 k0 = fr > 0 ? (fr / BK) * BK : 0;
             }
         }
@@ -676,7 +676,7 @@ int launch_k64(gpk_handle h, bool ta, bool tb, GemmArgs& g) {
 // ---- tile-list ("stream-K") plans: built on the host per launch SHAPE, cached on the device ------------------------------------
 
 struct SkKey {
-    int bm, bn, M, N, K, lower, lead, lead_div, tri, skip_upper, band, G;
+    int bm, bn, M, N, K, lower, lead, lz_div, tri, skip_upper, band, G;
     bool operator==(const SkKey& o) const { return memcmp(this, &o, sizeof(SkKey)) == 0; }
 };
 struct SkPlan {
@@ -709,7 +709,7 @@ void sk_enumerate(const GemmArgs& g, std::vector<SkTile>& out) {
         int kt0 = 0;
         if (g.lead > 0) {
             const int z = g.lead - (n0 + BN);
-            kt0 = z > 0 ? (z / g.lead_div) / BK : 0;
+            kt0 = z > 0 ? (z / g.lz_div) / BK : 0;
             if (kt0 > nk) kt0 = nk;
         }                                                            // (launches with a piecewise profile never take tile lists: launch_cfg)
         out.push_back({tm, tn, kt0, nk});
@@ -861,7 +861,7 @@ SkPlan* sk_plan_for(gpk_handle h, const GemmArgs& g, int G) {
     SkCache* c = (SkCache*)h->sk_cache;
     SkKey key;
     memset(&key, 0, sizeof key);
-    key.bm = BM; key.bn = BN; key.M = g.M; key.N = g.N; key.K = g.K; key.lower = g.lower_only; key.lead = g.lead; key.lead_div = g.lead_div;
+    key.bm = BM; key.bn = BN; key.M = g.M; key.N = g.N; key.K = g.K; key.lower = g.lower_only; key.lead = g.lead; key.lz_div = g.lz_div;
     key.tri = g.tri_a; key.skip_upper = g.skip_upper; key.band = g.band; key.G = G;
     for (SkPlan* p : c->plans) if (p->key == key) { p->stamp = ++c->clock; return p->nblocks > 0 ? p : nullptr; }
     SkPlan* p = sk_build<BM, BN>(h, g, G, key);
@@ -876,7 +876,7 @@ SkPlan* sk_plan_for(gpk_handle h, const GemmArgs& g, int G) {
 }
 
 template <int BM, int BN, int WM, int WN>
-int launch_cfg(gpk_handle h, bool ta, bool tb, GemmArgs& g) {
+int launch_cfg(gpk_handle h, bool ta, bool tb, GemmArgs& g, int splitk_want) {
     g.ntm = gpk_ceil_div(g.M, BM);
     g.ntm_full = g.ntm;
     if (g.tri_a) g.ntm = (g.ntm + 1) / 2;                            // one workgroup per pair of row tiles (see the kernel)
@@ -885,7 +885,7 @@ int launch_cfg(gpk_handle h, bool ta, bool tb, GemmArgs& g) {
     g.nsuper = 0;
     prof_count(h, g, BM, BN);
     int nblocks = g.ntiles;
-    if (g.lower_only && g.lead > 0 && h->tune.supertile && g.lead_div == 1 && g.stair.nseg == 0) {
+    if (g.lower_only && g.lead > 0 && h->tune.supertile && g.lz_div == 1 && g.lz_stair.nseg == 0) {
         const int T = g.ntm, ncg = gpk_ceil_div(T, SG_W);
         for (int cg = 0; cg < ncg; ++cg) g.nsuper += gpk_ceil_div(T - cg * SG_W, SG_H);
         nblocks = 8 * gpk_ceil_div(g.nsuper, 8) * SG_H * SG_W;
@@ -907,7 +907,7 @@ int launch_cfg(gpk_handle h, bool ta, bool tb, GemmArgs& g) {
         }
     }
     g.splitk = 1; g.ws = nullptr; g.cnt = nullptr;
-    int want = h->splitk_req;
+    int want = splitk_want;                                           // (the caller's request: gpk_i_gemm)
     if (want <= 1 && h->tune.force_splitk > 1 && gpk_i_splitk_reserve(h) == 0) want = h->tune.force_splitk;
     if (want > 1 && !g.lower_only && !g.tri_a && h->d_splitk_ws && h->d_splitk_cnt) {
         int s = want > 16 ? 16 : want;
@@ -924,7 +924,7 @@ int launch_cfg(gpk_handle h, bool ta, bool tb, GemmArgs& g) {
     // Tile-list launch?  Resident workgroup slots of this configuration (waves per workgroup -> workgroups per CU: 4 waves 4 (5 for the
     // 32-row tile), 8 waves 2, 16 waves 1); worth it when the launch is only a few rounds of them -- then the last, partly filled
     // round and the spread of tile lengths (leading zeros, triangular operand) cost a large share of its time.
-    if (h->tune.sk && g.splitk == 1 && g.nsuper == 0 && !h->no_sk && !g.rev_k && g.K >= 4 * BK && h->num_cu >= 8 && g.stair.nseg == 0) {
+    if (h->tune.sk && g.splitk == 1 && g.nsuper == 0 && h->ws_owner && !g.rev_k && g.K >= 4 * BK && h->num_cu >= 8 && g.lz_stair.nseg == 0) {
         constexpr int WAVES = (BM / WM) * (BN / WN);
         const int per_cu = WAVES >= 16 ? 1 : WAVES >= 8 ? 2 : (BM == 32 ? 5 : 4);
         const int G = ((h->num_cu * per_cu) / 8) * 8;
@@ -988,7 +988,8 @@ void gpk_i_sk_free(gpk_handle h) {
 }
 
 int gpk_i_gemm(gpk_handle h, bool ta, bool tb, int m, int n, int k, double alpha, const double* A, int lda,
-               const double* B, int ldb, double beta, double* C, int ldc, bool lower_only, int lead, bool tri_a, bool skip_upper) {
+               const double* B, int ldb, double beta, double* C, int ldc, bool lower_only, const GpkLz& lz, bool tri_a, bool skip_upper,
+               int splitk, int tile) {
     if (m <= 0 || n <= 0) return 0;
     if (k < 0 || !A || !B || !C) return gpk_bad_arg(h, "gemm: sizes/pointers");
     if (lower_only && m != n) return gpk_bad_arg(h, "gemm: lower_only needs a square C");
@@ -996,10 +997,11 @@ int gpk_i_gemm(gpk_handle h, bool ta, bool tb, int m, int n, int k, double alpha
     g.M = m; g.N = n; g.K = k; g.alpha = alpha; g.beta = beta;
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.lower_only = lower_only ? 1 : 0;
-    g.lead = (lead > 0 && !tb && (!lower_only || (ta && A == B))) ? lead : 0;
-    g.lead_div = h->lead_div > 0 ? h->lead_div : 1;
-    g.stair = GpkStair(); g.stair_col0 = g.stair_row0 = 0;
-    if (g.lead > 0 && h->stair.nseg > 0) { g.stair = h->stair; g.stair_col0 = h->stair_col0; g.stair_row0 = h->stair_row0; }
+    // (a piecewise profile replaces the closed form in the kernel: `lead` then only says that there is one)
+    g.lead = (!lz.is_dense() && !tb && (!lower_only || (ta && A == B))) ? (lz.is_piecewise() ? 1 : lz.lead) : 0;
+    g.lz_div = lz.div > 0 ? lz.div : 1;
+    g.lz_stair = GpkStair(); g.lz_col0 = g.lz_row0 = 0;
+    if (g.lead > 0 && lz.is_piecewise()) { g.lz_stair = lz.pw; g.lz_col0 = lz.col0; g.lz_row0 = lz.row0; }
     g.tri_a = (tri_a && !ta && !tb && !lower_only) ? 1 : 0;
     g.skip_upper = (skip_upper && !lower_only) ? 1 : 0;
     g.stagger = h->tune.stagger;
@@ -1016,26 +1018,26 @@ int gpk_i_gemm(gpk_handle h, bool ta, bool tb, int m, int n, int k, double alpha
     // operand layout (tools/gemm_big_probe.py: 62.0 vs 58.8 TF/s NN 10500^3-ish, 58.6 vs 49.8 NT K=512).  The large
     // tiles stay reachable through gpk_debug_set(0, 1) as the reference point for a register-leaner rewrite.
     const bool big = (h->tune.force_cfg == 1) && !g.tri_a;
-    if (big) return launch_cfg<128, 128, 64, 64>(h, ta, tb, g);
+    if (big) return launch_cfg<128, 128, 64, 64>(h, ta, tb, g, splitk);
     // (lower-triangular output with leading zeros = the product S^T S: from ~8000 lower 64 x 64 tiles on -- n_z ~ 8000 -- the 128 x 128 tile's
     // halved operand traffic wins: north-star size 23.9 -> 22.2 ms; at config 2, 2016 tiles, it loses: 1.59 -> 2.07 ms)
     const bool big_lower = lower_only && g.lead > 0 && h->tune.force_cfg == 0 && h->tune.big_lower_min > 0 && (long)gpk_ceil_div(m, 64) * (gpk_ceil_div(m, 64) + 1) / 2 >= h->tune.big_lower_min;
     if ((h->tune.force_cfg == 4 || big_lower || (h->tune.force_cfg == 0 && h->tune.big_min > 0 && k > 64 && (long)gpk_ceil_div(m, 64) * gpk_ceil_div(n, 64) >= h->tune.big_min)) && !g.tri_a && (!lower_only || h->tune.force_cfg == 4 || big_lower))
-        return launch_cfg<128, 128, 32, 32>(h, ta, tb, g);           // 16 waves, one workgroup per CU
+        return launch_cfg<128, 128, 32, 32>(h, ta, tb, g, splitk);           // 16 waves, one workgroup per CU
     if ((h->tune.force_cfg == 3 || (h->tune.force_cfg == 0 && h->tune.tall_min > 0 && (long)gpk_ceil_div(m, 64) * gpk_ceil_div(n, 64) >= h->tune.tall_min)) && !g.tri_a && !lower_only)
-        return launch_cfg<128, 64, 32, 32>(h, ta, tb, g);            // 8 waves, 2 workgroups per CU
+        return launch_cfg<128, 64, 32, 32>(h, ta, tb, g, splitk);            // 8 waves, 2 workgroups per CU
     // short-and-wide updates of the triangular-solve recursion (M = 256 or 512 against ~4000 columns): 64x64 tiles give
     // only 1-2 workgroups per CU, i.e. one wave per SIMD and nothing to hide latency behind; 32x64 tiles double that
     long t64 = (long)gpk_ceil_div(m, 64) * gpk_ceil_div(n, 64);
     if (g.tri_a) t64 /= 2;                                            // workgroups handle pairs of row tiles
     // (also for long K: restricting this to K <= 1024 was measured slower on the 512-column products of the pipelined SYRK and on
     // the mid-size updates of the triangular solve -- 504 tiles of 64x64 leave the CUs at 2-3 workgroups)
-    if (h->tune.force_cfg == 0 && h->tile_req == 128 && !lower_only && !g.tri_a) return launch_cfg<128, 64, 32, 32>(h, ta, tb, g);
-    if (h->tune.force_cfg == 0 && !lower_only && t64 < 2 * h->num_cu && m >= 64 && h->tile_req != 64) return launch_cfg<32, 64, 16, 32>(h, ta, tb, g);
+    if (h->tune.force_cfg == 0 && tile == 128 && !lower_only && !g.tri_a) return launch_cfg<128, 64, 32, 32>(h, ta, tb, g, splitk);
+    if (h->tune.force_cfg == 0 && !lower_only && t64 < 2 * h->num_cu && m >= 64 && tile != 64) return launch_cfg<32, 64, 16, 32>(h, ta, tb, g, splitk);
     // (A "round model" -- co-resident workgroups start and finish together, a partly filled last round costs at least half a round, so
     // e.g. 1260 tiles of 64 rows should lose against 2457 tiles of 32 rows -- was tried as the selector and is wrong for this kernel:
     // 383 -> 420 us for that launch, 1384 -> 1477 us for the 3276-tile one; only launches below 0.6 rounds gained, 121 -> 105 us.)
-    return launch_cfg<64, 64, 32, 32>(h, ta, tb, g);
+    return launch_cfg<64, 64, 32, 32>(h, ta, tb, g, splitk);
 }
 
 extern "C" int gpk_gemm(gpk_handle h, int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda,
@@ -1047,7 +1049,7 @@ extern "C" int gpk_gemm(gpk_handle h, int ta, int tb, int m, int n, int k, doubl
 extern "C" int gpk_gemm_lz(gpk_handle h, int ta, int m, int n, int k, double alpha, const double* A, int lda,
                            const double* B, int ldb, double beta, double* C, int ldc, int lead) {
     if (!h) return GPK_ERR_ARG;
-    return gpk_i_gemm(h, ta != 0, false, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, false, lead > 0 ? lead : 0);
+    return gpk_i_gemm(h, ta != 0, false, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, false, gpk_debug_lz(h, lead));
 }
 
 extern "C" int gpk_symmetrize_lower(gpk_handle h, double* A, int n, int lda) {

@@ -54,7 +54,7 @@ struct BuildArgs {
                        // row pos(j).  1: pos(j) = j (elliptic systems).  2: Eikonal, unknown groups [v0 | v1 | v2] taken in the
                        // order v1, v2, v0: their first non-zeros sit in rows t, N_d + t, 3 N_d + t >= pos.  3: Burgers, the three
                        // unknowns of point t (columns t, N_d + t, 2 N_d + t all start in row t) interleaved: pos(j) = 3t + group,
-                       // a staircase of slope 1/3 (column zero above row pos/3; gpk_ctx::lead_div = 3).  4: Darcy (round 4), unknown groups
+                       // a staircase of slope 1/3 (column zero above row pos/3; GpkLz::div = 3).  4: Darcy (round 4), unknown groups
                        // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below
     int nz;
     int family;        // elliptic system, gpk_gn_structured_prepare: 1 = only the unit entries of the first row group ([I; 0; 0], no F),
@@ -299,12 +299,16 @@ int exact_loss_chain(gpk_handle h, const Dims& d, bool after_main, bool* on_side
     *on_side = true;
     if (after_main) GPK_HIP(h, hipEventRecord(h->ev_loss[0], main_s));
     GPK_HIP(h, hipStreamWaitEvent(side, h->ev_loss[0], 0));
-    h->stream = side; h->trsv_alt = 1;
     int rc = 0;
-    for (int k = 0; k < d.ngroups && rc == 0; ++k)
-        if (d.g[k].L) rc = gpk_i_trsv(h, false, d.g[k].L, d.g[k].n, d.g[k].ldl, h->d_loss_work + d.g[k].off);
-    if (rc == 0) rc = gpk_i_dot(h, h->d_loss_work, h->d_loss_work, d.rows, h->d_scalars + 8);
-    h->stream = main_s; h->trsv_alt = 0;
+    {
+        GpkStreamScope scope(h);                                     // (single-vector solves and a dot product: no use for the GEMM workspace)
+        scope.use(side, false);
+        h->trsv_alt = 1;
+        for (int k = 0; k < d.ngroups && rc == 0; ++k)
+            if (d.g[k].L) rc = gpk_i_trsv(h, false, d.g[k].L, d.g[k].n, d.g[k].ldl, h->d_loss_work + d.g[k].off);
+        if (rc == 0) rc = gpk_i_dot(h, h->d_loss_work, h->d_loss_work, d.rows, h->d_scalars + 8);
+        h->trsv_alt = 0;
+    }
     if (rc) { (void)hipStreamSynchronize(side); return rc; }
     GPK_HIP(h, hipEventRecord(h->ev_loss[1], side));
     return 0;
@@ -318,15 +322,14 @@ int step_layout(gpk_handle h, const gpk_gn_problem* p) {
          : (p->system == GPK_GN_EIKONAL && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
 }
 
-// The handle state that goes with it for the duration of one call: the Eikonal profile (GEMM-only solve path: the exact two-segment
-// profile for the solve and the products; the substitution path keeps the conservative closed form, which gpk_i_trsm_left_lz understands),
-// the staircase slope of the Burgers system; everything reset on the way out, whichever way that is.
-struct LayoutScope {
-    gpk_handle h;
-    LayoutScope(gpk_handle hh, const gpk_gn_problem* p, int rev) : h(hh) { gpk_i_gn_layout_enter(h, p, rev); }
-    ~LayoutScope() { gpk_i_gn_layout_leave(h); }
-    LayoutScope(const LayoutScope&) = delete;
-};
+// The leading-zero profile of [A(z) | F] under that layout, a pure function of the problem and the handle's switches: the closed form
+// with lead = n_z (slope 1/3 for Burgers); for Eikonal on the GEMM-only solve path the exact two-segment profile for the solve and the
+// products (the substitution path keeps the conservative closed form).  Dense for the layouts 0 and 4: Darcy's two factors have a
+// profile each (darcy_u_profile; the a-part's closed form on its own columns), passed where they are used.
+GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
+    if (rev == 2 && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
+    return (rev >= 1 && rev <= 3) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
+}
 
 // every factored row group comes with its inverted diagonal blocks (the GEMM-only solve path is available)
 bool all_dinv(gpk_handle h, const gpk_gn_problem* p, const Dims& d) {
@@ -346,6 +349,7 @@ int assemble_normal_equations(gpk_handle h, const gpk_gn_problem* p, const Dims&
                               double* Hb, int ldh, double alpha, int rev, double** Wout = nullptr, int family = 0) {
     const int nc = d.nz + 1;
     if (lds < nc || ldh < nc) return gpk_bad_arg(h, "gn: lds/ldh < nz+1");
+    const GpkLz lz = step_profile(h, p, d.nz, rev);
     bool dinv = h->tune.use_dinv != 0;
     const int db = p->dinv_block > 0 ? p->dinv_block : 256;
     if (db != 256 && db != 512 && db != 1024 && db != 2048) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
@@ -389,18 +393,15 @@ int assemble_normal_equations(gpk_handle h, const gpk_gn_problem* p, const Dims&
                 // The 3 N_d columns do not depend on z (a permutation matrix against a fixed factor): with the result of
                 // gpk_gn_darcy_prepare at hand (p->Wa) that solve is not repeated -- the product below reads p->Wa / p->Ha instead
                 if (!(p->Wa && p->Ha))
-                    GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg + Nd, lds, Wg + Nd, lds, 3 * Nd, 3 * Nd, 0));
-                GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg + d.nz, lds, Wg + d.nz, lds, 1, 0, 0));
-            } else {
-                h->stair = darcy_u_profile(Nd);                      // u-part: three segments (reset by the caller's guard)
-                const int rc = gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg, lds, Wg, lds, nc, 1, 0);
-                h->stair = GpkStair(); h->stair_col0 = h->stair_row0 = 0;
-                GPK_TRY(rc);
+                    GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg + Nd, lds, Wg + Nd, lds, 3 * Nd, GpkLz::closed(3 * Nd)));
+                GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg + d.nz, lds, Wg + d.nz, lds, 1, GpkLz()));
+            } else {                                                 // u-part: three segments
+                GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg, lds, Wg, lds, nc, GpkLz::piecewise(darcy_u_profile(Nd))));
             }
         } else if (dinv) {
-            GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg, lds, W + (long)g.off * lds, lds, nc, rev ? d.nz : 0, 0));
+            GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Sg, lds, W + (long)g.off * lds, lds, nc, lz));
         } else if (rev) {
-            GPK_TRY(gpk_i_trsm_left_lz(h, g.L, g.n, g.ldl, Sg, nc, lds, d.nz, 0));
+            GPK_TRY(gpk_i_trsm_left_lz(h, g.L, g.n, g.ldl, Sg, nc, lds, lz));
         } else {
             GPK_TRY(gpk_i_trsm_left_mt(h, false, g.L, g.n, g.ldl, Sg, nc, lds));
         }
@@ -408,7 +409,7 @@ int assemble_normal_equations(gpk_handle h, const gpk_gn_problem* p, const Dims&
     GPK_PROF_MARK(h, 1);
     sig_guard.armed = false;                                         // the solve was issued completely
     if (Wout) { *Wout = W; return 0; }                               // gn_step: product and factorisation are pipelined by the caller
-    GPK_TRY(gpk_i_gemm(h, true, false, nc, nc, d.rows, alpha, W, lds, W, lds, 0.0, Hb, ldh, true, rev ? d.nz : 0));
+    GPK_TRY(gpk_i_gemm(h, true, false, nc, nc, d.rows, alpha, W, lds, W, lds, 0.0, Hb, ldh, true, lz));
     GPK_PROF_MARK(h, 2);
     return 0;
 }
@@ -604,7 +605,6 @@ extern "C" int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* p, 
     if (!elliptic && (rev < 2 || !all_dinv(h, p, d)))
         return gpk_bad_arg(h, "structured solve: this system needs the inverted diagonal blocks of every factor (Dinv, dinv_block) and the leading-zero layout");
     if (!elliptic && (ldw & 1)) return gpk_bad_arg(h, "structured solve: ldw must be even");
-    LayoutScope scope(h, p, elliptic ? 1 : rev);
     gpk_gn_problem q = *p;                                           // (the Darcy a-part is solved here like everything else: no cache)
     q.Wa = nullptr; q.Ha = nullptr;
     double* zero = nullptr;
@@ -672,8 +672,8 @@ extern "C" int gpk_gn_darcy_prepare(gpk_handle h, const gpk_gn_problem* p, doubl
     // exactly the step's launches for this block (assemble_normal_equations, rev = 4, k = 0; the product of gpk_gn_step): same
     // kernels, same shapes, same tile configurations -- only the destinations differ, hence bit-identical results
     if (rc == 0) rc = build(h, p, zero, S, lds, d.nz, 1, 4, 0);
-    if (rc == 0) rc = gpk_i_trsm_left_dinv(h, ga.L, ga.Dinv, db, ga.n, ga.ldl, S + (long)ga.off * lds + Nd, lds, Wa, ldwa, na, na, 0);
-    if (rc == 0) rc = gpk_i_gemm(h, true, false, na, na, ga.n, 1.0, Wa, ldwa, Wa, ldwa, 0.0, Ha, ldha, true, na);
+    if (rc == 0) rc = gpk_i_trsm_left_dinv(h, ga.L, ga.Dinv, db, ga.n, ga.ldl, S + (long)ga.off * lds + Nd, lds, Wa, ldwa, na, GpkLz::closed(na));
+    if (rc == 0) rc = gpk_i_gemm(h, true, false, na, na, ga.n, 1.0, Wa, ldwa, Wa, ldwa, 0.0, Ha, ldha, true, GpkLz::closed(na));
     (void)hipStreamSynchronize(h->stream);
     (void)hipFree(zero);
     return rc;
@@ -723,7 +723,6 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
     if (p->system == GPK_GN_DARCY && p->Wa && p->Ha && (p->ldwa < 3 * p->Nd || p->ldha < 3 * p->Nd))
         return gpk_bad_arg(h, "gn: ldwa/ldha < 3 Nd (gpk_gn_darcy_prepare)");
     const int rev = step_layout(h, p);
-    LayoutScope layout_scope(h, p, rev);
     double* W = nullptr;                                             // the solved block [L^{-1}A | L^{-1}F] (S or the workspace)
     const bool gram = h->tune.structured && p->system == GPK_GN_ELLIPTIC && p->G && p->pvec && p->ldg >= nz;
     // the same level for the Burgers / Eikonal / Darcy systems (round 6): H/2 = D G11 D + D G12 + G21 D + G22 from the Gram blocks of
@@ -784,7 +783,7 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         for (int k = 0; k < d.ngroups; ++k) {
             const Group& g = d.g[k];
             if (g.n <= 0) continue;
-            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, wv + g.off, 1, 1, 0, 0));
+            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, wv + g.off, 1, 1, GpkLz()));
             else GPK_HIP(h, hipMemcpy2DAsync(wv + g.off, 8, S + (long)g.off * lds + nz, (size_t)lds * 8, 8, g.n, hipMemcpyDeviceToDevice, h->stream));
         }
         GPK_PROF_MARK(h, 1);
@@ -817,7 +816,7 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         for (int k = 0; k < d.ngroups; ++k) {
             const Group& g = d.g[k];
             if (g.n <= 0) continue;
-            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, W + (long)g.off * lds + nz, lds, 1, 0, 0));
+            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, W + (long)g.off * lds + nz, lds, 1, GpkLz()));
             else GPK_HIP(h, hipMemcpy2DAsync(W + (long)g.off * lds + nz, (size_t)lds * 8, S + (long)g.off * lds + nz, (size_t)lds * 8, 8, g.n,
                                              hipMemcpyDeviceToDevice, h->stream));
         }
@@ -850,25 +849,24 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
             while (h->pipe_tev.size() < 2) { hipEvent_t e; GPK_HIP(h, hipEventCreate(&e)); h->pipe_tev.push_back(e); }
             GPK_HIP(h, hipEventRecord(h->pipe_tev[0], h->stream));
         }
-        h->stair = darcy_u_profile(Nd); h->stair_col0 = 0; h->stair_row0 = 0;
-        int rc = gpk_i_gemm(h, true, false, nc, nc, d.rows - gu.off, 1.0, Wu, lds, Wu, lds, 0.0, Hb, ldh, true, 1);
-        h->stair = GpkStair();
+        const GpkLz lz_a = GpkLz::closed(3 * Nd);                    // (the a-part's own columns [N_d, 4 N_d))
+        int rc = gpk_i_gemm(h, true, false, nc, nc, d.rows - gu.off, 1.0, Wu, lds, Wu, lds, 0.0, Hb, ldh, true, GpkLz::piecewise(darcy_u_profile(Nd)));
         const bool cached_a = p->Wa && p->Ha;                       // (checked: ldwa, ldha >= 3 N_d)
         if (rc == 0 && cached_a) {
             add_lower_kernel<<<3 * Nd, 256, 0, h->stream>>>(3 * Nd, p->Ha, p->ldha, Hb + (long)Nd * ldh + Nd, ldh);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) rc = gpk_fail(h, e, "add_lower_kernel", __FILE__, __LINE__);
         } else if (rc == 0)
-            rc = gpk_i_gemm(h, true, false, 3 * Nd, 3 * Nd, ga.n, 1.0, Wa + Nd, lds, Wa + Nd, lds, 1.0, Hb + (long)Nd * ldh + Nd, ldh, true, 3 * Nd);
+            rc = gpk_i_gemm(h, true, false, 3 * Nd, 3 * Nd, ga.n, 1.0, Wa + Nd, lds, Wa + Nd, lds, 1.0, Hb + (long)Nd * ldh + Nd, ldh, true, lz_a);
         if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 3 * Nd, ga.n, 1.0, Wa + nz, lds, cached_a ? p->Wa : Wa + Nd, cached_a ? p->ldwa : lds, 1.0,
-                                     Hb + (long)nz * ldh + Nd, ldh, false, 3 * Nd);
+                                     Hb + (long)nz * ldh + Nd, ldh, false, lz_a);
         if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 1, ga.n, 1.0, Wa + nz, lds, Wa + nz, lds, 1.0, Hb + (long)nz * ldh + nz, ldh, false);
         h->prof_phase = ph;
         GPK_TRY(rc);
         if (h->prof) { GPK_HIP(h, hipEventRecord(h->pipe_tev[1], h->stream)); h->pipe_tev_used = 2; }
         GPK_HIP(h, hipMemcpyAsync(d_loss, Hb + (long)nz * ldh + nz, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         GPK_TRY(gpk_i_potrf(h, Hb, nc, ldh, 0));
-    } else if (!gram && !gram_general) GPK_TRY(gpk_i_syrk_potrf(h, W, lds, d.rows, nz + 1, rev ? nz : 0, Hb, ldh, d_loss));
+    } else if (!gram && !gram_general) GPK_TRY(gpk_i_syrk_potrf(h, W, lds, d.rows, nz + 1, step_profile(h, p, nz, rev), Hb, ldh, d_loss));
     GPK_PROF_MARK(h, 2);
     GPK_PROF_MARK(h, 3);
     // the chain of the exact loss: on the GEMM partition's stream from here on (pipelined phase: that stream's last product finished before the
@@ -993,20 +991,13 @@ int gpk_i_gn_exact_loss(gpk_handle h, const gpk_gn_problem* p, const double* z, 
 }
 
 int gpk_i_gn_layout(gpk_handle h, const gpk_gn_problem* p) { return step_layout(h, p); }
-void gpk_i_gn_layout_enter(gpk_handle h, const gpk_gn_problem* p, int rev) {
-    if (rev == 2 && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) h->stair = eikonal_profile(p->Nd);
-    h->lead_div = rev == 3 ? 3 : 1;
-}
-void gpk_i_gn_layout_leave(gpk_handle h) { h->stair = GpkStair(); h->stair_col0 = h->stair_row0 = 0; h->stair_base = 0; h->lead_div = 1; }
-int gpk_i_gn_first_row(gpk_handle h, int nz, int c) {
-    if (c >= nz) return 0;                                           // the F column is dense
-    if (h->stair.nseg > 0) return gpk_stair_min(h->stair, c, c + 1);
-    const int sd = h->lead_div > 0 ? h->lead_div : 1;
-    return (nz - 1 - c) / sd;
+GpkLz gpk_i_gn_profile(gpk_handle h, const gpk_gn_problem* p, int rev) {
+    Dims d;
+    return gn_dims(p, d) == 0 ? step_profile(h, p, d.nz, rev) : GpkLz();
 }
 
-// Darcy pieces of the sharded step (gpk_mg.hip): the u-part's three-segment profile into the handle (gpk_i_gn_layout_leave resets it) ...
-void gpk_i_gn_darcy_profile(gpk_handle h, int Nd) { h->stair = darcy_u_profile(Nd); h->stair_col0 = h->stair_row0 = 0; }
+// Darcy pieces of the sharded step (gpk_mg.hip): the u-part's three-segment profile ...
+GpkLz gpk_i_gn_darcy_u_profile(int Nd) { return GpkLz::piecewise(darcy_u_profile(Nd)); }
 
 // ... and the cached a-part added to the rows [r0, r1) of Hb a rank has just computed from the u-part and data rows: H_a on the rows that lie
 // in [N_d, 4 N_d) and, if row n_z is among them, the border terms (L_a^{-1}F_a)^T W_a and |L_a^{-1}F_a|^2 (aF: the solved a-part F column,
@@ -1026,12 +1017,9 @@ int gpk_i_gn_darcy_add_a(gpk_handle h, const gpk_gn_problem* p, double* Hb, int 
         GPK_LAUNCH_CHECK(h);
     }
     if (r0 <= nz && nz < r1) {
-        const GpkStair keep = h->stair;                              // (closed-form staircase of the a-part's own columns, as on one GPU)
-        h->stair = GpkStair(); h->stair_col0 = h->stair_row0 = 0;
-        int rc = gpk_i_gemm(h, true, false, 1, na, na, 1.0, aF, ldaf, p->Wa, p->ldwa, 1.0, Hb + (long)nz * ldh + Nd, ldh, false, na);
-        if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 1, na, 1.0, aF, ldaf, aF, ldaf, 1.0, Hb + (long)nz * ldh + nz, ldh, false);
-        h->stair = keep;
-        GPK_TRY(rc);
+        // (closed-form staircase of the a-part's own columns, as on one GPU)
+        GPK_TRY(gpk_i_gemm(h, true, false, 1, na, na, 1.0, aF, ldaf, p->Wa, p->ldwa, 1.0, Hb + (long)nz * ldh + Nd, ldh, false, GpkLz::closed(na)));
+        GPK_TRY(gpk_i_gemm(h, true, false, 1, 1, na, 1.0, aF, ldaf, aF, ldaf, 1.0, Hb + (long)nz * ldh + nz, ldh, false));
     }
     return 0;
 }

@@ -274,10 +274,10 @@ int exec_potrf(gpk_mg_handle mg, double* A, int n, int lda) {
         GPK_HIP(h, hipStreamWaitEvent(mg->s_comm, mg->ev_begin, 0));
     }
     int rc = 0;
+    GpkStreamScope scope(h);
     for (const Op& op : plan) {
         const hipStream_t s = streams[op.stream];
-        h->stream = s;
-        h->no_sk = (la && op.stream != 0) ? 1 : 0;                   // tile-list GEMM launches (one workspace per handle) only on the main stream
+        scope.use(s, !(la && op.stream != 0));                       // tile-list GEMM launches (one workspace per handle) only on the main stream
         const int k = (op.kind == GPK_MG_UPDATE) ? op.b : op.a;
         const int k0 = k * nb, kb = std::min(nb, n - k0);
         hipError_t e = hipSuccess;
@@ -301,7 +301,7 @@ int exec_potrf(gpk_mg_handle mg, double* A, int n, int lda) {
         case GPK_MG_UPDATE: {
             const int j0 = op.a * nb, jb = std::min(nb, n - j0);
             const double* Lj = A + (long)j0 * lda + k0;              // rows j0.. of panel k
-            rc = gpk_i_gemm(h, false, true, n - j0, jb, kb, -1.0, Lj, lda, Lj, lda, 1.0, A + (long)j0 * lda + j0, lda, false, 0, false, true);
+            rc = gpk_i_gemm(h, false, true, n - j0, jb, kb, -1.0, Lj, lda, Lj, lda, 1.0, A + (long)j0 * lda + j0, lda, false, GpkLz(), false, true);
             break;
         }
         case GPK_MG_RECORD: e = hipEventRecord(mg->ev[op.a], s); break;
@@ -311,8 +311,6 @@ int exec_potrf(gpk_mg_handle mg, double* A, int n, int lda) {
         if (e != hipSuccess) rc = gpk_fail(h, e, "gpk_mg plan operation", __FILE__, __LINE__);
         if (rc) break;
     }
-    h->stream = main_s;
-    h->no_sk = 0;
     if (rc && la) { (void)hipStreamSynchronize(mg->s_panel); (void)hipStreamSynchronize(mg->s_comm); }
     return rc;
 }
@@ -669,10 +667,8 @@ extern "C" int gpk_mg_gn_step(gpk_mg_handle mg, const gpk_gn_problem* p, double*
         return gpk_bad_arg(h, "gpk_mg_gn_step: elliptic, Eikonal, Burgers and Darcy systems only (leading-zero layout)");
     if (!p->Dinv || !S2) return gpk_bad_arg(h, "gpk_mg_gn_step: needs the inverted diagonal blocks (Dinv) and S2");
     if (darcy && (!p->Wa || !p->Ha || !p->Dinv2)) return gpk_bad_arg(h, "gpk_mg_gn_step: the Darcy system needs its cached a-part (gpk_gn_darcy_prepare) and Dinv2");
-    struct LayoutGuard {                                             // Eikonal: its profile in the handle; Burgers: the slope; reset on every way out
-        gpk_handle h; LayoutGuard(gpk_handle hh, const gpk_gn_problem* pp, int r) : h(hh) { gpk_i_gn_layout_enter(h, pp, r); }
-        ~LayoutGuard() { gpk_i_gn_layout_leave(h); }
-    } layout_guard(h, p, rev);
+    // the profile of the sharded columns, in the frame of [A | F]: the step's own, or the three segments of the Darcy u-part
+    const GpkLz lz = darcy ? gpk_i_gn_darcy_u_profile(p->Nd) : gpk_i_gn_profile(h, p, rev);
     if (!mg->allgather) return gpk_bad_arg(h, "gpk_mg: world > 1 needs a communicator (gpk_mg_rccl_init / gpk_mg_set_comm)");
     int nz = 0, rows = 0;
     GPK_TRY(gpk_i_gn_dims(h, p, &nz, &rows));
@@ -691,29 +687,20 @@ extern "C" int gpk_mg_gn_step(gpk_mg_handle mg, const gpk_gn_problem* p, double*
     const int xoff = na, xrows = nu, prows = rows - na;
     double* const Sx = S + (long)xoff * lds;
     double* const S2x = S2 + (long)xoff * lds;
-    if (darcy) gpk_i_gn_darcy_profile(h, p->Nd);                      // the u-part's three-segment profile into the handle (reset by the guard)
     if (rev == 1) column_bounds(nc, nz, rows, P, mg->col_align, mg->bounds);
-    else column_bounds_by(nc, xrows, P, mg->col_align, [&](int c) { return gpk_i_gn_first_row(h, nz, c); }, mg->bounds);
+    else column_bounds_by(nc, xrows, P, mg->col_align, [&](int c) { return lz.first_row(c); }, mg->bounds);
     const std::vector<int>& b = mg->bounds;
     const int c0 = b[rank], c1 = b[rank + 1];
     int per = 0;
     for (int r = 0; r < P; ++r) per = std::max(per, b[r + 1] - b[r]);
-    if (c1 > c0) {
-        h->stair_base = c0;                                          // (piecewise profile: my shard's column 0 in the profile's frame)
-        const int rc = gpk_i_trsm_left_dinv(h, p->L, p->Dinv, db, xrows, p->ldl, Sx + c0, lds, S2x + c0, lds, c1 - c0, darcy ? 1 : std::max(nz - c0, 0), 0);
-        h->stair_base = 0; h->stair_col0 = h->stair_row0 = 0;        // (the products below read S2 from its column 0, row 0)
-        GPK_TRY(rc);
-    }
+    if (c1 > c0)                                                     // (my shard's column 0 is column c0 of the profile's frame)
+        GPK_TRY(gpk_i_trsm_left_dinv(h, p->L, p->Dinv, db, xrows, p->ldl, Sx + c0, lds, S2x + c0, lds, c1 - c0, lz.sub(c0, 0)));
     if (darcy) {
         // replicated on every rank (tiny): the data rows (identity factor: all columns) and the a-part's F column L_a^{-1}[w1; w2; w0]
         if (p->Ndata > 0)
             GPK_HIP(h, hipMemcpy2DAsync(S2x + (long)nu * lds, (size_t)lds * 8, Sx + (long)nu * lds, (size_t)lds * 8, (size_t)nc * 8, (size_t)p->Ndata,
                                         hipMemcpyDeviceToDevice, h->stream));
-        GpkStair keep = h->stair;                                    // (a dense one-column solve: no profile)
-        h->stair = GpkStair();
-        const int rc = gpk_i_trsm_left_dinv(h, p->L2, p->Dinv2, db, na, p->ldl2, S + nz, lds, S2 + nz, lds, 1, 0, 0);
-        h->stair = keep; h->stair_col0 = h->stair_row0 = 0;
-        GPK_TRY(rc);
+        GPK_TRY(gpk_i_trsm_left_dinv(h, p->L2, p->Dinv2, db, na, p->ldl2, S + nz, lds, S2 + nz, lds, 1, GpkLz()));   // (a dense one-column solve)
     }
     // ---- exchange of the column shards of S2, then my block rows (cyclic) of the lower triangle of Hb = S2^T S2 (structural zeros
     //      skipped).  Two forms of the exchange (gpk_mg_set_option key 3; bench.py times both on the fabric and keeps the faster):
@@ -737,8 +724,7 @@ extern "C" int gpk_mg_gn_step(gpk_mg_handle mg, const gpk_gn_problem* p, double*
                                     hipMemcpyDeviceToDevice, s));
     auto block_row = [&](int i) {
         const int i0 = i * nb, ib = std::min(nb, nc - i0);
-        h->stair_col0 = h->stair_row0 = 0;
-        int rc = gpk_i_gemm(h, true, false, ib, i0 + ib, prows, 1.0, S2x + i0, lds, S2x, lds, 0.0, Hb + (long)i0 * ldh, ldh, false, darcy ? 1 : nz);
+        int rc = gpk_i_gemm(h, true, false, ib, i0 + ib, prows, 1.0, S2x + i0, lds, S2x, lds, 0.0, Hb + (long)i0 * ldh, ldh, false, lz);
         // Darcy: + the cached a-part -- H_a on the rows of this block that lie in [N_d, 4 N_d), and in the block that holds the border row its
         // a-part terms (L_a^{-1}F_a)^T W_a and |L_a^{-1}F_a|^2, exactly the launches of the one-GPU step
         if (rc == 0 && darcy) rc = gpk_i_gn_darcy_add_a(h, p, Hb, ldh, i0, i0 + ib, S2 + nz, lds);
