@@ -38,6 +38,11 @@ enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1 };
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
 enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4 };
+/* Reaction term tau(u) of the elliptic systems, -psi[u] + tau(u) = f ("Reaction terms"); parameters p0, p1, p2:
+ *   POWER  p0 pow(u, p1)              (alpha u^m: the reference's equation, and what a zeroed gpk_gn_problem means)
+ *   EXP    p0 exp(p1 u)               SINH   p0 sinh(p1 u)              SIN   p0 sin(p1 u)
+ *   CUBIC  u (p0 + u (p1 + p2 u))     (p0 u + p1 u^2 + p2 u^3: Allen-Cahn, Fisher-KPP, any cubic without a constant term) */
+enum { GPK_NL_POWER = 0, GPK_NL_EXP = 1, GPK_NL_SINH = 2, GPK_NL_SIN = 3, GPK_NL_CUBIC = 4 };
 
 /* ---- context, memory, stream ------------------------------------------------------------------------------ */
 int gpk_create(int device, gpk_handle* out);
@@ -117,6 +122,11 @@ int gpk_extend_functionals(gpk_handle h, int layout, int kernel, const double* h
  *   DARCY               r = -e^a (Delta u + grad a . grad u) - f   (v3 = -v1 w1 - v2 w2 - f e^{-w0}, src/InverseProblems.py:185) */
 int gpk_pde_residual(gpk_handle h, int system, const double* host_params3, int Nt,
                      const double* fields_u, int ldu, const double* fields_a, int lda, const double* rhs, double* out);
+/* The same for the elliptic equation with the reaction term tau = GPK_NL_* (nonlin) and host_params3 = (p0, p1, p2):
+ *   r = -u3 + tau(u0) - f,   u0 = row 0 (value) and u3 = row 3 (Laplacian, or psi[u] under a domain operator) of fields_u (ld ldu >= Nt);
+ * rows 1 and 2 are not read.  nonlin = GPK_NL_POWER gives the numbers of gpk_pde_residual(GPK_GN_ELLIPTIC).  nonlin outside the enum: -9001. */
+int gpk_pde_residual_nl(gpk_handle h, int nonlin, const double* host_params3, int Nt,
+                        const double* fields_u, int ldu, const double* rhs, double* out);
 /* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
  *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
  *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
@@ -307,6 +317,9 @@ typedef struct {
     const double* G; int ldg; const double* pvec;
     /* optional (may be NULL), GPK_GN_DARCY only -- see gpk_gn_darcy_prepare */
     const double* Wa; int ldwa; const double* Ha; int ldha;
+    /* reaction term of ELLIPTIC(_RELAXED): GPK_NL_* with the parameters p0, p1 above and p2 (CUBIC only); 0 = alpha u^m.  Any other
+     * system takes 0 only (-9001 otherwise) */
+    int nonlin; double p2;
 } gpk_gn_problem;
 
 /* sizes: nz unknowns, rows of the stacked S = [L^{-1}A | L^{-1}F] buffer */
@@ -343,7 +356,8 @@ int gpk_gn_step(gpk_handle h, const gpk_gn_problem* host_prob, double* z, double
  *   W1 = L^{-1} [I; 0; 0],  W2 = L^{-1} [0; I; 0]   (s_rows x nz each, leading dimension ldw >= nz+1, columns in the internal order of
  *   gpk_gn_step),  v0 = L^{-1} F(0)  (s_rows)
  * computed ONCE by this call (two solves; S is scratch, s_rows x lds), every later gpk_gn_step whose host_prob carries W1, W2, v0, ldw
- * forms  S = [W1 diag(d(z)) + W2 | v0 + W1 (alpha z^m) + W2 z]  in one memory-bound pass instead of the triangular solve.  Same
+ * forms  S = [W1 diag(tau'(z)) + W2 | v0 + W1 (tau(z) - tau(0)) + W2 z]  in one memory-bound pass instead of the triangular solve
+ * (F(0) carries tau(0), which is p0 for GPK_NL_EXP and 0 for every other kind).  Same
  * iterates up to rounding (tests/test_gpu_structured.py); the product, the factorisation and the update are unchanged.
  * Systems other than the elliptic one (round 6: GPK_GN_BURGERS, GPK_GN_EIKONAL, GPK_GN_DARCY; needs Dinv / Dinv2 / dinv_block, i.e. the
  * GEMM-only solve path and its leading-zero layout).  Every column of their A(z) has at most ONE entry that depends on z -- Burgers:
@@ -359,7 +373,7 @@ int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* host_prob, dou
  *   pvec = [W1^T v0 (nz); W2^T v0 (nz); v0^T v0 (1)],
  * computed ONCE by this call from W1, W2, v0 (host_prob must carry them), gpk_gn_step assembles the bordered matrix directly,
  *   H/2 = D G11 D + D G12 + G21 D + G22,   g/2 = D q1 + q2,   loss = v0^T v0 + a.p1 + z.p2 + a.q1 + z.q2
- *   (D = diag(alpha m z^(m-1)), a = alpha z^m, q1 = G11 a + G12 z + p1, q2 = G21 a + G22 z + p2),
+ *   (D = diag(tau'(z)), a = tau(z) - tau(0) -- alpha m z^(m-1) and alpha z^m for the power law --, q1 = G11 a + G12 z + p1, q2 = G21 a + G22 z + p2),
  * in O(nz^2) memory-bound work per step: neither the triangular solve nor the product S^T S is executed; the Cholesky
  * factorisation of H, the solve and the update are unchanged.  Same iterates up to rounding (tests/test_gpu_structured.py).
  * Burgers / Eikonal / Darcy (round 6; host_prob carries the W1, W2 of their structured form, A(z) = A1 diag(d(z)) + A2): the same four

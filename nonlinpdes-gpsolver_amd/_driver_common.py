@@ -29,6 +29,35 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     parser.add_argument("--test_residual", type=bool, default=False)
 
 
+NL_DEFAULTS = {'exp': (-1.0, 1.0), 'sinh': (1.0, 1.0), 'sin': (1.0, 1.0), 'cubic': (-1.0, 0.0, 1.0)}
+
+
+def add_nonlinearity(parser):
+    """--nonlinearity / --nl_params of the elliptic drivers: the reaction term tau(u) of -psi[u] + tau(u) = f (src/nonlinearity.py)"""
+    parser.add_argument("--nonlinearity", type=str, default='power', choices=['power', 'exp', 'sinh', 'sin', 'cubic'])
+    # comma-separated parameters of tau: p0,p1 (exp, sinh, sin: p0*fn(p1*u); power: alpha,m) or c1,c2,c3 (cubic: c1*u + c2*u^2 + c3*u^3)
+    parser.add_argument("--nl_params", type=str, default=None)
+
+
+def nonlinearity_from(cfg):
+    """(tau, spec): the Nonlinearity the command line asks for and what goes into cfg.nonlinearity -- None for `power` without
+    --nl_params, which is the equation alpha*u^m of --alpha / --m, untouched"""
+    from src.nonlinearity import Nonlinearity
+    params = None if cfg.nl_params is None else tuple(float(v) for v in cfg.nl_params.split(',') if v.strip())
+    if cfg.nonlinearity == 'power':
+        if params is None:
+            return Nonlinearity.power(cfg.alpha, cfg.m), None
+        if len(params) != 2:
+            raise SystemExit('--nonlinearity power takes --nl_params alpha,m')
+        cfg.alpha, cfg.m = params
+        return Nonlinearity.power(cfg.alpha, cfg.m), None
+    try:
+        tau = Nonlinearity(cfg.nonlinearity, *(params if params is not None else NL_DEFAULTS[cfg.nonlinearity]))
+    except ValueError as e:
+        raise SystemExit(f'--nl_params: {e}')
+    return tau, tau
+
+
 def figures_enabled(cfg):
     """Figures need matplotlib and a display backend; without them the drivers run headless and say so."""
     if not cfg.show_figure:

@@ -302,6 +302,15 @@ __global__ __launch_bounds__(256) void pde_residual_kernel(int sys, double p0, d
     out[t] = r;
 }
 
+// the elliptic equation with a reaction term of the family (gpk.h, gpk_pde_residual_nl): r = -u3 + tau(u0) - f
+__global__ __launch_bounds__(256) void pde_residual_nl_kernel(int nonlin, double p0, double p1, double p2, int Nt, const double* __restrict__ u,
+                                                              long ldu, const double* __restrict__ f, double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Nt) return;
+    const double u0 = u[t], u3 = u[3 * ldu + t], ft = f[t];
+    out[t] = -u3 + nl_tau(nonlin, p0, p1, p2, u0) - ft;
+}
+
 // f(std::integral_constant<int, L>) for the layout id: the one place that turns it into a template argument; false: not a layout
 template <class F>
 bool with_layout(int layout, F&& f) {
@@ -483,6 +492,21 @@ extern "C" int gpk_pde_residual(gpk_handle h, int system, const double* params3,
     const double p0 = params3 ? params3[0] : 0.0, p1 = params3 ? params3[1] : 0.0;
     pde_residual_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(system, p0, p1, Nt, fields_u, ldu,
                                                                       system == GPK_GN_DARCY ? fields_a : nullptr, lda, rhs, out);
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int gpk_pde_residual_nl(gpk_handle h, int nonlin, const double* params3, int Nt, const double* fields_u, int ldu,
+                                   const double* rhs, double* out) {
+    if (!h) return GPK_ERR_ARG;
+    if (!gpk_nl_valid(nonlin)) return gpk_bad_arg(h, "pde_residual_nl: nonlin is not one of GPK_NL_POWER .. GPK_NL_CUBIC");
+    if (Nt <= 0) return gpk_bad_arg(h, "pde_residual_nl: Nt <= 0");
+    if (!fields_u || !rhs || !out || ldu < Nt) return gpk_bad_arg(h, "pde_residual_nl: fields_u / rhs / out / ldu");
+    if (!params3) return gpk_bad_arg(h, "pde_residual_nl: host_params3");
+    if (nonlin == GPK_NL_POWER)                                       // the power law: the kernel of gpk_pde_residual, hence its numbers
+        pde_residual_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(GPK_GN_ELLIPTIC, params3[0], params3[1], Nt, fields_u, ldu, nullptr, 0, rhs, out);
+    else
+        pde_residual_nl_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(nonlin, params3[0], params3[1], params3[2], Nt, fields_u, ldu, rhs, out);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

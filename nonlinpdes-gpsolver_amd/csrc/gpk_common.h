@@ -317,3 +317,26 @@ int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, cons
                     double* z, double step_size);
 
 static inline int gpk_ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// Reaction term tau(u) of the elliptic systems and its derivative (gpk.h, GPK_NL_*; DESIGN.md section K, "Reaction terms").  The one
+// place that knows the family: gn_build_kernel, structured_coeff_kernel and pde_residual_nl_kernel call it.  GPK_NL_POWER spells
+// alpha * pow(u, m) and alpha * m * pow(u, m - 1.0) exactly as the kernels did before there was a family: same bits.
+__device__ __forceinline__ double nl_tau(int kind, double p0, double p1, double p2, double u) {
+    switch (kind) {
+        case GPK_NL_EXP:   return p0 * exp(p1 * u);
+        case GPK_NL_SINH:  return p0 * sinh(p1 * u);
+        case GPK_NL_SIN:   return p0 * sin(p1 * u);
+        case GPK_NL_CUBIC: return u * (p0 + u * (p1 + p2 * u));
+        default:           return p0 * pow(u, p1);
+    }
+}
+__device__ __forceinline__ double nl_dtau(int kind, double p0, double p1, double p2, double u) {
+    switch (kind) {
+        case GPK_NL_EXP:   return p0 * p1 * exp(p1 * u);
+        case GPK_NL_SINH:  return p0 * p1 * cosh(p1 * u);
+        case GPK_NL_SIN:   return p0 * p1 * cos(p1 * u);
+        case GPK_NL_CUBIC: return p0 + u * (2.0 * p1 + 3.0 * p2 * u);
+        default:           return p0 * p1 * pow(u, p1 - 1.0);
+    }
+}
+static inline bool gpk_nl_valid(int kind) { return kind >= GPK_NL_POWER && kind <= GPK_NL_CUBIC; }

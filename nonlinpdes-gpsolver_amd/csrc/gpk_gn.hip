@@ -48,6 +48,7 @@ int gn_dims(const gpk_gn_problem* p, Dims& d) {
 struct BuildArgs {
     int system, Nd, Nb, Ndata;
     double p0, p1, lam;
+    int nonlin; double p2;   // reaction term of the elliptic systems (GPK_NL_*; nl_tau / nl_dtau of gpk_common.h)
     const double* f; const double* gb; const double* data; const double* z;
     double* S; long lds; int fcol; int write_A;
     int rev;           // leading-zero layout of gn_step: unknown j is stored in column nz-1-pos(j), and that column of A(z) is zero above
@@ -111,14 +112,19 @@ __global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
     const int Nd = a.Nd, Nb = a.Nb;
     const double* z = a.z;
     if (a.system == GPK_GN_ELLIPTIC) {                      // src/PDEs.py:84-85 (F), :95-96 (A)
-        const double alpha = a.p0, m = a.p1;
         if (a.family == 1) {
             if (t < Nd) putA(a, t, t, 1.0);
         } else if (t < Nd) {
             const double zi = z[t];
-            if (a.family == 0) putA(a, t, t, alpha * m * pow(zi, m - 1.0));
+            if (a.nonlin == GPK_NL_POWER) {                 // the reference's equation, spelled as it always was: same bits
+                const double alpha = a.p0, m = a.p1;
+                if (a.family == 0) putA(a, t, t, alpha * m * pow(zi, m - 1.0));
+                putF(a, t, alpha * pow(zi, m) - a.f[t]);
+            } else {
+                if (a.family == 0) putA(a, t, t, nl_dtau(a.nonlin, a.p0, a.p1, a.p2, zi));
+                putF(a, t, nl_tau(a.nonlin, a.p0, a.p1, a.p2, zi) - a.f[t]);
+            }
             putA(a, Nd + t, t, 1.0);
-            putF(a, t, alpha * pow(zi, m) - a.f[t]);
             putF(a, Nd + t, zi);
         } else if (t < Nd + Nb) putF(a, 2 * Nd + (t - Nd), a.gb[t - Nd]);
     } else if (a.family != 0) {
@@ -195,8 +201,14 @@ __global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
             const double v = z[t], w = z[Nd + t];
             putA(a, t, t, 1.0); putF(a, t, v);
             putA(a, Nd + t, Nd + t, 1.0); putF(a, Nd + t, w);
-            putA(a, P + t, t, -rs); putA(a, P + t, Nd + t, alpha * m * pow(w, m - 1.0) * rs);
-            putF(a, P + t, (-v + alpha * pow(w, m) - a.f[t]) * rs);
+            putA(a, P + t, t, -rs);
+            if (a.nonlin == GPK_NL_POWER) {
+                putA(a, P + t, Nd + t, alpha * m * pow(w, m - 1.0) * rs);
+                putF(a, P + t, (-v + alpha * pow(w, m) - a.f[t]) * rs);
+            } else {
+                putA(a, P + t, Nd + t, nl_dtau(a.nonlin, a.p0, a.p1, a.p2, w) * rs);
+                putF(a, P + t, (-v + nl_tau(a.nonlin, a.p0, a.p1, a.p2, w) - a.f[t]) * rs);
+            }
         } else if (t < Nd + Nb) putF(a, 2 * Nd + (t - Nd), a.gb[t - Nd]);
     }
 }
@@ -227,6 +239,7 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     a.rev = rev; a.nz = fcol; a.family = family;
     a.system = p->system; a.Nd = p->Nd; a.Nb = p->Nb; a.Ndata = p->Ndata;
     a.p0 = p->p0; a.p1 = p->p1; a.lam = p->pen_lambda;
+    a.nonlin = p->nonlin; a.p2 = p->p2;
     a.f = p->rhs_f; a.gb = p->bdy_g; a.data = p->data_u; a.z = z;
     a.S = S; a.lds = lds; a.fcol = fcol; a.write_A = write_A;
     gn_build_kernel<<<gpk_ceil_div(p->Nd + p->Nb, 256), 256, 0, h->stream>>>(a);
@@ -234,9 +247,18 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     return 0;
 }
 
+// the reaction term is one of the family, and only the elliptic systems have one
+int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
+    if (!gpk_nl_valid(p->nonlin)) return gpk_bad_arg(h, "gn: nonlin is not one of GPK_NL_POWER .. GPK_NL_CUBIC");
+    if (p->nonlin != GPK_NL_POWER && p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_ELLIPTIC_RELAXED)
+        return gpk_bad_arg(h, "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED");
+    return 0;
+}
+
 int check_prob(gpk_handle h, const gpk_gn_problem* p, Dims& d) {
     if (!p) return gpk_bad_arg(h, "gn: null problem");
     if (gn_dims(p, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");
+    GPK_TRY(check_nonlin(h, p));
     if (!p->rhs_f || (p->Nb > 0 && !p->bdy_g) || !p->L) return gpk_bad_arg(h, "gn: null rhs_f/bdy_g/L");
     if (p->system == GPK_GN_DARCY && (!p->L2 || (p->Ndata > 0 && !p->data_u))) return gpk_bad_arg(h, "gn: Darcy needs L2 and data_u");
     return 0;
@@ -416,13 +438,21 @@ int assemble_normal_equations(gpk_handle h, const gpk_gn_problem* p, const Dims&
 
 // ---- structured solve of the elliptic system (optional, gpk_gn_structured_prepare) -------------------------------------------
 // per-column coefficients in the internal (reversed) column order: column c holds unknown u = nz-1-c
-__global__ void structured_coeff_kernel(int nz, double alpha, double m, const double* __restrict__ z, double* __restrict__ dcol,
-                                        double* __restrict__ acol, double* __restrict__ zcol) {
+// dcol = tau'(z), acol = tau(z) - tau(0): v0 = L^{-1}F(0) of gpk_gn_structured_prepare already carries tau(0) (p0 for GPK_NL_EXP, 0 for
+// every other kind; the power law keeps its own expression, to the bit)
+__global__ void structured_coeff_kernel(int nz, int nonlin, double p0, double p1, double p2, const double* __restrict__ z,
+                                        double* __restrict__ dcol, double* __restrict__ acol, double* __restrict__ zcol) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= nz) return;
     const double zi = z[nz - 1 - c];
-    dcol[c] = alpha * m * pow(zi, m - 1.0);
-    acol[c] = alpha * pow(zi, m);
+    if (nonlin == GPK_NL_POWER) {
+        const double alpha = p0, m = p1;
+        dcol[c] = alpha * m * pow(zi, m - 1.0);
+        acol[c] = alpha * pow(zi, m);
+    } else {
+        dcol[c] = nl_dtau(nonlin, p0, p1, p2, zi);
+        acol[c] = nonlin == GPK_NL_EXP ? p0 * expm1(p1 * zi) : nl_tau(nonlin, p0, p1, p2, zi) - nl_tau(nonlin, p0, p1, p2, 0.0);
+    }
     zcol[c] = zi;
 }
 
@@ -737,7 +767,7 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         // optional Gram level (gpk_gn_gram_prepare): the bordered matrix assembled in O(nz^2), no solve and no product this step
         GPK_PROF_MARK(h, 0);
         double* coef = S;                                            // d, a, z (column order), then q1, q2: 5 nz doubles of scratch
-        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->p0, p->p1, z, coef, coef + nz, coef + 2 * nz);
+        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
         gram_gemv_kernel<<<nz, 256, 0, h->stream>>>(nz, p->G, p->ldg, p->pvec, coef + nz, coef + 2 * nz, coef + 3 * nz);
         GPK_PROF_MARK(h, 1);
         gram_form_kernel<<<nz + 1, 256, 0, h->stream>>>(nz, p->G, p->ldg, coef, coef + 3 * nz, Hb, ldh);
@@ -757,7 +787,7 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         double* coef = S;                                            // 3 nz doubles of scratch (S is free in this mode)
         GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &W));
         h->work_sig[0] = -1;                                         // (the workspace no longer holds a solve of a known shape)
-        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->p0, p->p1, z, coef, coef + nz, coef + 2 * nz);
+        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
         structured_form_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, p->v0, coef, coef + nz, coef + 2 * nz, W, lds);
         GPK_LAUNCH_CHECK(h);
         if (h->tune.exact_loss) { exact = true; GPK_TRY(exact_loss(h, p, d, z)); }   // reported loss: true substitution (round 6), as in the plain branch
@@ -945,6 +975,7 @@ extern "C" int gpk_gn_build(gpk_handle h, const gpk_gn_problem* p, const double*
     Dims d;
     gpk_gn_problem q = *p;
     if (gn_dims(&q, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");
+    GPK_TRY(check_nonlin(h, &q));
     if (lds < d.nz + 1) return gpk_bad_arg(h, "gn: lds < nz+1");
     GPK_HIP(h, hipMemsetAsync(S, 0, (size_t)d.rows * lds * sizeof(double), h->stream));
     return build(h, &q, z, S, lds, d.nz, 1);
@@ -958,6 +989,7 @@ extern "C" int gpk_gn_build_rev(gpk_handle h, const gpk_gn_problem* p, const dou
     Dims d;
     gpk_gn_problem q = *p;
     if (gn_dims(&q, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");
+    GPK_TRY(check_nonlin(h, &q));
     if (lds < d.nz + 1) return gpk_bad_arg(h, "gn: lds < nz+1");
     GPK_HIP(h, hipMemsetAsync(S, 0, (size_t)d.rows * lds * sizeof(double), h->stream));
     return build(h, &q, z, S, lds, d.nz, 1, rev);
@@ -976,6 +1008,7 @@ extern "C" int gpk_gn_measurement(gpk_handle h, const gpk_gn_problem* p, const d
     Dims d;
     gpk_gn_problem q = *p;
     if (gn_dims(&q, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");
+    GPK_TRY(check_nonlin(h, &q));
     GPK_HIP(h, hipMemsetAsync(out, 0, (size_t)d.rows * sizeof(double), h->stream));
     return build(h, &q, z, out, 1, 0, 0);
 }

@@ -20,7 +20,8 @@ class GNProblemStruct(C.Structure):
                 ('Dinv', C.c_void_p), ('Dinv2', C.c_void_p), ('dinv_block', C.c_int),
                 ('W1', C.c_void_p), ('W2', C.c_void_p), ('v0', C.c_void_p), ('ldw', C.c_int),
                 ('G', C.c_void_p), ('ldg', C.c_int), ('pvec', C.c_void_p),
-                ('Wa', C.c_void_p), ('ldwa', C.c_int), ('Ha', C.c_void_p), ('ldha', C.c_int)]
+                ('Wa', C.c_void_p), ('ldwa', C.c_int), ('Ha', C.c_void_p), ('ldha', C.c_int),
+                ('nonlin', C.c_int), ('p2', C.c_double)]
 
 
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
@@ -90,6 +91,7 @@ PROTOTYPES = {
     'gpk_assemble_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _vp, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     'gpk_pde_residual': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'gpk_pde_residual_nl': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _vp]),
     'gpk_potrf': (_i, [_vp, _vp, _i, _i, _pi]),
     'gpk_tril': (_i, [_vp, _vp, _i, _i]),
     'gpk_symmetrize_lower': (_i, [_vp, _vp, _i, _i]),

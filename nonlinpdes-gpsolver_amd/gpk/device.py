@@ -34,6 +34,7 @@ def dinv_block_for(n):
         db //= 2
     return db
 SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4}
+NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
 
 
 def pad_ld(n, mult=16):
@@ -123,8 +124,10 @@ class GNProblem:
     """Device-side description of one equation's Gauss-Newton system (gpk_gn_problem)."""
 
     def __init__(self, ctx, system, Nd, Nb, rhs_f, bdy_g, L, p0=0.0, p1=0.0, pen_lambda=0.0, data_u=None, L2=None, dinv=True, structured=False,
-                 cache_a=None):
-        """structured: False (default: the reference's operation sequence every step), True / 1 (prepare_structured), 2 (+ prepare_gram).
+                 cache_a=None, nonlin=0, p2=0.0):
+        """nonlin, p2 (elliptic systems only): the reaction term tau(u) -- a GPK_NL_* id or its name in NONLIN -- with the parameters
+        p0, p1, p2; 0 / 'power' is p0 u^p1, the reference's equation.
+        structured: False (default: the reference's operation sequence every step), True / 1 (prepare_structured), 2 (+ prepare_gram).
         cache_a (Darcy only): keep the iteration-independent a-part of the step (prepare_darcy: bit-identical iterates, less work per step);
         None = on unless GPK_DARCY_CACHE=0.
         dinv: also compute the inverses of the diagonal blocks of the factor(s) once (gpk_trtri_diag; True = blocks of
@@ -144,6 +147,7 @@ class GNProblem:
         s.Nd, s.Nb = int(Nd), int(Nb)
         s.Ndata = 0 if data_u is None else int(np.asarray(data_u).size)
         s.p0, s.p1, s.pen_lambda = float(p0), float(p1), float(pen_lambda)
+        s.nonlin, s.p2 = (NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)), float(p2)
         s.rhs_f, s.bdy_g = self.rhs_f.ptr, self.bdy_g.ptr
         s.data_u = self.data_u.ptr if self.data_u is not None else None
         s.L, s.ldl = L.ptr, L.ld
@@ -514,6 +518,19 @@ class Context:
         p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]]) if params is not None else None
         self._chk(self.lib.gpk_pde_residual(self.h, SYSTEM[system], p, Nt, du.ptr, du.ld, da.ptr if da is not None else None,
                                             da.ld if da is not None else 0, dr.ptr, out.ptr))
+        self.synchronize()
+        return out
+
+    def pde_residual_nl(self, nonlin, params, fields_u, rhs):
+        """Pointwise residual -u3 + tau(u0) - f of the elliptic equation with the reaction term `nonlin` (a GPK_NL_* id or its name in
+        NONLIN) and params = (p0, p1, p2) (gpk_pde_residual_nl), as an (Nt,) DeviceArray.  fields_u, rhs as for pde_residual."""
+        du = fields_u if isinstance(fields_u, DeviceArray) else self.array(np.atleast_2d(fields_u))
+        Nt = du.cols
+        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        out = DeviceArray(self, Nt)
+        p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]])
+        kind = NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)
+        self._chk(self.lib.gpk_pde_residual_nl(self.h, kind, p, Nt, du.ptr, du.ld, dr.ptr, out.ptr))
         self.synchronize()
         return out
 

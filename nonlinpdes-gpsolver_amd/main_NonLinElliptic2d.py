@@ -7,12 +7,18 @@ The manufactured solution's right-hand side is written out analytically (the ref
 instead of u = g, with g formed from the manufactured solution's gradient and the outward normal.
 --operator advection_diffusion (no counterpart in the reference either) solves -div(a grad u) + v . grad u + c u + alpha*u^m = f with the
 fields of advection_diffusion_fields() below and the right-hand side that makes the same u* the solution; --operator laplace (the
-default) is the equation above.  --bc works with either."""
+default) is the equation above.  --bc works with either.
+--nonlinearity exp|sinh|sin|cubic [--nl_params=p0,p1[,p2]] (no counterpart in the reference) replaces alpha*u^m by another reaction term
+tau(u): p0*exp(p1*u), p0*sinh(p1*u), p0*sin(p1*u) or p0*u + p1*u^2 + p2*u^3; the right-hand side is manufactured with the same tau, so
+every --operator / --bc combination works with every kind:
+    python main_NonLinElliptic2d.py --nonlinearity exp --nl_params=-1,1 --nugget 1e-8          (Bratu)
+    python main_NonLinElliptic2d.py --nonlinearity sinh --nl_params=4,1 --bc robin --nugget 1e-8   (Poisson-Boltzmann)"""
 import argparse
 
 import numpy as onp
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, solve_forward, tensor_grid
+from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, add_nonlinearity, nonlinearity_from, report_test_error,
+                            report_test_residual, solve_forward, tensor_grid)
 
 UNIT_SQUARE = [[0, 1], [0, 1]]
 
@@ -26,20 +32,28 @@ def parse(argv=None):
     parser.add_argument("--bc", type=str, default='dirichlet', choices=['dirichlet', 'neumann', 'robin'])
     parser.add_argument("--robin_beta", type=float, default=1.0)        # beta of --bc robin: beta u + du/dn = g
     parser.add_argument("--operator", type=str, default='laplace', choices=['laplace', 'advection_diffusion'])
+    add_nonlinearity(parser)
     add_gn_and_logs(parser, 'rdm', 4, method_choices=['elimination', 'relaxation'])
     return parser.parse_args(argv)
 
 
-def manufactured(alpha, m):
-    """u* = sin(pi x1) sin(pi x2) + 2 sin(4 pi x1) sin(4 pi x2) and f = -Laplace(u*) + alpha u*^m"""
+def reaction(alpha, m=None):
+    """the reaction term as a Nonlinearity: `alpha` is one already, or (alpha, m) of the power law"""
+    from src.nonlinearity import Nonlinearity
+    return alpha if isinstance(alpha, Nonlinearity) else Nonlinearity.power(alpha, m)
+
+
+def manufactured(alpha, m=None):
+    """u* = sin(pi x1) sin(pi x2) + 2 sin(4 pi x1) sin(4 pi x2) and f = -Laplace(u*) + tau(u*); tau: a Nonlinearity, or alpha, m of alpha u^m"""
     pi = onp.pi
+    tau = reaction(alpha, m)
 
     def u(x1, x2):
         return onp.sin(pi * x1) * onp.sin(pi * x2) + 2 * onp.sin(4 * pi * x1) * onp.sin(4 * pi * x2)
 
     def f(x1, x2):
         lap = -2 * pi ** 2 * onp.sin(pi * x1) * onp.sin(pi * x2) - 64 * pi ** 2 * onp.sin(4 * pi * x1) * onp.sin(4 * pi * x2)
-        return -lap + alpha * (u(x1, x2) ** m)
+        return -lap + tau.tau(u(x1, x2))
     return u, f
 
 
@@ -68,16 +82,17 @@ def advection_diffusion(x1, x2):
 OPERATORS = {'laplace': None, 'advection_diffusion': advection_diffusion}
 
 
-def manufactured_operator_rhs(alpha, m):
-    """f = -div(a grad u*) + v . grad u* + c u* + alpha u*^m for u* of manufactured() and the fields above"""
+def manufactured_operator_rhs(alpha, m=None):
+    """f = -div(a grad u*) + v . grad u* + c u* + tau(u*) for u* of manufactured() and the fields above"""
     pi = onp.pi
-    u, _ = manufactured(alpha, m)
+    tau = reaction(alpha, m)
+    u, _ = manufactured(tau)
 
     def f(x1, x2):
         a, a1, a2, v1, v2, c = advection_diffusion_fields(x1, x2)
         u1, u2 = manufactured_gradient(x1, x2)
         lap = -2 * pi ** 2 * onp.sin(pi * x1) * onp.sin(pi * x2) - 64 * pi ** 2 * onp.sin(4 * pi * x1) * onp.sin(4 * pi * x2)
-        return -(a * lap + a1 * u1 + a2 * u2) + v1 * u1 + v2 * u2 + c * u(x1, x2) + alpha * (u(x1, x2) ** m)
+        return -(a * lap + a1 * u1 + a2 * u2) + v1 * u1 + v2 * u2 + c * u(x1, x2) + tau.tau(u(x1, x2))
     return f
 
 
@@ -98,9 +113,10 @@ def boundary_data(u, bc, robin_beta, domain=UNIT_SQUARE):
 
 def main(argv=None):
     cfg = parse(argv)
-    u, f = manufactured(cfg.alpha, cfg.m)
+    tau, cfg.nonlinearity = nonlinearity_from(cfg)                      # (None: alpha*u^m of --alpha / --m, the facade's default)
+    u, f = manufactured(tau)
     if cfg.operator != 'laplace':
-        f = manufactured_operator_rhs(cfg.alpha, cfg.m)
+        f = manufactured_operator_rhs(tau)
         cfg.operator = OPERATORS[cfg.operator]                           # the facade takes the callable (or 'laplace' / None: the Laplacian)
     solver, show = solve_forward(cfg, "Nonlinear_elliptic", boundary_data(u, cfg.bc, cfg.robin_beta), f, UNIT_SQUARE,
                                  solve_kwargs={'method': cfg.method, 'pen_lambda': cfg.pen_lambda}, verbose=cfg.print_hist)

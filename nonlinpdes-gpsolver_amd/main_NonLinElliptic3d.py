@@ -10,12 +10,16 @@ and the right-hand side that makes the same u* the solution (--bc works with it)
 --operator parabolic treats axis 3 as time: u_t - nu Laplace_x u + alpha*u^m = f on the unit square x [0,1] by space-time collocation,
 initial and lateral data only (no points on the face t = 1; N_boundary divisible by 5 for random points), Dirichlet data:
     python main_NonLinElliptic3d.py --operator advection_diffusion --bc robin --robin_beta 2
-    python main_NonLinElliptic3d.py --operator parabolic --nu 0.2 --N_boundary 485"""
+    python main_NonLinElliptic3d.py --operator parabolic --nu 0.2 --N_boundary 485
+--nonlinearity exp|sinh|sin|cubic [--nl_params=p0,p1[,p2]] replaces alpha*u^m by another reaction term tau(u), as in two dimensions; with
+--operator parabolic and a cubic this is time-dependent Allen-Cahn, u_t - nu Laplace_x u - u + u^3 = f:
+    python main_NonLinElliptic3d.py --operator parabolic --nonlinearity cubic --nl_params=-1,0,1 --N_boundary 485"""
 import argparse
 
 import numpy as onp
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, solve_forward
+from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, add_nonlinearity, nonlinearity_from, report_test_error,
+                            report_test_residual, solve_forward)
 
 UNIT_CUBE = [[0, 1], [0, 1], [0, 1]]
 GRID = 20                                                                # test grid: GRID^3 points
@@ -30,13 +34,21 @@ def parse(argv=None):
     parser.add_argument("--robin_beta", type=float, default=1.0)        # beta of --bc robin: beta u + du/dn = g
     parser.add_argument("--operator", type=str, default='laplace', choices=['laplace', 'advection_diffusion', 'parabolic'])
     parser.add_argument("--nu", type=float, default=0.2)                # diffusivity of --operator parabolic
+    add_nonlinearity(parser)
     add_gn_and_logs(parser, 'rdm', 6, method_choices=['elimination'])
     return parser.parse_args(argv)
 
 
-def manufactured(alpha, m):
-    """u* = prod_k sin(pi x_k) + 2 prod_k sin(2 pi x_k) and f = -Laplace(u*) + alpha u*^m"""
+def reaction(alpha, m=None):
+    """the reaction term as a Nonlinearity: `alpha` is one already, or (alpha, m) of the power law"""
+    from src.nonlinearity import Nonlinearity
+    return alpha if isinstance(alpha, Nonlinearity) else Nonlinearity.power(alpha, m)
+
+
+def manufactured(alpha, m=None):
+    """u* = prod_k sin(pi x_k) + 2 prod_k sin(2 pi x_k) and f = -Laplace(u*) + tau(u*); tau: a Nonlinearity, or alpha, m of alpha u^m"""
     pi = onp.pi
+    tau = reaction(alpha, m)
 
     def modes(x1, x2, x3):
         return (onp.sin(pi * x1) * onp.sin(pi * x2) * onp.sin(pi * x3),
@@ -49,7 +61,7 @@ def manufactured(alpha, m):
     def f(x1, x2, x3):
         s1, s2 = modes(x1, x2, x3)
         lap = -3 * pi ** 2 * s1 - 24 * pi ** 2 * s2
-        return -lap + alpha * (u(x1, x2, x3) ** m)
+        return -lap + tau.tau(u(x1, x2, x3))
     return u, f
 
 
@@ -79,26 +91,34 @@ def advection_diffusion(x1, x2, x3):
     return divergence_form3d(*advection_diffusion_fields(x1, x2, x3))
 
 
-def operator_rhs(fields, u, grad, lap, alpha, m):
-    """f = -div(a grad u) + v . grad u + c u + alpha u^m for the fields (a, grad a, v, c) and a solution given with gradient and Laplacian"""
+def operator_rhs(fields, u, grad, lap, alpha, m=None):
+    """f = -div(a grad u) + v . grad u + c u + tau(u) for the fields (a, grad a, v, c) and a solution given with gradient and Laplacian"""
+    tau = reaction(alpha, m)
+
     def f(x1, x2, x3):
         a, a1, a2, a3, v1, v2, v3, c = fields(x1, x2, x3)
         u1, u2, u3 = grad(x1, x2, x3)
         w = u(x1, x2, x3)
-        return -(a * lap(x1, x2, x3) + a1 * u1 + a2 * u2 + a3 * u3) + v1 * u1 + v2 * u2 + v3 * u3 + c * w + alpha * (w ** m)
+        return -(a * lap(x1, x2, x3) + a1 * u1 + a2 * u2 + a3 * u3) + v1 * u1 + v2 * u2 + v3 * u3 + c * w + tau.tau(w)
     return f
 
 
-def manufactured_operator_rhs(alpha, m):
+def manufactured_operator_rhs(alpha, m=None):
     """the right-hand side of --operator advection_diffusion for u* of manufactured()"""
-    u, f0 = manufactured(alpha, m)
-    lap = lambda x1, x2, x3: -(f0(x1, x2, x3) - alpha * (u(x1, x2, x3) ** m))
-    return operator_rhs(advection_diffusion_fields, u, manufactured_gradient, lap, alpha, m)
+    tau = reaction(alpha, m)
+    u, f0 = manufactured(tau)
+    lap = lambda x1, x2, x3: -(f0(x1, x2, x3) - tau.tau(u(x1, x2, x3)))
+    return operator_rhs(advection_diffusion_fields, u, manufactured_gradient, lap, tau)
 
 
-def parabolic_manufactured(alpha, m, nu):
-    """u*(x1, x2, t) = e^{-t} sin(pi x1) sin(pi x2) + t/2 sin(2 pi x1) sin(pi x2) and f = u*_t - nu Laplace_x u* + alpha u*^m"""
+def parabolic_manufactured(alpha, m, nu=None):
+    """u*(x1, x2, t) = e^{-t} sin(pi x1) sin(pi x2) + t/2 sin(2 pi x1) sin(pi x2) and f = u*_t - nu Laplace_x u* + tau(u*); called as
+    (alpha, m, nu) for alpha u^m or as (tau, nu) with a Nonlinearity"""
     pi = onp.pi
+    if nu is None:
+        tau, nu = reaction(alpha), m
+    else:
+        tau = reaction(alpha, m)
 
     def modes(x1, x2):
         return onp.sin(pi * x1) * onp.sin(pi * x2), onp.sin(2 * pi * x1) * onp.sin(pi * x2)
@@ -111,7 +131,7 @@ def parabolic_manufactured(alpha, m, nu):
         s1, s2 = modes(x1, x2)
         ut = -onp.exp(-t) * s1 + 0.5 * s2
         lap = -2 * pi ** 2 * onp.exp(-t) * s1 - 5 * pi ** 2 * 0.5 * t * s2
-        return ut - nu * lap + alpha * (u(x1, x2, t) ** m)
+        return ut - nu * lap + tau.tau(u(x1, x2, t))
     return u, f
 
 
@@ -138,19 +158,20 @@ def cube_grid(n=GRID):
 def main(argv=None):
     cfg = parse(argv)
     cfg.show_figure = False                                              # accepted and ignored
-    u, f = manufactured(cfg.alpha, cfg.m)
+    tau, cfg.nonlinearity = nonlinearity_from(cfg)                      # (None: alpha*u^m of --alpha / --m, the facade's default)
+    u, f = manufactured(tau)
     bdy = u
     if cfg.operator == 'parabolic':
         if cfg.bc != 'dirichlet':
             raise SystemExit('--operator parabolic takes Dirichlet data (initial and lateral values)')
         from src.PDEs import parabolic_form
-        u, f = parabolic_manufactured(cfg.alpha, cfg.m, cfg.nu)
+        u, f = parabolic_manufactured(tau, cfg.nu)
         bdy = u
         cfg.operator = parabolic_form(cfg.nu)                            # the facade takes the callable (or 'laplace' / None: the Laplacian)
         cfg.time_dependent = True
     else:
         if cfg.operator == 'advection_diffusion':
-            f = manufactured_operator_rhs(cfg.alpha, cfg.m)
+            f = manufactured_operator_rhs(tau)
             cfg.operator = advection_diffusion
         if cfg.bc != 'dirichlet':
             bdy = boundary_data(u, manufactured_gradient, cfg.bc, cfg.robin_beta)

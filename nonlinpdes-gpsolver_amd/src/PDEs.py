@@ -14,6 +14,7 @@ from numpy import random
 import gpk
 
 from ._runtime import eval_callback, get_context
+from .nonlinearity import Nonlinearity
 from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
@@ -99,6 +100,16 @@ class _GPEquation(object):
     def _gn_params(self):
         raise NotImplementedError
 
+    def _nl_args(self):
+        """GNProblem keywords of the reaction term: none unless an elliptic class carries one other than the power law (whose alpha, m
+        travel as p0, p1 of _gn_params(), as they always did)"""
+        if getattr(self, 'nonlinearity', None) is None:
+            return {}
+        tau = self._tau()
+        if tau.kind == 0:
+            return {}
+        return dict(p0=tau.params[0], p1=tau.params[1], p2=tau.params[2], nonlin=tau.kind)
+
     def _problem(self):
         if getattr(self, '_prob', None) is None:
             if getattr(self, '_dL', None) is None:
@@ -110,7 +121,7 @@ class _GPEquation(object):
             structured = int(os.environ.get('GPK_STRUCTURED', '0') or 0)
             # (2 = the Gram level: since round 6 for every system with a structured form)
             self._prob = gpk.GNProblem(get_context(), self._system, self.N_domain, self.N_boundary, self.rhs_f, self.bdy_g,
-                                       self._dL, p0=p0, p1=p1, pen_lambda=lam, structured=structured)
+                                       self._dL, **dict(dict(p0=p0, p1=p1), **self._nl_args()), pen_lambda=lam, structured=structured)
         return self._prob
 
     # ---- Gram matrix + Cholesky ------------------------------------------------------------------------------------
@@ -283,13 +294,20 @@ class _GPEquation(object):
     def _residual_params(self):
         return self._gn_params()[:2]
 
+    def _residual(self, fields_u, fields_a, rhs):
+        """the residual kernel on rows of the extension: gpk_pde_residual, or gpk_pde_residual_nl when a reaction term other than the
+        power law is set (elliptic classes)"""
+        tau = self._tau() if getattr(self, 'nonlinearity', None) is not None else None
+        if tau is not None and tau.kind != 0:
+            return get_context().pde_residual_nl(tau.kind, tau.params, fields_u, rhs).download().reshape(-1)
+        return get_context().pde_residual(self._system, self._residual_params(), fields_u, fields_a, rhs).download().reshape(-1)
+
     def PDE_residual(self, X_test):
         """pointwise residual of the equation at X_test from the derivatives of the GP solution (rhs evaluated at X_test)"""
         X_test = onp.asarray(X_test, dtype=onp.float64)
         fields = self._derivative_fields(X_test)
         rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
-        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields['u'], fields.get('a'),
-                                                        rhs).download().reshape(-1)
+        self.test_residual = self._residual(fields['u'], fields.get('a'), rhs)
         return self.test_residual
 
 
@@ -302,8 +320,11 @@ class Nonlinear_elliptic2d(_GPEquation):
     _BC = ('dirichlet', 'neumann', 'robin')
 
     def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
-                 operator=None):
-        """bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
+                 operator=None, nonlinearity=None):
+        """nonlinearity (no counterpart in the reference): the reaction term tau of -psi[u] + tau(u) = f as (name, parameters...) --
+        ('exp', p0, p1) p0 exp(p1 u); ('sinh', p0, p1); ('sin', p0, p1); ('cubic', c1, c2, c3) c1 u + c2 u^2 + c3 u^3; ('power', alpha, m)
+        -- or None: alpha u^m with the arguments alpha, m, and every call goes the way it always went (src/nonlinearity.py).
+        bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
         g = B u is what `bdy(x1, x2)` returns -- 'dirichlet' B u = u; 'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the
         outward unit normal (sample_points.boundary_normals).  set_boundary_operator() takes an arbitrary first-order operator per
         boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went.
@@ -326,9 +347,14 @@ class Nonlinear_elliptic2d(_GPEquation):
             raise ValueError(f'operator {operator!r}: a callable operator(x1, x2) returning six coefficient arrays, or None')
         self.operator = operator
         self.domain_coeffs = None
+        self.nonlinearity = None if nonlinearity is None else Nonlinearity.make(nonlinearity)
 
     def _gn_params(self):
         return float(self.alpha), float(self.m), 0.0
+
+    def _tau(self):
+        """the reaction term: the one given, or the power law of the current alpha, m"""
+        return self.nonlinearity if self.nonlinearity is not None else Nonlinearity.power(self.alpha, self.m)
 
     # ---- boundary operator: (N_boundary, 3) coefficients (c0, c1, c2) of c0 u + c1 u_x1 + c2 u_x2, or None = Dirichlet, today's path ----
     def _set_points(self, X_domain, X_boundary):
@@ -442,7 +468,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         X_test = onp.asarray(X_test, dtype=onp.float64)
         fields = self._derivative_fields(X_test, coeffs_t)
         rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
-        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields['u'], None, rhs).download().reshape(-1)
+        self.test_residual = self._residual(fields['u'], None, rhs)
         return self.test_residual
 
     def boundary_residual(self, X_bt, coeffs_t, g_t):
@@ -467,7 +493,7 @@ class Nonlinear_elliptic2d(_GPEquation):
 
     def GN_loss(self, z, z_old):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        zz = onp.concatenate([self.alpha * self.m * (z_old ** (self.m - 1)) * (z - z_old), z, self.bdy_g])
+        zz = onp.concatenate([self._tau().dtau(z_old) * (z - z_old), z, self.bdy_g])
         return self._tri_loss(zz)
 
     def Hessian_GN(self, z, z_old):
@@ -477,7 +503,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         sol = self._initial(initial_sol, self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        self.sol_vec = onp.concatenate([self.alpha * (sol ** self.m) - self.rhs_f, sol, self.bdy_g])
+        self.sol_vec = onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g])
         self.sol_sampled_pts = sol
 
     # ---- relaxed (penalised) formulation, reference src/PDEs.py:137-201 ----
@@ -485,7 +511,8 @@ class Nonlinear_elliptic2d(_GPEquation):
         key = ('_prob_relaxed', float(pen_lambda))
         if getattr(self, '_prob_relaxed_key', None) != key:
             self._prob_relaxed = gpk.GNProblem(get_context(), 'Nonlinear_elliptic_relaxed', self.N_domain, self.N_boundary,
-                                               self.rhs_f, self.bdy_g, self._dL, p0=float(self.alpha), p1=float(self.m),
+                                               self.rhs_f, self.bdy_g, self._dL,
+                                               **dict(dict(p0=float(self.alpha), p1=float(self.m)), **self._nl_args()),
                                                pen_lambda=float(pen_lambda))
             self._prob_relaxed_key = key
         return self._prob_relaxed
@@ -500,7 +527,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
         Nd = self.N_domain
         v, w, w_old = z[:Nd], z[Nd:], z_old[Nd:]
-        ss2 = -v + self.alpha * self.m * (w_old ** (self.m - 1)) * (w - w_old) - self.rhs_f
+        ss2 = -v + self._tau().dtau(w_old) * (w - w_old) - self.rhs_f
         return self._tri_loss(onp.concatenate([v, w, self.bdy_g])) + float(ss2 @ ss2) / pen_lambda
 
     def Hessian_GN_relaxed(self, z, z_old, pen_lambda):
@@ -533,8 +560,10 @@ class Nonlinear_elliptic3d(_GPEquation):
     _op_names = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')    # rows of gpk_extend_functionals_op3d
 
     def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
-                 operator=None):
-        """bc: the operator B on the boundary, whose prescribed value g = B u is what `bdy(x1, x2, x3)` returns -- 'dirichlet' B u = u;
+                 operator=None, nonlinearity=None):
+        """nonlinearity: the reaction term tau of -psi[u] + tau(u) = f as (name, parameters...), as for Nonlinear_elliptic2d; None:
+        alpha u^m.  With parabolic_form() and ('cubic', -1, 0, 1) the equation is time-dependent Allen-Cahn.
+        bc: the operator B on the boundary, whose prescribed value g = B u is what `bdy(x1, x2, x3)` returns -- 'dirichlet' B u = u;
         'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the outward unit normal (sample_points.boundary_normals3d).
         operator: a callable operator(x1, x2, x3) returning the ten coefficient arrays (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) of
         psi; the equation solved is then -psi[u] + alpha u^m = f (divergence_form3d(), parabolic_form(); a mixed coefficient multiplies
@@ -553,6 +582,9 @@ class Nonlinear_elliptic3d(_GPEquation):
         self.operator = operator
         self.boundary_coeffs = None
         self.domain_coeffs = None
+        self.nonlinearity = None if nonlinearity is None else Nonlinearity.make(nonlinearity)
+
+    _tau = Nonlinear_elliptic2d._tau
 
     def get_bd(self, x1, x2, x3):
         return self.bdy(x1, x2, x3)
@@ -635,7 +667,7 @@ class Nonlinear_elliptic3d(_GPEquation):
                 raise RuntimeError('call Gram_matrix() and Gram_Cholesky() first')
             p0, p1, lam = self._gn_params()
             self._prob = gpk.GNProblem(get_context(), self._system, self.N_domain, self.N_boundary, self.rhs_f, self.bdy_g,
-                                       self._dL, p0=p0, p1=p1, pen_lambda=lam, structured=False)
+                                       self._dL, **dict(dict(p0=p0, p1=p1), **self._nl_args()), pen_lambda=lam, structured=False)
         return self._prob
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
@@ -656,7 +688,7 @@ class Nonlinear_elliptic3d(_GPEquation):
 
     def GN_loss(self, z, z_old):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        zz = onp.concatenate([self.alpha * self.m * (z_old ** (self.m - 1)) * (z - z_old), z, self.bdy_g])
+        zz = onp.concatenate([self._tau().dtau(z_old) * (z - z_old), z, self.bdy_g])
         return self._tri_loss(zz)
 
     def Hessian_GN(self, z, z_old):
@@ -666,7 +698,7 @@ class Nonlinear_elliptic3d(_GPEquation):
         sol = self._initial(initial_sol, self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        self.sol_vec = onp.concatenate([self.alpha * (sol ** self.m) - self.rhs_f, sol, self.bdy_g])
+        self.sol_vec = onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g])
         self.sol_sampled_pts = sol
 
     def _fields(self, X_test, which):
@@ -732,7 +764,7 @@ class Nonlinear_elliptic3d(_GPEquation):
         else:
             fields = self._fields(X_test, ('value', 'd1', 'd2', 'laplacian'))  # the rows gpk_pde_residual takes; it reads value and laplacian
         rhs = eval_callback(self.get_rhs, *X_test.T)
-        self.test_residual = get_context().pde_residual(self._system, self._residual_params(), fields, None, rhs).download().reshape(-1)
+        self.test_residual = self._residual(fields, None, rhs)
         return self.test_residual
 
     def boundary_residual(self, X_bt, coeffs_t, g_t):

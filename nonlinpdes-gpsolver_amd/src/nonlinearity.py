@@ -1,0 +1,73 @@
+"""The reaction term tau(u) of the semilinear equation -psi[u] + tau(u) = f and its derivative on the host (numpy): the mirror of
+nl_tau / nl_dtau of csrc/gpk_common.h.  Every host expression of the elliptic classes that involves tau goes through one of these
+objects; the device evaluates the same family (gpk.h, GPK_NL_*).
+
+    power   p0 u^p1                      (alpha u^m: the reference's equation)
+    exp     p0 exp(p1 u)                 Bratu / Liouville
+    sinh    p0 sinh(p1 u)                Poisson-Boltzmann
+    sin     p0 sin(p1 u)                 sine-Gordon
+    cubic   p0 u + p1 u^2 + p2 u^3       Allen-Cahn (-1, 0, 1) / eps^2, Fisher-KPP (-r, r, 0)
+"""
+import numpy as onp
+
+KINDS = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}            # name -> GPK_NL_*
+ARITY = {'power': 2, 'exp': 2, 'sinh': 2, 'sin': 2, 'cubic': 3}
+_FORM = {'power': '{0}*u^{1}', 'exp': '{0}*exp({1}*u)', 'sinh': '{0}*sinh({1}*u)', 'sin': '{0}*sin({1}*u)',
+         'cubic': '{0}*u + {1}*u^2 + {2}*u^3'}
+
+
+class Nonlinearity(object):
+    """tau(u), dtau(u) for numpy arrays; name, kind (GPK_NL_*), params (p0, p1, p2)"""
+
+    def __init__(self, name, *params):
+        if name not in KINDS:
+            raise ValueError(f'nonlinearity {name!r}: one of {tuple(KINDS)}')
+        if len(params) != ARITY[name]:
+            raise ValueError(f'nonlinearity {name!r} takes {ARITY[name]} parameters, got {len(params)}')
+        self.name = name
+        self.kind = KINDS[name]
+        self.raw = tuple(params)                                         # as given (the power law keeps the user's alpha and m untouched)
+        self.params = tuple(float(p) for p in params) + (0.0,) * (3 - len(params))
+
+    @classmethod
+    def power(cls, alpha, m):
+        return cls('power', alpha, m)
+
+    @classmethod
+    def make(cls, spec, alpha=1.0, m=3):
+        """spec: None (the power law alpha u^m), a Nonlinearity, or a sequence (name, parameters...)"""
+        if spec is None:
+            return cls.power(alpha, m)
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str) or not hasattr(spec, '__len__') or len(spec) < 1 or not isinstance(spec[0], str):
+            raise ValueError(f"nonlinearity {spec!r}: None or (name, parameters...), e.g. ('exp', -1.0, 1.0)")
+        return cls(spec[0], *spec[1:])
+
+    def tau(self, u):
+        p0, p1, p2 = self.raw + (0.0,) * (3 - len(self.raw))
+        if self.name == 'power':
+            return p0 * (u ** p1)
+        if self.name == 'exp':
+            return p0 * onp.exp(p1 * u)
+        if self.name == 'sinh':
+            return p0 * onp.sinh(p1 * u)
+        if self.name == 'sin':
+            return p0 * onp.sin(p1 * u)
+        return u * (p0 + u * (p1 + p2 * u))
+
+    def dtau(self, u):
+        p0, p1, p2 = self.raw + (0.0,) * (3 - len(self.raw))
+        if self.name == 'power':
+            return p0 * p1 * (u ** (p1 - 1))
+        if self.name == 'exp':
+            return p0 * p1 * onp.exp(p1 * u)
+        if self.name == 'sinh':
+            return p0 * p1 * onp.cosh(p1 * u)
+        if self.name == 'sin':
+            return p0 * p1 * onp.cos(p1 * u)
+        return p0 + u * (2.0 * p1 + 3.0 * p2 * u)
+
+    def describe(self):
+        """tau(u) as text, e.g. -1.0*exp(1.0*u)"""
+        return _FORM[self.name].format(*self.params)

@@ -5,6 +5,7 @@ import numpy as onp
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
 from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
+from .nonlinearity import Nonlinearity
 
 
 def _operator_of(c):
@@ -22,8 +23,43 @@ def _operator_of(c):
 def _operator_lines(c):
     """header line of a variable-coefficient domain operator (nothing for the Laplacian: the reference's header)"""
     if _operator_of(c) is not None:
+        if _tau_of(c) is not None:
+            return ['[Domain operator] - psi[u] + tau(u) = f, psi a second-order operator with variable coefficients given by the user']
         return ['[Domain operator] - psi[u] + alpha*u^m = f, psi a second-order operator with variable coefficients given by the user']
     return []
+
+
+def _tau_of(c):
+    """cfg.nonlinearity as a Nonlinearity, or None: the power law alpha*u^m of cfg.alpha, cfg.m with the reference's header (absent, None, or
+    the name 'power', which is what a driver's command line leaves there by default)"""
+    spec = getattr(c, 'nonlinearity', None)
+    if spec is None or (isinstance(spec, str) and spec == 'power'):
+        return None
+    return Nonlinearity.make(spec)
+
+
+def _form_line(c, default):
+    """the [Equation form] line: `default` (the reference's text) unless a reaction term is set, which is then named"""
+    tau = _tau_of(c)
+    if tau is None:
+        return default
+    lhs = '- \\Delta u' if _operator_of(c) is None else '- psi[u]'
+    return f'[Equation form] {lhs} + tau(u) = f, tau(u) = {tau.describe()}'
+
+
+def _param_line(c):
+    tau = _tau_of(c)
+    if tau is None:
+        return f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'
+    return f'[Equation parameter] nonlinearity = {tau.name}, parameters = {tau.raw}'
+
+
+def _elliptic_kwargs(c):
+    """constructor arguments both elliptic classes read from the configuration"""
+    kw = dict(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'), robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c))
+    if _tau_of(c) is not None:
+        kw['nonlinearity'] = _tau_of(c)
+    return kw
 
 
 def _time_lines(c):
@@ -48,20 +84,20 @@ _EQUATIONS = {
     'Nonlinear_elliptic': (
         # (cfg.bc / cfg.robin_beta: Neumann / Robin boundary operator; configurations without them are Dirichlet, as in the reference;
         #  cfg.operator: a callable operator(x1, x2) -> six coefficient arrays, or None / absent = the Laplacian, as in the reference)
-        lambda c, **k: Nonlinear_elliptic2d(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'),
-                                            robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c), **k),
-        lambda c: ['[Equation type] Nonlinear elliptic equation', '[Equation form] - \\Delta u + alpha*u^m = f'] + _operator_lines(c)
-        + _bc_lines(c),
-        lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
+        #  cfg.nonlinearity: (name, parameters...) of the reaction term, or None / absent = alpha*u^m, as in the reference
+        lambda c, **k: Nonlinear_elliptic2d(**_elliptic_kwargs(c), **k),
+        lambda c: ['[Equation type] Nonlinear elliptic equation', _form_line(c, '[Equation form] - \\Delta u + alpha*u^m = f')]
+        + _operator_lines(c) + _bc_lines(c),
+        _param_line),
     'Nonlinear_elliptic3d': (
         # (cfg.bc / cfg.robin_beta / cfg.operator as for two dimensions, the callable taking (x1, x2, x3) and returning ten arrays;
         #  cfg.time_dependent: axis 3 is time, auto_sample() places no boundary points on the face x3 = max)
-        lambda c, **k: Nonlinear_elliptic3d(alpha=c.alpha, m=c.m, bc=getattr(c, 'bc', 'dirichlet'),
-                                            robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c), **k),
+        lambda c, **k: Nonlinear_elliptic3d(**_elliptic_kwargs(c), **k),
         lambda c: ['[Equation type] Nonlinear elliptic equation in three space dimensions',
-                   '[Equation form] - \\Delta u + alpha*u^m = f' if _operator_of(c) is None else '[Equation form] - psi[u] + alpha*u^m = f']
+                   _form_line(c, '[Equation form] - \\Delta u + alpha*u^m = f' if _operator_of(c) is None
+                              else '[Equation form] - psi[u] + alpha*u^m = f')]
         + _operator_lines(c) + _time_lines(c) + _bc_lines(c),
-        lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.m}'),
+        _param_line),
     'Burgers': (
         lambda c, **k: Burgers(alpha=c.alpha, nu=c.nu, **k),
         lambda c: ['[Equation type] Burgers equation', '[Equation form] u_t+ alpha u u_x- nu u_xx=0'],
