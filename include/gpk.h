@@ -411,6 +411,49 @@ int gpk_gn_hessian_grad(gpk_handle h, const gpk_gn_problem* host_prob, const dou
 /* measurement vector(s) F(z) = sol_vec (src/PDEs.py:132-134,338-342,488-497; IP.py:176-186): out (s_rows,) */
 int gpk_gn_measurement(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, double* out);
 
+/* ---- Posterior variance of the GP solution at test points, Gauss-Newton / Laplace form ("Posterior variance").
+ *      No reference call site: the reference returns the posterior mean only.  With A = dF/dz at the final iterate z*, L L^T = Theta and
+ *      H/2 = A^T Theta^{-1} A (what gpk_gn_hessian_grad returns, halved; Darcy's data term included),
+ *        var(x) = 1 - ||L^{-1} k_x||^2 + ||L_H^{-1} A^T Theta^{-1} k_x||^2,   L_H L_H^T = H/2,
+ *                 `--- var_cond ----'   `---------- var_gn ----------'
+ *      k_x = the covariances of u(x) with the N collocation functionals (k(x,x) = 1 for both kernels).  The value functional only; the
+ *      five reference layouts; GPK_GN_ELLIPTIC_RELAXED is not served (-9001).  Bad arguments: -9001, named in gpk_last_error. */
+/* The block of gpk_assemble_test transposed: out is N x Nt row-major, ld >= Nt, out[c * ld + t] = Theta_test[t, c] -- the layout
+ * gpk_trsm / gpk_trsm_dinv take as B, so no transpose pass exists anywhere.  Any alignment of out / ld is accepted (16-byte stores
+ * when base, ld and Nt allow; 8-byte stores otherwise, with the same values); nothing outside the N x Nt view is written.  The launch is
+ * not part of the per-phase timing: gpk_prof_read_assembly keeps reporting the last Gram launch. */
+int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const double* host_kparams,
+                       const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
+                       double* out, int ld);
+/* out[t] = (base ? base[t] : 0) + alpha * sum_r V[r, t]^2 for the rows x cols view V (ld ldv >= cols); base may be out.  One pass over
+ * V; the rows are cut into a number of slabs that depends on (rows, cols) only and the partial sums are added in slab order: no
+ * atomics, a repeated call gives bit-identical output.  Uses the handle's workspace for the partial sums. */
+int gpk_col_sumsq(gpk_handle h, const double* V, int rows, int cols, int ldv, double alpha, const double* base, double* out);
+/* Workspace query (pure host function) for the two calls below with batches of nt test points.  ldp / ldr / ldk: the leading dimensions
+ * the caller intends to use for P / R / K and W (0 = the smallest admissible one -- nz + 1, nz, nt -- rounded up to 16 doubles; returned
+ * in *host_ld*).  *P_bytes = s_rows * ldp * 8, *R_bytes = nz * ldr * 8, *K_bytes = (rows of the largest field) * ldk * 8, *W_bytes =
+ * nz * ldk * 8, *handle_bytes = what the two calls ask of the handle's workspace, computed by the functions they size it with: the
+ * larger of prepare's [A | F] block (s_rows * ldp * 8, when every factor comes with its inverted diagonal blocks) and variance's
+ * out-of-place V (N_field * ldk * 8, when the field's factor has them) plus the partial sums of the reductions; 0 inverted blocks: the
+ * partial sums alone.  Any output pointer may be NULL. */
+int gpk_posterior_worksize(const gpk_gn_problem* host_prob, int nt, int ldp, int ldr, int ldk, int* host_ldp, int* host_ldr,
+                           int* host_ldk, size_t* P_bytes, size_t* R_bytes, size_t* K_bytes, size_t* W_bytes, size_t* handle_bytes);
+/* Once per converged iterate z:  P <- L^{-1} A(z) (s_rows x nz in the natural column order of gpk_gn_build, every row group solved with
+ * its own factor, the rows without a factor copied; ld ldp >= nz + 1 -- column nz is scratch),  R <- the lower Cholesky factor of
+ * H/2 (nz x nz, ld ldr >= nz; strict upper triangle unspecified, as gpk_potrf).  H/2 is formed as P^T P with Darcy's data rows
+ * (1 / gamma, no factor) kept in P: the product gpk_gn_hessian_grad issues, without its border column and its factor 2.  The solve
+ * takes gpk_gn_hessian_grad's path: GEMMs only when every factor comes with its inverted diagonal blocks, substitution otherwise.
+ * host_info as gpk_potrf. */
+int gpk_posterior_prepare(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, double* P, int ldp, double* R, int ldr,
+                          int* host_info);
+/* One batch of nt test points.  field: 0 = u, 1 = a (GPK_GN_DARCY only: factor L2, the a-rows of P; anything else -9001).  K: N_field x
+ * nt from gpk_assemble_cross (ld ldk >= nt), OVERWRITTEN;  W: nz x nt scratch (ld ldw >= nt).
+ *   V = L_field^{-1} K;  var_cond[t] = 1 - sum_r V[r,t]^2;  W = P_field^T V;  W <- R^{-1} W;  var[t] = var_cond[t] + sum_r W[r,t]^2.
+ * var_cond, var: (nt,) on the device, either may be NULL (var == NULL: steps 3-5 are skipped and P, R, W are not read).  Raw values,
+ * nothing is clipped. */
+int gpk_posterior_variance(gpk_handle h, const gpk_gn_problem* host_prob, const double* P, int ldp, const double* R, int ldr, int field,
+                           double* K, int ldk, int nt, double* W, int ldw, double* var_cond, double* var);
+
 /* Development switches, phase stamps, probes and the micro-benchmarks behind the roofline denominators: include/gpk_debug.h. */
 
 #ifdef __cplusplus

@@ -51,6 +51,9 @@ int gpk_debug_syrk_lz(gpk_handle h, int n, int k, double alpha, const double* A,
  * null) the a-part's closed form on the columns [N_d, 4 N_d), 3 N_d elsewhere.  Returns the layout (1 elliptic systems, 2 Eikonal,
  * 3 Burgers, 4 Darcy); a problem on the dense schedule is refused. */
 int gpk_debug_first_rows(gpk_handle h, const gpk_gn_problem* host_prob, int* out_u, int* out_a);
+/* *host_bytes = current size of the handle's workspace (gpk_i_workspace: the out-of-place solve buffers, partial sums of gpk_col_sumsq): what
+ * tests hold against the handle_bytes of gpk_gn_worksize / gpk_posterior_worksize. */
+int gpk_debug_workspace_bytes(gpk_handle h, size_t* host_bytes);
 
 #ifdef __cplusplus
 }

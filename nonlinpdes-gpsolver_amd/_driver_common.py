@@ -27,6 +27,8 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     parser.add_argument("--show_figure", type=bool, default=True)
     # opt-in: also print the PDE residual of the solution on the test grid (no truth solution needed)
     parser.add_argument("--test_residual", type=bool, default=False)
+    # opt-in: also print the posterior standard deviation of the solution on the test grid (Gauss-Newton / Laplace form)
+    parser.add_argument("--test_variance", type=bool, default=False)
 
 
 NL_DEFAULTS = {'exp': (-1.0, 1.0), 'sinh': (1.0, 1.0), 'sin': (1.0, 1.0), 'cubic': (-1.0, 0.0, 1.0)}
@@ -120,3 +122,9 @@ def report_test_residual(cfg, solver, X_test):
     """--test_residual: the residual of the equation on the driver's test grid (solver_GP.test_residual)"""
     if cfg.test_residual:
         solver.test_residual(X_test)
+
+
+def report_test_variance(cfg, solver, X_test):
+    """--test_variance: the posterior standard deviation of the solution on the driver's test grid (solver_GP.test_variance)"""
+    if cfg.test_variance:
+        solver.test_variance(X_test)

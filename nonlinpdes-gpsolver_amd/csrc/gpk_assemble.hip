@@ -183,6 +183,50 @@ __global__ __launch_bounds__(256) void assemble_test_kernel(AsmArgs g) {
     }
 }
 
+// cross-covariance columns (gpk_assemble_cross): the entries of assemble_test_kernel, transposed -- out[(off[BJ] + p) * ld + t] for the
+// column point p of block BJ and the test point t.  Lanes run along t, two test points per lane (t, t + 1): for a fixed (block, column
+// point) a wave stores 1 KB contiguous with the 16-byte store (WIDE: base and ld even, Nt even), or the same two values as two
+// 8-byte stores (any alignment, odd Nt).  One kernel body for both: the values are the same bits either way.  The column point is
+// wave-uniform (scalar loads), and one exp + one pair of Hermite evaluations per point pair feeds every block of the layout.
+constexpr int CROSS_TP = 8;               // column points per workgroup: the grid is N_t / 512 wide, so the rows supply the parallelism
+
+template <int L, int BJ, bool WIDE>
+__device__ __forceinline__ void store_cross(const AsmArgs& g, int p, int t, const double (&a0)[5], const double (&b0)[5], double e0,
+                                            const double (&a1)[5], const double (&b1)[5], double e1) {
+    if (p < g.size[BJ]) {                               // wave-uniform
+        const double v0 = pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a0, b0) * e0;
+        const double v1 = pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a1, b1) * e1;
+        double* const dst = g.out + (long)(g.off[BJ] + p) * g.ld + t;
+        if constexpr (WIDE) store2<0>(dst, v0, v1);
+        else { dst[0] = v0; if (t + 1 < g.Nt) dst[1] = v1; }
+    }
+}
+
+template <int L, bool WIDE>
+__global__ __launch_bounds__(256) void assemble_cross_kernel(AsmArgs g) {
+    const int t = 2 * (blockIdx.x * 256 + threadIdx.x);
+    const bool live = t < g.Nt;
+    const int tb = min(t + 1, g.Nt - 1);                // odd Nt: the last lane computes its point twice and stores it once
+    const double x1a = live ? g.tx[2 * t] : 0.0, x2a = live ? g.tx[2 * t + 1] : 0.0;
+    const double x1b = live ? g.tx[2 * tb] : 0.0, x2b = live ? g.tx[2 * tb + 1] : 0.0;
+    const int p0 = blockIdx.y * CROSS_TP;
+    const int pend = min(p0 + CROSS_TP, g.M);
+    for (int p = p0; p < pend; ++p) {
+        const double y1 = g.px[p], y2 = g.py[p];        // uniform address -> scalar loads
+        if (!live) continue;
+        const double d1a = x1a - y1, d2a = x2a - y2, d1b = x1b - y1, d2b = x2b - y2;
+        const double e0 = exp(-0.5 * (g.p1 * d1a * d1a + g.p2 * d2a * d2a));
+        const double e1 = exp(-0.5 * (g.p1 * d1b * d1b + g.p2 * d2b * d2b));
+        double a0[5], b0[5], a1[5], b1[5];
+        hermite_plain(g.p1, d1a, a0); hermite_plain(g.p2, d2a, b0);
+        hermite_plain(g.p1, d1b, a1); hermite_plain(g.p2, d2b, b1);
+        store_cross<L, 0, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
+        if (Lay<L>::nb > 1) store_cross<L, 1, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
+        if (Lay<L>::nb > 2) store_cross<L, 2, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
+        if (Lay<L>::nb > 3) store_cross<L, 3, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
+    }
+}
+
 template <int L, int BJ>
 __device__ __forceinline__ double acc_test(const AsmArgs& g, int q, const double (&a)[5], const double (&b)[5]) {
     return (q < g.size[BJ]) ? pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a, b) * g.coeff[g.off[BJ] + q] : 0.0;
@@ -411,6 +455,28 @@ extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const dou
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
     with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+// The block of gpk_assemble_test, transposed: N x Nt, the right-hand-side layout of gpk_trsm / gpk_trsm_dinv (gpk.h, "Posterior variance").
+// It lives here, not in gpk_posterior.hip, because Lay<L>, the plain pair_coeff and fill_common are this file's.
+extern "C" int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const double* kp, const double* Xt, int Nt,
+                                  const double* Xd, int Nd, const double* Xb, int Nb, double* out, int ld) {
+    if (!h) return GPK_ERR_ARG;
+    if (!out || !Xt) return gpk_bad_arg(h, "assemble_cross: pointers");
+    if (Nt <= 0) return gpk_bad_arg(h, "assemble_cross: Nt <= 0");
+    if (ld < Nt) return gpk_bad_arg(h, "assemble_cross: ld < Nt");
+    AsmArgs g{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
+    const bool wide = pairs_eligible(h, out, ld, Nt);
+    const dim3 grid(gpk_ceil_div(gpk_ceil_div(Nt, 2), 256), gpk_ceil_div(g.M, CROSS_TP));
+    with_layout(layout, [&](auto l) {                                // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
+        constexpr int L = decltype(l)::value;
+        if (wide) assemble_cross_kernel<L, true><<<grid, 256, 0, h->stream>>>(g);
+        else assemble_cross_kernel<L, false><<<grid, 256, 0, h->stream>>>(g);
+    });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

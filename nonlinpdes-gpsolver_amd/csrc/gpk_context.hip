@@ -333,6 +333,14 @@ int gpk_i_splitk_reserve(gpk_handle h) {
     return 0;
 }
 
+#ifdef GPK_DEV
+extern "C" int gpk_debug_workspace_bytes(gpk_handle h, size_t* host_bytes) {
+    if (!h || !host_bytes) return GPK_ERR_ARG;
+    *host_bytes = h->work_cap;
+    return 0;
+}
+#endif
+
 int gpk_i_workspace(gpk_handle h, size_t bytes, double** out) {
     if (h->work_cap < bytes) {
         GPK_HIP(h, hipStreamSynchronize(h->stream));

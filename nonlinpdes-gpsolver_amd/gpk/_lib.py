@@ -120,6 +120,11 @@ PROTOTYPES = {
     'gpk_gn_loss': (_i, [_vp, _pp, _vp, _vp, _pd]),
     'gpk_gn_hessian_grad': (_i, [_vp, _pp, _vp, _vp, _i, _vp, _i, _vp]),
     'gpk_gn_measurement': (_i, [_vp, _pp, _vp, _vp]),
+    'gpk_assemble_cross': (_i, [_vp, _i, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_col_sumsq': (_i, [_vp, _vp, _i, _i, _i, _d, _vp, _vp]),
+    'gpk_posterior_worksize': (_i, [_pp, _i, _i, _i, _i, _pi, _pi, _pi] + [C.POINTER(_sz)] * 5),
+    'gpk_posterior_prepare': (_i, [_vp, _pp, _vp, _vp, _i, _vp, _i, _pi]),
+    'gpk_posterior_variance': (_i, [_vp, _pp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
     'gpk_tune': (_i, [_vp, _i, _i]),
 }
 
@@ -136,6 +141,7 @@ DEV_PROTOTYPES = {
     'gpk_debug_set_profile': (_i, [_vp, _i, _i, _pi, _pi, _pi, _pi, _i]),
     'gpk_debug_syrk_lz': (_i, [_vp, _i, _i, _d, _vp, _i, _d, _vp, _i, _i]),
     'gpk_debug_first_rows': (_i, [_vp, _pp, _pi, _pi]),
+    'gpk_debug_workspace_bytes': (_i, [_vp, C.POINTER(_sz)]),
 }
 
 _lib = None

@@ -623,6 +623,91 @@ class Context:
         self.synchronize()
         return work.download()
 
+    # ---- posterior variance (gpk_assemble_cross, gpk_col_sumsq, gpk_posterior_prepare, gpk_posterior_variance) ----
+    def assemble_cross(self, layout, kernel, kernel_parameter, Xt, Xd, Xb, out=None):
+        """Cross-covariances of u at the test points Xt with the N collocation functionals of `layout`: the block of assemble_test
+        transposed, an (N, Nt) DeviceArray -- the right-hand-side layout of trsm / trsm_dinv.  out: a DeviceArray to write into
+        (rows >= N, leading dimension >= Nt)."""
+        Xt, Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 2) for X in (Xt, Xd, Xb))
+        Nt, Nd, Nb = Xt.shape[0], Xd.shape[0], Xb.shape[0]
+        dXt, dXd, dXb = self.points(Xt), self.points(Xd), self.points(Xb)
+        lay = LAYOUT[layout]
+        N = {0: 2 * Nd + Nb, 1: 4 * Nd + Nb, 2: 4 * Nd + Nb, 3: 3 * Nd}[lay]
+        K = out if out is not None else DeviceArray(self, N, Nt)
+        self._chk(self.lib.gpk_assemble_cross(self.h, lay, KERNEL[kernel], kernel_params(kernel, kernel_parameter),
+                                              dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, K.ptr, K.ld))
+        self.synchronize()
+        return K
+
+    def col_sumsq(self, V, alpha=1.0, base=None, rows=None, cols=None):
+        """(cols,) DeviceArray: base + alpha * column sums of squares of the DeviceArray V (gpk_col_sumsq; base: DeviceArray or None)"""
+        rows = V.rows if rows is None else rows
+        cols = V.cols if cols is None else cols
+        out = DeviceArray(self, cols)
+        self._chk(self.lib.gpk_col_sumsq(self.h, V.ptr, rows, cols, V.ld, float(alpha), base.ptr if base is not None else None, out.ptr))
+        return out
+
+    def posterior_worksize(self, prob, nt, ldp=0, ldr=0, ldk=0):
+        """gpk_posterior_worksize for batches of nt test points: dict with the leading dimensions ldp, ldr, ldk (0 = the smallest
+        admissible, padded) and P_bytes, R_bytes, K_bytes, W_bytes, handle_bytes.  Pure host query."""
+        ld = [C.c_int() for _ in range(3)]
+        sz = [C.c_size_t() for _ in range(5)]
+        rc = self.lib.gpk_posterior_worksize(C.byref(prob.struct), int(nt), int(ldp), int(ldr), int(ldk),
+                                             *[C.byref(x) for x in ld], *[C.byref(x) for x in sz])
+        if rc != 0:                                                       # (a host function: it leaves no text in gpk_last_error)
+            raise GpkError(f'libgpk error {rc}: gpk_posterior_worksize rejected the problem or the sizes (the relaxed elliptic system '
+                           'is not served; nt > 0; leading dimensions at least nz + 1, nz, nt)')
+        return dict(zip(('ldp', 'ldr', 'ldk', 'P_bytes', 'R_bytes', 'K_bytes', 'W_bytes', 'handle_bytes'), [x.value for x in ld + sz]))
+
+    def posterior_prepare(self, prob, z):
+        """Once per converged iterate z (DeviceArray): (P, R, info) with P = L^{-1} A(z) and R the Cholesky factor of H/2
+        (gpk_posterior_prepare); info as potrf.  Buffers as gpk_posterior_worksize sizes them."""
+        ws = self.posterior_worksize(prob, 1)
+        P = DeviceArray(self, prob.rows, prob.nz + 1, ld=ws['ldp'])
+        R = DeviceArray(self, prob.nz, prob.nz, ld=ws['ldr'])
+        info = C.c_int()
+        self._chk(self.lib.gpk_posterior_prepare(self.h, C.byref(prob.struct), z.ptr, P.ptr, P.ld, R.ptr, R.ld, C.byref(info)))
+        return P, R, self._chk_info(info.value)
+
+    def posterior_variance(self, prob, P, R, K, field=0, nt=None, W=None, want_cond=True, want_var=True):
+        """One batch of test points: K (N_field, nt) from assemble_cross is overwritten; returns (var_cond, var) as (nt,) DeviceArrays
+        (None where not asked for) -- gpk_posterior_variance.  field: 0 = u, 1 = a (Darcy only).  W: (nz, >= nt) scratch."""
+        nt = K.cols if nt is None else int(nt)
+        if W is None and want_var:
+            W = DeviceArray(self, prob.nz, nt)
+        vc = DeviceArray(self, nt) if want_cond else None
+        v = DeviceArray(self, nt) if want_var else None
+        self._chk(self.lib.gpk_posterior_variance(self.h, C.byref(prob.struct), P.ptr if P is not None else None, P.ld if P is not None else 0,
+                                                  R.ptr if R is not None else None, R.ld if R is not None else 0, int(field),
+                                                  K.ptr, K.ld, nt, W.ptr if W is not None else None, W.ld if W is not None else 0,
+                                                  vc.ptr if vc is not None else None, v.ptr if v is not None else None))
+        return vc, v
+
+    def posterior_variance_points(self, prob, P, R, field, layout, kernel, kernel_parameter, X_test, Xd, Xb, nt_chunk=1024):
+        """(var_cond, var) as numpy arrays at all of X_test, in batches of nt_chunk points: one K (N_field x nt_chunk) and one W
+        (nz x nt_chunk) buffer serve every batch, so the workspace does not grow with the number of test points."""
+        X_test = np.ascontiguousarray(X_test, dtype=np.float64).reshape(-1, 2)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nt, Nd, Nb = X_test.shape[0], np.asarray(Xd).shape[0], Xb.shape[0]
+        nt_chunk = max(1, min(int(nt_chunk), Nt))
+        lay = LAYOUT[layout]
+        N = {0: 2 * Nd + Nb, 1: 4 * Nd + Nb, 2: 4 * Nd + Nb, 3: 3 * Nd}[lay]
+        dXt, dXd, dXb = self.points(X_test), self.points(Xd), self.points(Xb)
+        ldk = self.posterior_worksize(prob, nt_chunk)['ldk']
+        K, W = DeviceArray(self, N, nt_chunk, ld=ldk), DeviceArray(self, prob.nz, nt_chunk, ld=ldk)
+        vc, v = DeviceArray(self, Nt), DeviceArray(self, Nt)
+        kp = kernel_params(kernel, kernel_parameter)
+        for t0 in range(0, Nt, nt_chunk):
+            nt = min(nt_chunk, Nt - t0)
+            self._chk(self.lib.gpk_assemble_cross(self.h, lay, KERNEL[kernel], kp, dXt.at(t0), nt, dXd.ptr, Nd, dXb.ptr, Nb, K.ptr, K.ld))
+            self._chk(self.lib.gpk_posterior_variance(self.h, C.byref(prob.struct), P.ptr, P.ld, R.ptr, R.ld, int(field), K.ptr, K.ld, nt,
+                                                      W.ptr, W.ld, vc.ptr + 8 * t0, v.ptr + 8 * t0))
+        self.synchronize()
+        out = vc.download(), v.download()
+        for a in (K, W, vc, v, dXt, dXd, dXb):
+            a.free()
+        return out
+
     # ---- per-phase timing of gn_step ----
     def prof_enable(self, on=True):
         self._chk(self.lib.gpk_prof_enable(self.h, int(on)))

@@ -44,6 +44,7 @@ class Darcy_flow2d(_GPEquation):
         self.data_u = data_u + noise_level * random.normal(0, 1.0, onp.shape(data_u)[0])
         self.noise_level = noise_level
         self.__dict__.pop('_prob', None)
+        self._drop_posterior()
 
     # ---- device state --------------------------------------------------------------------------------------------------
     def _drop_device_state(self):
@@ -56,6 +57,8 @@ class Darcy_flow2d(_GPEquation):
             p.free()                                           # (workspace, inverted blocks, prepared operators: everything but the factors)
         for name in ('_Theta_u_host', '_Theta_a_host', '_L_u_host', '_L_a_host'):
             self.__dict__.pop(name, None)
+        self._drop_posterior()
+        self.__dict__.pop('_z_star', None)
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-10, nugget_type='adaptive'):
         if nugget_type not in ('adaptive', 'identity', 'none'):
@@ -159,3 +162,20 @@ class Darcy_flow2d(_GPEquation):
 
     def _residual_params(self):
         return None
+
+    # ---- posterior variance of both fields (src/PDEs.py, _GPEquation): u with Theta_u and the u-rows of A, a with Theta_a and the a-rows;
+    # one H/2 of all 6 N_domain unknowns, data term included --------------------------------------------------------------------------
+    _posterior_fields = (('_u', 0, 'Darcy_u'), ('_a', 1, 'Darcy_a'))
+
+    def posterior_variance(self, X_test, nt_chunk=1024):
+        """Posterior variance of u and of the log-permeability a at X_test, Gauss-Newton (Laplace) form at the final iterate of
+        GN_method (see _GPEquation.posterior_variance).  Sets extended_var_u, extended_var_a, their _cond companions (raw values) and
+        extended_std_u / extended_std_a = sqrt(max(var, 0)); returns (extended_var_u, extended_var_a).  The values of the two fields
+        only.  No attribute of extend_sol or GN_method is touched."""
+        res = self._posterior_compute(X_test, nt_chunk)
+        for tag in ('_u', '_a'):
+            vc, v = res[tag]
+            setattr(self, 'extended_var_cond' + tag, vc)
+            setattr(self, 'extended_var' + tag, v)
+            setattr(self, 'extended_std' + tag, onp.sqrt(onp.maximum(v, 0.0)))
+        return self.extended_var_u, self.extended_var_a

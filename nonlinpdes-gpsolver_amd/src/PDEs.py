@@ -93,6 +93,15 @@ class _GPEquation(object):
             p.free()                                           # (workspace, inverted blocks, prepared operators: everything but the factors)
         self.__dict__.pop('_Theta_host', None)
         self.__dict__.pop('_L_host', None)
+        self._drop_posterior()
+        self.__dict__.pop('_z_star', None)
+
+    def _drop_posterior(self):
+        """free what posterior_variance prepared (P = L^{-1} A(z*), the factor of H/2): it belongs to one iterate of one problem"""
+        st = self.__dict__.pop('_posterior', None)
+        if st is not None:
+            for a in st[:2]:
+                a.free()
 
     def _n_unknowns(self):
         return self._blocks_per_point * self.N_domain
@@ -218,6 +227,7 @@ class _GPEquation(object):
 
     def _gn_iterate(self, prob, sol, max_iter, step_size, print_hist, check_nan=True):
         self.step_info = []
+        self._drop_posterior()
         ctx = get_context()
         z = ctx.array(sol)
         loss_hist = []
@@ -252,7 +262,8 @@ class _GPEquation(object):
         self.max_iter = max_iter
         self.step_size = step_size
         self.loss_hist = loss_hist
-        return z.download()
+        self._z_star = (prob, z.download())                   # the final iterate and the system it belongs to (posterior_variance)
+        return self._z_star[1]
 
     def extend_sol(self, X_test):
         ctx = get_context()
@@ -310,6 +321,61 @@ class _GPEquation(object):
         self.test_residual = self._residual(fields['u'], fields.get('a'), rhs)
         return self.test_residual
 
+    # ---- posterior variance of the solution at test points (gpk_posterior_prepare, gpk_assemble_cross, gpk_posterior_variance) -------
+    _posterior_fields = (('', 0, None),)                        # (attribute suffix, field id, Gram layout or None = self._layout)
+
+    def _posterior_unserved(self):
+        """why posterior_variance is not available for this object, or None"""
+        return None
+
+    def _posterior_state(self):
+        """(P, R, info, prob): prepared once per final iterate, dropped with the device state and at the next GN_method"""
+        reason = self._posterior_unserved()
+        if reason is not None:
+            raise NotImplementedError('posterior_variance: ' + reason)
+        star = self.__dict__.get('_z_star')
+        if star is None:
+            raise RuntimeError('posterior_variance: call GN_method() first')
+        prob, z = star
+        if prob.struct.system == gpk.SYSTEM['Nonlinear_elliptic_relaxed']:
+            raise NotImplementedError('posterior_variance: the relaxed formulation (GN_relaxed_method) has no variance entry point '
+                                      '(gpk_posterior_prepare returns -9001 for GPK_GN_ELLIPTIC_RELAXED); solve with GN_method')
+        if self.__dict__.get('_posterior') is None:
+            ctx = get_context()
+            dz = ctx.array(z)
+            P, R, info = ctx.posterior_prepare(prob, dz)
+            dz.free()
+            if info != 0:
+                print('[Warning] Cholesky factorization of the Gauss-Newton matrix at the final iterate met a non-positive pivot at index',
+                      info, ': the posterior variance is not defined there')
+            self._posterior = (P, R, info, prob)
+        return self._posterior
+
+    def _posterior_compute(self, X_test, nt_chunk):
+        """{suffix: (var_cond, var)} as numpy arrays for every field of the equation"""
+        P, R, _, prob = self._posterior_state()
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        out = {}
+        for tag, field, layout in self._posterior_fields:
+            out[tag] = get_context().posterior_variance_points(prob, P, R, field, layout or self._layout, self.kernel, self.kernel_parameter,
+                                                               X_test, self.X_domain, self.X_boundary, nt_chunk)
+        return out
+
+    def posterior_variance(self, X_test, nt_chunk=1024):
+        """Posterior variance of the GP solution u at X_test, Gauss-Newton (Laplace) form at the final iterate of GN_method:
+        var = var_cond + var_gn with var_cond = k(x,x) - k^T Theta^{-1} k (the collocation values taken as known) and var_gn the
+        contribution of their own covariance (A^T Theta^{-1} A)^{-1}.  Sets extended_var, extended_var_cond (raw values: rounding can leave
+        either slightly negative where the variance is at the nugget level) and extended_std = sqrt(max(extended_var, 0)); returns
+        extended_var.  X_test is processed in batches of nt_chunk points, so the workspace is (N + n_z) * nt_chunk doubles whatever
+        the number of test points.  The value of u only; Nonlinear_elliptic2d (Dirichlet data, the Laplacian, any nonlinearity),
+        Burgers, Eikonal and Darcy_flow2d -- NotImplementedError with bc / operator set, for Nonlinear_elliptic3d and after
+        GN_relaxed_method.  No attribute of extend_sol or GN_method is touched."""
+        vc, v = self._posterior_compute(X_test, nt_chunk)['']
+        self.extended_var_cond = vc
+        self.extended_var = v
+        self.extended_std = onp.sqrt(onp.maximum(v, 0.0))
+        return self.extended_var
+
 
 class Nonlinear_elliptic2d(_GPEquation):
     """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208); with operator=... / set_domain_operator() the semilinear
@@ -355,6 +421,15 @@ class Nonlinear_elliptic2d(_GPEquation):
     def _tau(self):
         """the reaction term: the one given, or the power law of the current alpha, m"""
         return self.nonlinearity if self.nonlinearity is not None else Nonlinearity.power(self.alpha, self.m)
+
+    def _posterior_unserved(self):
+        if self.bc != 'dirichlet' or self.boundary_coeffs is not None:
+            return ('boundary functionals (bc / set_boundary_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
+                    'gpk_assemble_bc yet')
+        if self.operator is not None or self.domain_coeffs is not None:
+            return ('domain operator (operator / set_domain_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
+                    'gpk_assemble_op yet')
+        return None
 
     # ---- boundary operator: (N_boundary, 3) coefficients (c0, c1, c2) of c0 u + c1 u_x1 + c2 u_x2, or None = Dirichlet, today's path ----
     def _set_points(self, X_domain, X_boundary):
@@ -585,6 +660,9 @@ class Nonlinear_elliptic3d(_GPEquation):
         self.nonlinearity = None if nonlinearity is None else Nonlinearity.make(nonlinearity)
 
     _tau = Nonlinear_elliptic2d._tau
+
+    def _posterior_unserved(self):
+        return 'Nonlinear_elliptic3d: gpk_assemble_cross has no rectangular evaluator for the three-dimensional layouts yet'
 
     def get_bd(self, x1, x2, x3):
         return self.bdy(x1, x2, x3)

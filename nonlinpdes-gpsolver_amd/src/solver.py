@@ -141,6 +141,9 @@ _LOG = {
     'res_n': '[Testing PDE residual...] Number of test points: {n}',
     'res_max': '[Test residual] Max residual {v}',
     'res_l2': '[Test residual] L2 residual {v}',
+    'var_n': '[Testing posterior variance...] Number of test points: {n}',
+    'var_mean': '[Test variance] Mean posterior std{tag} {v}',
+    'var_max': '[Test variance] Max posterior std{tag} {v}',
 }
 
 
@@ -246,6 +249,21 @@ class solver_GP(object):
         _, self.test_res_max, self.test_res_L2 = get_context().error_metrics(onp.zeros(r.size), r)
         _say(print_option, 'res_max', v=self.test_res_max)
         _say(print_option, 'res_l2', v=self.test_res_L2)
+
+    def test_variance(self, X_test, print_option=True):
+        """The error bar of the GP solution between the collocation points: its posterior standard deviation at X_test in the
+        Gauss-Newton (Laplace) form (eqn.posterior_variance), reduced to mean and maximum.  Darcy flow: both fields u and a."""
+        _say(print_option, 'var_n', n=X_test.shape[0])
+        self.eqn.posterior_variance(X_test)
+        self.test_std_mean, self.test_std_max = {}, {}
+        for tag in ('', '_u', '_a'):
+            std = getattr(self.eqn, 'extended_std' + tag, None)
+            if std is None:
+                continue
+            self.test_std_mean[tag], self.test_std_max[tag] = float(onp.mean(std)), float(onp.max(std))
+            label = ' of ' + tag[1:] if tag else ''
+            _say(print_option, 'var_mean', tag=label, v=self.test_std_mean[tag])
+            _say(print_option, 'var_max', tag=label, v=self.test_std_max[tag])
 
     # ---- figures (cosmetic; need matplotlib only): src/_figures.py ---------------------------------------------------------
     def _planar_only(self):
