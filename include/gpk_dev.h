@@ -51,6 +51,11 @@ int gpk_debug_syrk_lz(gpk_handle h, int n, int k, double alpha, const double* A,
  * null) the a-part's closed form on the columns [N_d, 4 N_d), 3 N_d elsewhere.  Returns the layout (1 elliptic systems, 2 Eikonal,
  * 3 Burgers, 4 Darcy); a problem on the dense schedule is refused. */
 int gpk_debug_first_rows(gpk_handle h, const gpk_gn_problem* host_prob, int* out_u, int* out_a);
+/* Which way gpk_gn_step would run host_prob on this handle, without running it: *mode = 0 plain solve, 1 structured solve of the elliptic
+ * system, 2 its Gram level, 3 structured solve of the Burgers / Eikonal / Darcy systems, 4 their Gram level; *product = what follows the
+ * mode: 0 nothing (the Gram levels factor the bordered matrix themselves), 1 the pipelined product + Cholesky, 2 Darcy's two-factor
+ * product.  Nothing is launched and no device pointer is dereferenced. */
+int gpk_debug_step_mode(gpk_handle h, const gpk_gn_problem* host_prob, int* mode, int* product);
 /* *host_bytes = current size of the handle's workspace (gpk_i_workspace: the out-of-place solve buffers, partial sums of gpk_col_sumsq): what
  * tests hold against the handle_bytes of gpk_gn_worksize / gpk_posterior_worksize. */
 int gpk_debug_workspace_bytes(gpk_handle h, size_t* host_bytes);

@@ -46,3 +46,16 @@ extern "C" int gpk_debug_first_rows(gpk_handle h, const gpk_gn_problem* p, int* 
     }
     return rev;
 }
+
+// The mode gpk_gn_step would run host_prob in and the product that follows it, as ints in the order of StepMode / StepProduct (gpk_gn.hip).
+// Asks the step's own selector after the step's own checks; launches nothing and dereferences no device pointer.
+extern "C" int gpk_debug_step_mode(gpk_handle h, const gpk_gn_problem* p, int* mode, int* product) {
+    if (!h || !mode || !product) return GPK_ERR_ARG;
+    Dims d;
+    GPK_TRY(check_prob(h, p, d));
+    const int rev = step_layout(h, p);
+    const StepMode m = select_mode(h, p, d, rev);
+    *mode = (int)m;
+    *product = (int)select_product(m, rev);
+    return 0;
+}

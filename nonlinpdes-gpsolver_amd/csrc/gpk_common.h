@@ -154,7 +154,7 @@ struct GpkTune {
                                         // 0 = the squared norm of the F column of the GEMM-only solve (free, ~1e-8 relative error at nugget <= 1e-12 near convergence; rounds 2-4).
                                         // Measured and lost: the chain next to the SOLVE phase -- on the 32-CU chain partition beside whole-chip GEMM launches the solve grows by
                                         // 0.67 ms, with the first solve launches moved to the 224-CU partition meanwhile by 0.63 ms (the chain alone takes 0.93 ms on 32 CUs)
-    int structured = 1;                 // key 40: 0 = ignore W1/W2/v0 (always the triangular solve); 1 = honour W1/W2/v0 only (never the Gram blocks); 2 would be redundant: the Gram level is used whenever G/pvec are set
+    int structured = 1;                 // key 40: 0 = ignore everything prepared (always the triangular solve); non-zero = honour what has been prepared: W1/W2/v0, and the Gram level whenever G is set as well
 };
 
 struct gpk_ctx {
@@ -317,6 +317,7 @@ int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, cons
                     double* z, double step_size);
 
 static inline int gpk_ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline bool dinv_block_ok(int db) { return db == 256 || db == 512 || db == 1024 || db == 2048; }   // block sizes of gpk_i_trtri_diag / gpk_i_trsm_left_dinv
 
 // Reaction term tau(u) of the elliptic systems and its derivative (gpk.h, GPK_NL_*; DESIGN.md section K, "Reaction terms").  The one
 // place that knows the family: gn_build_kernel, structured_coeff_kernel and pde_residual_nl_kernel call it.  GPK_NL_POWER spells

@@ -1098,8 +1098,6 @@ __global__ void dinv_identity_kernel(double* __restrict__ D, int n, int db) {
     if (i < (long)n * db) D[i] = ((i / db) % db == i % db) ? 1.0 : 0.0;
 }
 
-inline bool dinv_block_ok(int db) { return db == 256 || db == 512 || db == 1024 || db == 2048; }
-
 int gpk_i_trtri_diag(gpk_handle h, const double* L, int n, int ldl, double* Dinv, int db) {
     if (n <= 0) return 0;
     if (!dinv_block_ok(db)) return gpk_bad_arg(h, "trtri_diag: block size must be 256, 512, 1024 or 2048");

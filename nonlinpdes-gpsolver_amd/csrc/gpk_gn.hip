@@ -45,6 +45,13 @@ int gn_dims(const gpk_gn_problem* p, Dims& d) {
     return 0;
 }
 
+// the GEMM-only solve is available: there is a factored row group and every one comes with its inverted diagonal blocks
+bool every_factor_has_dinv(const Dims& d) {
+    bool any = false;
+    for (int k = 0; k < d.ngroups; ++k) if (d.g[k].L) { if (!d.g[k].Dinv) return false; any = true; }
+    return any;
+}
+
 struct BuildArgs {
     int system, Nd, Nb, Ndata;
     double p0, p1, lam;
@@ -353,11 +360,9 @@ GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
     return (rev >= 1 && rev <= 3) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
-// every factored row group comes with its inverted diagonal blocks (the GEMM-only solve path is available)
+// the GEMM-only solve path is available and switched on, with the block size given (the structured modes of the other systems need it)
 bool all_dinv(gpk_handle h, const gpk_gn_problem* p, const Dims& d) {
-    if (!h->tune.use_dinv || p->dinv_block <= 0) return false;
-    for (int k = 0; k < d.ngroups; ++k) if (d.g[k].L && !d.g[k].Dinv) return false;
-    return true;
+    return h->tune.use_dinv && p->dinv_block > 0 && every_factor_has_dinv(d);
 }
 
 #define GPK_PROF_MARK(h, i) do { if ((h)->prof) { (h)->prof_phase = (i); GPK_HIP((h), hipEventRecord((h)->pev[i], (h)->stream)); } } while (0)
@@ -372,10 +377,9 @@ int assemble_normal_equations(gpk_handle h, const gpk_gn_problem* p, const Dims&
     const int nc = d.nz + 1;
     if (lds < nc || ldh < nc) return gpk_bad_arg(h, "gn: lds/ldh < nz+1");
     const GpkLz lz = step_profile(h, p, d.nz, rev);
-    bool dinv = h->tune.use_dinv != 0;
+    const bool dinv = h->tune.use_dinv && every_factor_has_dinv(d);
     const int db = p->dinv_block > 0 ? p->dinv_block : 256;
-    if (db != 256 && db != 512 && db != 1024 && db != 2048) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
-    for (int k = 0; k < d.ngroups; ++k) if (d.g[k].L && !d.g[k].Dinv) dinv = false;
+    if (!dinv_block_ok(db)) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
     double* W = S;
     if (dinv) {
         GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &W));
@@ -617,6 +621,166 @@ __global__ __launch_bounds__(1024) void gram_loss_kernel(int nz, const double* _
     }
 }
 
+// ---- the five ways gpk_gn_step runs a step, and what follows the mode (None: the Gram modes factor Hb themselves) ----------------
+enum class StepMode { Plain, StructuredElliptic, GramElliptic, StructuredGeneral, GramGeneral };
+enum class StepProduct { None, SyrkPotrf, Darcy };
+
+// No side effects.  A mode is chosen only when everything it reads has been prepared; an incomplete preparation falls through to the
+// next line and in the end to Plain.  (The elliptic system has layout 1, and its relaxed form is a system of its own: always Plain.)
+StepMode select_mode(gpk_handle h, const gpk_gn_problem* p, const Dims& d, int rev) {
+    if (!h->tune.structured) return StepMode::Plain;
+    const bool ops = p->W1 && p->W2 && p->ldw >= d.nz + 1;           // gpk_gn_structured_prepare
+    const bool gram = p->G && p->ldg >= d.nz;                        // gpk_gn_gram_prepare
+    if (p->system == GPK_GN_ELLIPTIC && ops && p->v0) return gram && p->pvec ? StepMode::GramElliptic : StepMode::StructuredElliptic;
+    if (rev >= 2 && ops && all_dinv(h, p, d)) return gram ? StepMode::GramGeneral : StepMode::StructuredGeneral;
+    return StepMode::Plain;
+}
+StepProduct select_product(StepMode m, int rev) {
+    return (m == StepMode::GramElliptic || m == StepMode::GramGeneral) ? StepProduct::None : rev == 4 ? StepProduct::Darcy : StepProduct::SyrkPotrf;
+}
+
+// what a mode hands back: the solved block [L^{-1}A | L^{-1}F] (not the Gram modes), exact loss started, its chain still to be issued
+struct ModeOut { double* W = nullptr; bool exact = false, exact_late = false; };
+
+// the loss of the iterate the step starts from by substitution (gpk_tune key 52): late on the side stream if allowed and there is one, else at once
+int start_exact_loss(gpk_handle h, const gpk_gn_problem* p, const Dims& d, const double* z, bool allow_late, bool* exact, bool* exact_late) {
+    if (!h->tune.exact_loss) return 0;
+    *exact = true;
+    *exact_late = h->tune.exact_loss == 1 && allow_late && h->pipe_g && !h->pipe_unavailable;
+    return *exact_late ? exact_loss_build(h, p, d, z) : exact_loss(h, p, d, z);
+}
+
+// w = L^{-1}F(z) from the F column of S (every row has an entry) -> dst[row * dst_stride]: one single-column solve per factor, other rows copied
+int solve_f_column(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* S, int lds, double* dst, int dst_stride) {
+    for (int k = 0; k < d.ngroups; ++k) {
+        const Group& g = d.g[k];
+        if (g.n <= 0) continue;
+        double* src = S + (long)g.off * lds + d.nz;
+        double* out = dst + (long)g.off * dst_stride;
+        if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, p->dinv_block, g.n, g.ldl, src, lds, out, dst_stride, 1, GpkLz()));
+        else GPK_HIP(h, hipMemcpy2DAsync(out, (size_t)dst_stride * 8, src, (size_t)lds * 8, 8, g.n, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return 0;
+}
+
+int mode_plain(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* z, double* S, int lds, double* Hb, int ldh, int rev, ModeOut& o) {
+    GPK_TRY(start_exact_loss(h, p, d, z, true, &o.exact, &o.exact_late));     // in front of the solve
+    return assemble_normal_equations(h, p, d, z, S, lds, Hb, ldh, 1.0, rev, &o.W);
+}
+
+// gpk_gn_structured_prepare, elliptic system: one memory-bound pass over W1, W2 instead of the triangular solve
+int mode_structured_elliptic(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* z, double* S, int lds, double*, int, int, ModeOut& o) {
+    const int nz = d.nz;
+    GPK_PROF_MARK(h, 0);
+    double* coef = S;                                                // 3 nz doubles of scratch (S is free in this mode)
+    GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &o.W));
+    h->work_sig[0] = -1;                                             // (the workspace no longer holds a solve of a known shape)
+    structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
+    structured_form_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, p->v0, coef, coef + nz, coef + 2 * nz, o.W, lds);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(start_exact_loss(h, p, d, z, false, &o.exact, &o.exact_late));    // reported loss: true substitution (round 6), as in the plain mode
+    GPK_PROF_MARK(h, 1);
+    return 0;
+}
+
+// gpk_gn_gram_prepare, elliptic system: the bordered matrix assembled in O(nz^2), no solve and no product this step
+int mode_gram_elliptic(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* z, double* S, int, double* Hb, int ldh, int, ModeOut& o) {
+    const int nz = d.nz;
+    double* d_loss = h->d_scalars;
+    GPK_PROF_MARK(h, 0);
+    double* coef = S;                                                // d, a, z (column order), then q1, q2: 5 nz doubles of scratch
+    structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
+    gram_gemv_kernel<<<nz, 256, 0, h->stream>>>(nz, p->G, p->ldg, p->pvec, coef + nz, coef + 2 * nz, coef + 3 * nz);
+    GPK_PROF_MARK(h, 1);
+    gram_form_kernel<<<nz + 1, 256, 0, h->stream>>>(nz, p->G, p->ldg, coef, coef + 3 * nz, Hb, ldh);
+    gram_loss_kernel<<<1, 1024, 0, h->stream>>>(nz, p->pvec, coef + nz, coef + 2 * nz, coef + 3 * nz, Hb + (long)nz * ldh + nz, d_loss);
+    // (the level's own loss from w = L^{-1}F(z) itself, see structured_w_kernel; w lives behind the five coefficient vectors in S)
+    structured_w_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, p->v0, coef + nz, coef + 2 * nz, coef + 5 * nz);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(gpk_i_dot(h, coef + 5 * nz, coef + 5 * nz, d.rows, d_loss));
+    h->pipe_tev_used = 0; h->prof_pipelined = 0;
+    GPK_TRY(gpk_i_potrf(h, Hb, nz + 1, ldh, 0));
+    // the REPORTED loss by true substitution here too (round 6; the class API takes its history from this number): one vector on
+    // the main stream behind the factorisation -- the level's own d_loss (above) stays the corner of Hb
+    return start_exact_loss(h, p, d, z, false, &o.exact, &o.exact_late);
+}
+
+// gpk_gn_structured_prepare, Burgers / Eikonal / Darcy (round 6): W = W1 diag(d(z)) + W2 in one memory-bound pass; the F column solved (exact)
+int mode_structured_general(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* z, double* S, int lds, double*, int, int rev, ModeOut& o) {
+    const int nz = d.nz;
+    GPK_TRY(start_exact_loss(h, p, d, z, true, &o.exact, &o.exact_late));
+    GPK_PROF_MARK(h, 0);
+    GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &o.W));
+    h->work_sig[0] = -1;                                             // (the workspace no longer holds a solve of a known shape)
+    double* coef = S;                                                // nz doubles of scratch: row 0 of S left of its F column
+    structured_coeff_general_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(p->system, p->Nd, nz, rev, p->p0, p->p1, p->rhs_f, z, coef);
+    structured_form_general_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, coef, o.W, lds);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(build(h, p, z, S, lds, nz, 0));                          // F(z) into column nz of S
+    GPK_TRY(solve_f_column(h, p, d, S, lds, o.W + nz, lds));
+    GPK_PROF_MARK(h, 1);
+    return 0;
+}
+
+// gpk_gn_gram_prepare, Burgers / Eikonal / Darcy (round 6): H/2 = D G11 D + D G12 + G21 D + G22 from the Gram blocks of W1 = L^{-1}A1,
+// W2 = L^{-1}A2; the border from the SOLVED column w = L^{-1}F(z): g/2 = D W1^T w + W2^T w, loss = w^T w
+int mode_gram_general(gpk_handle h, const gpk_gn_problem* p, const Dims& d, double* z, double* S, int lds, double* Hb, int ldh, int rev, ModeOut& o) {
+    const int nz = d.nz;
+    GPK_TRY(start_exact_loss(h, p, d, z, true, &o.exact, &o.exact_late));
+    GPK_PROF_MARK(h, 0);
+    double* wv = nullptr;                                            // [w (rows) | d (nz) | q1 (nz) | q2 (nz)]
+    GPK_TRY(gpk_i_workspace(h, ((size_t)d.rows + 3 * (size_t)nz + 16) * sizeof(double), &wv));
+    h->work_sig[0] = -1;
+    double* dcol = wv + ((d.rows + 1) & ~1L);                        // (16-byte aligned)
+    double* q = dcol + nz;
+    structured_coeff_general_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(p->system, p->Nd, nz, rev, p->p0, p->p1, p->rhs_f, z, dcol);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(build(h, p, z, S, lds, nz, 0));                          // F(z) into column nz of S
+    GPK_TRY(solve_f_column(h, p, d, S, lds, wv, 1));
+    GPK_PROF_MARK(h, 1);
+    GPK_TRY(gpk_i_gemm(h, true, false, nz, 1, d.rows, 1.0, p->W1, p->ldw, wv, 1, 0.0, q, 1, false));          // q1 = W1^T w
+    GPK_TRY(gpk_i_gemm(h, true, false, nz, 1, d.rows, 1.0, p->W2, p->ldw, wv, 1, 0.0, q + nz, 1, false));     // q2 = W2^T w
+    gram_form_kernel<<<nz + 1, 256, 0, h->stream>>>(nz, p->G, p->ldg, dcol, q, Hb, ldh);
+    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(gpk_i_dot(h, wv, wv, d.rows, Hb + (long)nz * ldh + nz));
+    GPK_HIP(h, hipMemcpyAsync(h->d_scalars, Hb + (long)nz * ldh + nz, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    h->pipe_tev_used = 0; h->prof_pipelined = 0;
+    return gpk_i_potrf(h, Hb, nz + 1, ldh, 0);
+}
+
+// Darcy (layout 4): Hb = W_u^T W_u (u-part rows + the data rows below them, piecewise profile) + W_a^T W_a (the a-part's own staircase on
+// its sub-square of columns, its F column as a border row), d_loss = its corner, then the factorisation
+int darcy_product(gpk_handle h, const gpk_gn_problem* p, const Dims& d, const double* W, int lds, double* Hb, int ldh, double* d_loss) {
+    const int Nd = p->Nd, nz = d.nz, nc = nz + 1;
+    const Group& ga = d.g[0];
+    const Group& gu = d.g[1];
+    const double* Wa = W + (long)ga.off * lds;
+    const double* Wu = W + (long)gu.off * lds;
+    const int ph = h->prof_phase;
+    h->prof_phase = 2;                                               // (flop accounting: the product)
+    h->pipe_tev_used = 0; h->prof_pipelined = 0;
+    if (h->prof) {
+        while (h->pipe_tev.size() < 2) { hipEvent_t e; GPK_HIP(h, hipEventCreate(&e)); h->pipe_tev.push_back(e); }
+        GPK_HIP(h, hipEventRecord(h->pipe_tev[0], h->stream));
+    }
+    const GpkLz lz_a = GpkLz::closed(3 * Nd);                        // (the a-part's own columns [N_d, 4 N_d))
+    int rc = gpk_i_gemm(h, true, false, nc, nc, d.rows - gu.off, 1.0, Wu, lds, Wu, lds, 0.0, Hb, ldh, true, GpkLz::piecewise(darcy_u_profile(Nd)));
+    const bool cached_a = p->Wa && p->Ha;                            // (checked: ldwa, ldha >= 3 N_d)
+    if (rc == 0 && cached_a) {
+        add_lower_kernel<<<3 * Nd, 256, 0, h->stream>>>(3 * Nd, p->Ha, p->ldha, Hb + (long)Nd * ldh + Nd, ldh);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = gpk_fail(h, e, "add_lower_kernel", __FILE__, __LINE__);
+    } else if (rc == 0)
+        rc = gpk_i_gemm(h, true, false, 3 * Nd, 3 * Nd, ga.n, 1.0, Wa + Nd, lds, Wa + Nd, lds, 1.0, Hb + (long)Nd * ldh + Nd, ldh, true, lz_a);
+    if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 3 * Nd, ga.n, 1.0, Wa + nz, lds, cached_a ? p->Wa : Wa + Nd, cached_a ? p->ldwa : lds, 1.0,
+                                 Hb + (long)nz * ldh + Nd, ldh, false, lz_a);
+    if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 1, ga.n, 1.0, Wa + nz, lds, Wa + nz, lds, 1.0, Hb + (long)nz * ldh + nz, ldh, false);
+    h->prof_phase = ph;
+    GPK_TRY(rc);
+    if (h->prof) { GPK_HIP(h, hipEventRecord(h->pipe_tev[1], h->stream)); h->pipe_tev_used = 2; }
+    GPK_HIP(h, hipMemcpyAsync(d_loss, Hb + (long)nz * ldh + nz, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return gpk_i_potrf(h, Hb, nc, ldh, 0);
+}
 
 }  // namespace
 
@@ -690,7 +854,7 @@ extern "C" int gpk_gn_darcy_prepare(gpk_handle h, const gpk_gn_problem* p, doubl
     if (!p->Dinv || !p->Dinv2 || p->dinv_block <= 0) return gpk_bad_arg(h, "darcy_prepare: needs Dinv, Dinv2 and dinv_block (the GEMM-only solve path)");
     const int Nd = p->Nd, na = 3 * Nd, nc = d.nz + 1, db = p->dinv_block;
     if (lds < nc || ldwa < na || ldha < na) return gpk_bad_arg(h, "darcy_prepare: lds/ldwa/ldha");
-    if (db != 256 && db != 512 && db != 1024 && db != 2048) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
+    if (!dinv_block_ok(db)) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
     const Group& ga = d.g[0];
     double* zero = nullptr;
     GPK_HIP(h, hipMalloc((void**)&zero, (size_t)d.nz * sizeof(double)));
@@ -724,12 +888,9 @@ extern "C" int gpk_gn_worksize(const gpk_gn_problem* p, int lds, int* host_lds, 
     const int nc = d.nz + 1;
     if (lds == 0) lds = ((nc + 15) / 16) * 16;
     if (lds < nc) return GPK_ERR_ARG;
-    // as assemble_normal_equations decides it: the out-of-place GEMM-only solve runs whenever EVERY factor comes with its inverted diagonal
-    // blocks (dinv_block = 0 means 256 there too); the figure assumes the default gpk_tune(10, 1) -- with the substitution schedule forced
-    // the handle reserves nothing
-    bool dinv = false;
-    for (int k = 0; k < d.ngroups; ++k) if (d.g[k].L && d.g[k].Dinv) dinv = true;
-    for (int k = 0; k < d.ngroups; ++k) if (d.g[k].L && !d.g[k].Dinv) dinv = false;
+    // as assemble_normal_equations decides it (dinv_block = 0 means 256 there too); the figure assumes the default gpk_tune(10, 1) -- with
+    // the substitution schedule forced the handle reserves nothing
+    const bool dinv = every_factor_has_dinv(d);
     if (host_lds) *host_lds = lds;
     if (S_bytes) *S_bytes = (size_t)d.rows * lds * sizeof(double);
     if (Hb_bytes) *Hb_bytes = (size_t)nc * lds * sizeof(double);
@@ -744,159 +905,27 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
     Dims d;
     GPK_TRY(check_prob(h, p, d));
     const int nz = d.nz;
-    // reversed column order (leading-zero layout): unknown u's column of A(z) is zero above row u for the elliptic system (rows t and
-    // N_d + t) and for its relaxed form (unknowns [v; w]: rows t resp. N_d + t of the Theta block, penalty rows at the bottom)
-    // Eikonal: the same after regrouping the unknowns (BuildArgs::rev = 2).  Burgers: the three columns of point t all start in row
-    // t -- interleaved they form a staircase of slope 1/3 (rev = 3).  Darcy (two factors with different column supports) runs the
-    // dense schedule.
-    // Darcy (round 4): leading-zero layout with a piecewise profile per factor (darcy_u_profile), only on the GEMM-only solve path
     if (p->system == GPK_GN_DARCY && p->Wa && p->Ha && (p->ldwa < 3 * p->Nd || p->ldha < 3 * p->Nd))
         return gpk_bad_arg(h, "gn: ldwa/ldha < 3 Nd (gpk_gn_darcy_prepare)");
     const int rev = step_layout(h, p);
-    double* W = nullptr;                                             // the solved block [L^{-1}A | L^{-1}F] (S or the workspace)
-    const bool gram = h->tune.structured && p->system == GPK_GN_ELLIPTIC && p->G && p->pvec && p->ldg >= nz;
-    // the same level for the Burgers / Eikonal / Darcy systems (round 6): H/2 = D G11 D + D G12 + G21 D + G22 from the Gram blocks of
-    // W1 = L^{-1}A1, W2 = L^{-1}A2; the border from the SOLVED column w = L^{-1}F(z): g/2 = D W1^T w + W2^T w, loss = w^T w
-    const bool gram_general = h->tune.structured && rev >= 2 && p->G && p->W1 && p->W2 && p->ldg >= nz && p->ldw >= nz + 1 && all_dinv(h, p, d);
+    const StepMode mode = select_mode(h, p, d, rev);
     double* d_loss = h->d_scalars;
-    bool exact = false, exact_late = false;                          // (d_scalars[8]: the loss by substitution, exact_loss*)
     GPK_HIP(h, hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-    if ((gram || (h->tune.structured && p->W1)) && (long)d.rows * lds < 5L * nz + d.rows)
+    if (h->tune.structured && p->W1 && (long)d.rows * lds < 5L * nz + d.rows)   // (every structured mode has W1; S is their scratch)
         return gpk_bad_arg(h, "gn: S too small for the scratch vectors of the structured modes");
-    if (gram) {
-        // optional Gram level (gpk_gn_gram_prepare): the bordered matrix assembled in O(nz^2), no solve and no product this step
-        GPK_PROF_MARK(h, 0);
-        double* coef = S;                                            // d, a, z (column order), then q1, q2: 5 nz doubles of scratch
-        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
-        gram_gemv_kernel<<<nz, 256, 0, h->stream>>>(nz, p->G, p->ldg, p->pvec, coef + nz, coef + 2 * nz, coef + 3 * nz);
-        GPK_PROF_MARK(h, 1);
-        gram_form_kernel<<<nz + 1, 256, 0, h->stream>>>(nz, p->G, p->ldg, coef, coef + 3 * nz, Hb, ldh);
-        gram_loss_kernel<<<1, 1024, 0, h->stream>>>(nz, p->pvec, coef + nz, coef + 2 * nz, coef + 3 * nz, Hb + (long)nz * ldh + nz, d_loss);
-        // (the reported loss from w = L^{-1}F(z) itself, see structured_w_kernel; w lives behind the five coefficient vectors in S)
-        structured_w_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, p->v0, coef + nz, coef + 2 * nz, coef + 5 * nz);
-        GPK_LAUNCH_CHECK(h);
-        GPK_TRY(gpk_i_dot(h, coef + 5 * nz, coef + 5 * nz, d.rows, d_loss));
-        h->pipe_tev_used = 0; h->prof_pipelined = 0;
-        GPK_TRY(gpk_i_potrf(h, Hb, nz + 1, ldh, 0));
-        // the REPORTED loss by true substitution here too (round 6; the class API takes its history from this number): one vector on
-        // the main stream behind the factorisation -- the level's own d_loss (above) stays the corner of Hb
-        if (h->tune.exact_loss) { exact = true; GPK_TRY(exact_loss(h, p, d, z)); }
-    } else if (h->tune.structured && p->system == GPK_GN_ELLIPTIC && p->W1 && p->W2 && p->v0 && p->ldw >= nz + 1) {
-        // optional structured solve (gpk_gn_structured_prepare): one memory-bound pass over W1, W2 instead of the triangular solve
-        GPK_PROF_MARK(h, 0);
-        double* coef = S;                                            // 3 nz doubles of scratch (S is free in this mode)
-        GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &W));
-        h->work_sig[0] = -1;                                         // (the workspace no longer holds a solve of a known shape)
-        structured_coeff_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, p->nonlin, p->p0, p->p1, p->p2, z, coef, coef + nz, coef + 2 * nz);
-        structured_form_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, p->v0, coef, coef + nz, coef + 2 * nz, W, lds);
-        GPK_LAUNCH_CHECK(h);
-        if (h->tune.exact_loss) { exact = true; GPK_TRY(exact_loss(h, p, d, z)); }   // reported loss: true substitution (round 6), as in the plain branch
-        GPK_PROF_MARK(h, 1);
-    } else if (gram_general) {
-        if (h->tune.exact_loss) {
-            exact = true;
-            exact_late = h->tune.exact_loss == 1 && h->pipe_g && !h->pipe_unavailable;
-            if (exact_late) GPK_TRY(exact_loss_build(h, p, d, z));
-            else GPK_TRY(exact_loss(h, p, d, z));
-        }
-        GPK_PROF_MARK(h, 0);
-        const int db = p->dinv_block;
-        double* ws = nullptr;                                        // [w (rows) | d (nz) | q1 (nz) | q2 (nz)]
-        GPK_TRY(gpk_i_workspace(h, ((size_t)d.rows + 3 * (size_t)nz + 16) * sizeof(double), &ws));
-        h->work_sig[0] = -1;
-        double* wv = ws;
-        double* dcol = ws + ((d.rows + 1) & ~1L);                    // (16-byte aligned)
-        double* q = dcol + nz;
-        structured_coeff_general_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(p->system, p->Nd, nz, rev, p->p0, p->p1, p->rhs_f, z, dcol);
-        GPK_LAUNCH_CHECK(h);
-        GPK_TRY(build(h, p, z, S, lds, nz, 0));                      // F(z) into column nz of S; w = L^{-1}F(z), one column per factor
-        for (int k = 0; k < d.ngroups; ++k) {
-            const Group& g = d.g[k];
-            if (g.n <= 0) continue;
-            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, wv + g.off, 1, 1, GpkLz()));
-            else GPK_HIP(h, hipMemcpy2DAsync(wv + g.off, 8, S + (long)g.off * lds + nz, (size_t)lds * 8, 8, g.n, hipMemcpyDeviceToDevice, h->stream));
-        }
-        GPK_PROF_MARK(h, 1);
-        GPK_TRY(gpk_i_gemm(h, true, false, nz, 1, d.rows, 1.0, p->W1, p->ldw, wv, 1, 0.0, q, 1, false));          // q1 = W1^T w
-        GPK_TRY(gpk_i_gemm(h, true, false, nz, 1, d.rows, 1.0, p->W2, p->ldw, wv, 1, 0.0, q + nz, 1, false));     // q2 = W2^T w
-        gram_form_kernel<<<nz + 1, 256, 0, h->stream>>>(nz, p->G, p->ldg, dcol, q, Hb, ldh);
-        GPK_LAUNCH_CHECK(h);
-        GPK_TRY(gpk_i_dot(h, wv, wv, d.rows, Hb + (long)nz * ldh + nz));
-        GPK_HIP(h, hipMemcpyAsync(d_loss, Hb + (long)nz * ldh + nz, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->pipe_tev_used = 0; h->prof_pipelined = 0;
-        GPK_TRY(gpk_i_potrf(h, Hb, nz + 1, ldh, 0));
-    } else if (h->tune.structured && rev >= 2 && p->W1 && p->W2 && p->ldw >= nz + 1 && all_dinv(h, p, d)) {
-        // structured solve of the Burgers / Eikonal / Darcy systems (round 6, gpk_gn_structured_prepare): W = W1 diag(d(z)) + W2 in one
-        // memory-bound pass over all rows; the F column by its own one-column solve per factor (exact; rows without a factor copied)
-        if (h->tune.exact_loss) {
-            exact = true;
-            exact_late = h->tune.exact_loss == 1 && h->pipe_g && !h->pipe_unavailable;
-            if (exact_late) GPK_TRY(exact_loss_build(h, p, d, z));
-            else GPK_TRY(exact_loss(h, p, d, z));
-        }
-        GPK_PROF_MARK(h, 0);
-        const int nc = nz + 1, db = p->dinv_block;
-        GPK_TRY(gpk_i_workspace(h, (size_t)d.rows * lds * sizeof(double), &W));
-        h->work_sig[0] = -1;                                         // (the workspace no longer holds a solve of a known shape)
-        double* coef = S;                                            // nz doubles of scratch: row 0 of S left of its F column
-        structured_coeff_general_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(p->system, p->Nd, nz, rev, p->p0, p->p1, p->rhs_f, z, coef);
-        structured_form_general_kernel<<<d.rows, 256, 0, h->stream>>>(nz, p->W1, p->W2, p->ldw, coef, W, lds);
-        GPK_LAUNCH_CHECK(h);
-        GPK_TRY(build(h, p, z, S, lds, nz, 0));                      // F(z) into column nz of S (every row has an entry)
-        for (int k = 0; k < d.ngroups; ++k) {
-            const Group& g = d.g[k];
-            if (g.n <= 0) continue;
-            if (g.L) GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, S + (long)g.off * lds + nz, lds, W + (long)g.off * lds + nz, lds, 1, GpkLz()));
-            else GPK_HIP(h, hipMemcpy2DAsync(W + (long)g.off * lds + nz, (size_t)lds * 8, S + (long)g.off * lds + nz, (size_t)lds * 8, 8, g.n,
-                                             hipMemcpyDeviceToDevice, h->stream));
-        }
-        (void)nc;
-        GPK_PROF_MARK(h, 1);
-    } else {
-        // the loss of the iterate this step starts from, exact (true substitution with the factors, one vector), in front of the solve
-        if (h->tune.exact_loss) {
-            exact = true;
-            exact_late = h->tune.exact_loss == 1 && h->pipe_g && !h->pipe_unavailable;
-            if (exact_late) GPK_TRY(exact_loss_build(h, p, d, z));
-            else GPK_TRY(exact_loss(h, p, d, z));
-        }
-        GPK_TRY(assemble_normal_equations(h, p, d, z, S, lds, Hb, ldh, 1.0, rev, &W));
+    ModeOut o;
+    switch (mode) {
+        case StepMode::Plain:              GPK_TRY(mode_plain(h, p, d, z, S, lds, Hb, ldh, rev, o)); break;
+        case StepMode::StructuredElliptic: GPK_TRY(mode_structured_elliptic(h, p, d, z, S, lds, Hb, ldh, rev, o)); break;
+        case StepMode::GramElliptic:       GPK_TRY(mode_gram_elliptic(h, p, d, z, S, lds, Hb, ldh, rev, o)); break;
+        case StepMode::StructuredGeneral:  GPK_TRY(mode_structured_general(h, p, d, z, S, lds, Hb, ldh, rev, o)); break;
+        case StepMode::GramGeneral:        GPK_TRY(mode_gram_general(h, p, d, z, S, lds, Hb, ldh, rev, o)); break;
     }
     // Hb = W^T W and its Cholesky factor, pipelined by column blocks (gpk_factor.hip); d_loss = Hb[nz][nz] before factoring;
     // the last row of the factor is (L_H^{-1} g/2)^T
-    if (rev == 4 && !gram_general) {
-        // Darcy: Hb = W_u^T W_u (u-part rows + the data rows below them, piecewise profile) + W_a^T W_a (the a-part's own staircase on
-        // its sub-square of columns, its F column as a border row), then the factorisation
-        const int Nd = p->Nd, nc = nz + 1;
-        const Group& ga = d.g[0];
-        const Group& gu = d.g[1];
-        const double* Wa = W + (long)ga.off * lds;
-        const double* Wu = W + (long)gu.off * lds;
-        const int ph = h->prof_phase;
-        h->prof_phase = 2;                                           // (flop accounting: the product)
-        h->pipe_tev_used = 0; h->prof_pipelined = 0;
-        if (h->prof) {
-            while (h->pipe_tev.size() < 2) { hipEvent_t e; GPK_HIP(h, hipEventCreate(&e)); h->pipe_tev.push_back(e); }
-            GPK_HIP(h, hipEventRecord(h->pipe_tev[0], h->stream));
-        }
-        const GpkLz lz_a = GpkLz::closed(3 * Nd);                    // (the a-part's own columns [N_d, 4 N_d))
-        int rc = gpk_i_gemm(h, true, false, nc, nc, d.rows - gu.off, 1.0, Wu, lds, Wu, lds, 0.0, Hb, ldh, true, GpkLz::piecewise(darcy_u_profile(Nd)));
-        const bool cached_a = p->Wa && p->Ha;                       // (checked: ldwa, ldha >= 3 N_d)
-        if (rc == 0 && cached_a) {
-            add_lower_kernel<<<3 * Nd, 256, 0, h->stream>>>(3 * Nd, p->Ha, p->ldha, Hb + (long)Nd * ldh + Nd, ldh);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = gpk_fail(h, e, "add_lower_kernel", __FILE__, __LINE__);
-        } else if (rc == 0)
-            rc = gpk_i_gemm(h, true, false, 3 * Nd, 3 * Nd, ga.n, 1.0, Wa + Nd, lds, Wa + Nd, lds, 1.0, Hb + (long)Nd * ldh + Nd, ldh, true, lz_a);
-        if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 3 * Nd, ga.n, 1.0, Wa + nz, lds, cached_a ? p->Wa : Wa + Nd, cached_a ? p->ldwa : lds, 1.0,
-                                     Hb + (long)nz * ldh + Nd, ldh, false, lz_a);
-        if (rc == 0) rc = gpk_i_gemm(h, true, false, 1, 1, ga.n, 1.0, Wa + nz, lds, Wa + nz, lds, 1.0, Hb + (long)nz * ldh + nz, ldh, false);
-        h->prof_phase = ph;
-        GPK_TRY(rc);
-        if (h->prof) { GPK_HIP(h, hipEventRecord(h->pipe_tev[1], h->stream)); h->pipe_tev_used = 2; }
-        GPK_HIP(h, hipMemcpyAsync(d_loss, Hb + (long)nz * ldh + nz, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        GPK_TRY(gpk_i_potrf(h, Hb, nc, ldh, 0));
-    } else if (!gram && !gram_general) GPK_TRY(gpk_i_syrk_potrf(h, W, lds, d.rows, nz + 1, step_profile(h, p, nz, rev), Hb, ldh, d_loss));
+    const StepProduct product = select_product(mode, rev);
+    if (product == StepProduct::Darcy) GPK_TRY(darcy_product(h, p, d, o.W, lds, Hb, ldh, d_loss));
+    else if (product == StepProduct::SyrkPotrf) GPK_TRY(gpk_i_syrk_potrf(h, o.W, lds, d.rows, nz + 1, step_profile(h, p, nz, rev), Hb, ldh, d_loss));
     GPK_PROF_MARK(h, 2);
     GPK_PROF_MARK(h, 3);
     // the chain of the exact loss: on the GEMM partition's stream from here on (pipelined phase: that stream's last product finished before the
@@ -908,25 +937,16 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         ~ChainGuard() { if (armed && h->pipe_g) (void)hipStreamSynchronize(h->pipe_g); }
     } chain_guard{h, false};
     bool chain_on_side = false;
-    if (exact_late) {
+    if (o.exact_late) {
         GPK_TRY(exact_loss_chain(h, d, !h->prof_pipelined, &chain_on_side));
         chain_guard.armed = chain_on_side;
     }
-    double* dl = rev ? S : delta;                                    // scratch for the (reversed-order) solution: S is free now
-    GPK_HIP(h, hipMemcpyAsync(dl, Hb + (long)nz * ldh, (size_t)nz * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    GPK_TRY(gpk_i_trsv(h, true, Hb, nz, ldh, dl));
-    if (rev) {
-        reverse_copy_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, dl, delta, rev, p->Nd);
-        axpy_rev_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, -step_size, dl, z, rev, p->Nd);
-    } else {
-        axpy_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, -step_size, delta, z);
-    }
-    GPK_LAUNCH_CHECK(h);
+    GPK_TRY(gpk_i_gn_finish(h, p, nz, rev, Hb, ldh, S, delta, z, step_size));   // (S is free now: scratch for the reversed-order solution)
     GPK_PROF_MARK(h, 4);
     // the two host scalars of the step through pinned memory (h_pinned[0] = loss, the int behind h_pinned[1] = pivot status)
     GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (chain_on_side) GPK_HIP(h, hipStreamWaitEvent(h->stream, h->ev_loss[1], 0));
-    GPK_HIP(h, hipMemcpyAsync(h->h_pinned, exact ? h->d_scalars + 8 : d_loss, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned, o.exact ? h->d_scalars + 8 : d_loss, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     GPK_HIP(h, hipStreamSynchronize(h->stream));
     chain_guard.armed = false;                                       // the main stream waited for the chain's event: it is complete
     int info = *reinterpret_cast<const int*>(h->h_pinned + 1);
@@ -1084,5 +1104,5 @@ int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, cons
 
 
 #ifdef GPK_DEV
-#include "dev/gpk_gn_dev_abi.inc"        // gpk_debug_set_profile, gpk_debug_syrk_lz, gpk_debug_first_rows (include/gpk_dev.h): development build only
+#include "dev/gpk_gn_dev_abi.inc"        // gpk_debug_set_profile, gpk_debug_syrk_lz, gpk_debug_first_rows, gpk_debug_step_mode (include/gpk_dev.h): development build only
 #endif

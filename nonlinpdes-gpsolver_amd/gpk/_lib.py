@@ -141,6 +141,7 @@ DEV_PROTOTYPES = {
     'gpk_debug_set_profile': (_i, [_vp, _i, _i, _pi, _pi, _pi, _pi, _i]),
     'gpk_debug_syrk_lz': (_i, [_vp, _i, _i, _d, _vp, _i, _d, _vp, _i, _i]),
     'gpk_debug_first_rows': (_i, [_vp, _pp, _pi, _pi]),
+    'gpk_debug_step_mode': (_i, [_vp, _pp, _pi, _pi]),
     'gpk_debug_workspace_bytes': (_i, [_vp, C.POINTER(_sz)]),
 }
 
