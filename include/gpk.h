@@ -32,8 +32,14 @@ typedef struct gpk_ctx* gpk_handle;
 
 /* Gram layouts = the `eqn` strings of src/Gram_matrice.py:41,58,100,137 (Darcy yields two matrices: _U and _A). */
 enum { GPK_LAYOUT_ELLIPTIC = 0, GPK_LAYOUT_BURGERS = 1, GPK_LAYOUT_EIKONAL = 2, GPK_LAYOUT_DARCY_U = 2, GPK_LAYOUT_DARCY_A = 3 };
-/* kernel classes of src/kernels.py:8,91 */
-enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1 };
+/* kernel classes of src/kernels.py:8,91, and the Matern family nu = 5/2, 7/2, 9/2 ("Matern kernels"):
+ *   kappa = exp(-t) theta_m(t) / theta_m(0),  nu = m + 1/2,  t = sqrt(2 nu) |((x1-y1)/rho_1, (x2-y2)/rho_2)|,  theta_m the reverse Bessel
+ *   polynomial (nu = 5/2: (1 + t + t^2/3) exp(-t)).  host_kparams = {rho_1, rho_2}: BOTH are read, each finite and > 0, else -9001.
+ * The Matern ids are served by the calls of the reference layouts -- gpk_assemble, gpk_assemble_test, gpk_extend, gpk_extend_functionals,
+ * gpk_assemble_cross, for every layout -- and by nothing else: the 3-D, boundary-functional and operator calls return -9001 for them.
+ * Ids 2..7 and every id above 10 are invalid everywhere (-9001).  nu = 3/2 is absent on purpose: that kernel is not C^4 at coincident
+ * points, so the diagonal of a Laplacian block does not exist. */
+enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 = 8, GPK_KERNEL_MATERN72 = 9, GPK_KERNEL_MATERN92 = 10 };
 /* nugget_type of src/PDEs.py:56,250,391 / src/InverseProblems.py:66 */
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
@@ -86,7 +92,7 @@ int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
 /* ---- Gram assembly: replaces Gram_matrix_assembly (src/Gram_matrice.py:11-187) plus the nugget of
  *      *.Gram_matrix (src/PDEs.py:56-73,250-269,391-409; src/InverseProblems.py:66-99) in one fused pass.
- *      kparams: Gaussian {sigma, unused}; anisotropic {sigma_t, sigma_x}.  Xd (Nd,2), Xb (Nb,2) row-major.
+ *      kparams: Gaussian {sigma, unused}; anisotropic {sigma_t, sigma_x}; Matern {rho_1, rho_2}.  Xd (Nd,2), Xb (Nb,2) row-major.
  *      Theta: N x N, N = 2Nd+Nb (ELLIPTIC), 4Nd+Nb (BURGERS/EIKONAL/DARCY_U), 3Nd (DARCY_A).
  *      host_ratios[3]: adaptive trace ratios (unused entries 0). */
 int gpk_assemble(gpk_handle h, int layout, int kernel, const double* host_kparams,

@@ -16,8 +16,9 @@
 // (~1 exp + ~60 flops) is >10x below the HBM write time of its 32..128 output bytes.
 //
 // The functional tables, the Hermite evaluation (hermite_plain), the frame of the extension kernel, the 16-byte store and the host side
-// of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.
-#include "gpk_assemble_common.h"
+// of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.  The layouts, the argument structs and
+// the layout dispatch are shared with the Matern family of these layouts (gpk_assemble_matern.hip, launched from the entry points below): gpk_assemble_ref.h.
+#include "gpk_assemble_ref.h"
 
 using namespace gpk_asm;
 
@@ -39,24 +40,6 @@ __host__ __device__ __forceinline__ double pair_coeff(const double (&a)[5], cons
     }
     return s;
 }
-
-// layouts: functional of each Theta block and whether it lives on domain points only (0) or domain+boundary (1)
-template <int LAYOUT> struct Lay;
-template <> struct Lay<GPK_LAYOUT_ELLIPTIC> { static constexpr int nb = 2; static constexpr int f[4] = {F_LAP, F_DELTA, 0, 0};          static constexpr int db[4] = {0, 1, 0, 0}; };
-template <> struct Lay<GPK_LAYOUT_BURGERS>  { static constexpr int nb = 4; static constexpr int f[4] = {F_D1, F_D2, F_DD2, F_DELTA};   static constexpr int db[4] = {0, 0, 0, 1}; };
-template <> struct Lay<GPK_LAYOUT_EIKONAL>  { static constexpr int nb = 4; static constexpr int f[4] = {F_D1, F_D2, F_LAP, F_DELTA};   static constexpr int db[4] = {0, 0, 0, 1}; };
-template <> struct Lay<GPK_LAYOUT_DARCY_A>  { static constexpr int nb = 3; static constexpr int f[4] = {F_D1, F_D2, F_DELTA, 0};       static constexpr int db[4] = {0, 0, 0, 0}; };
-
-struct AsmArgs {
-    const double* px; const double* py;   // SoA points: domain first, then boundary
-    int Nd, M;                            // M = number of points visited (Nd+Nb, or Nd for DARCY_A)
-    double p1, p2;
-    double* out; long ld;
-    int off[4]; int size[4];
-    double nug[4];
-    const double* tx; int Nt;             // test mode: (Nt,2) row-major test points
-    const double* coeff;                  // extend mode
-};
 
 __global__ void pack_points_kernel(const double* __restrict__ Xd, int Nd, const double* __restrict__ Xb, int Nb,
                                    double* __restrict__ px, double* __restrict__ py) {
@@ -188,8 +171,6 @@ __global__ __launch_bounds__(256) void assemble_test_kernel(AsmArgs g) {
 // point) a wave stores 1 KB contiguous with the 16-byte store (WIDE: base and ld even, Nt even), or the same two values as two
 // 8-byte stores (any alignment, odd Nt).  One kernel body for both: the values are the same bits either way.  The column point is
 // wave-uniform (scalar loads), and one exp + one pair of Hermite evaluations per point pair feeds every block of the layout.
-constexpr int CROSS_TP = 8;               // column points per workgroup: the grid is N_t / 512 wide, so the rows supply the parallelism
-
 template <int L, int BJ, bool WIDE>
 __device__ __forceinline__ void store_cross(const AsmArgs& g, int p, int t, const double (&a0)[5], const double (&b0)[5], double e0,
                                             const double (&a1)[5], const double (&b1)[5], double e1) {
@@ -264,16 +245,6 @@ __global__ __launch_bounds__(256) void extend_kernel(AsmArgs g) {
 // Mapping: a workgroup owns FN_TT test points (wave-uniform: scalar loads) and its 256 lanes stride over the column points as in
 // extend_kernel; each column point's coordinates and its nb coefficient slices are loaded once and serve all FN_TT test points, and each
 // lane keeps FN_TT x popcount(MASK) accumulators.  Points, zeroing and reduction: the frame of gpk_assemble_common.h.
-struct FnArgs {
-    const double* px; const double* py;   // SoA column points (fill_common)
-    int M;
-    double p1, p2;
-    int off[4]; int size[4];
-    const double* tx; int Nt;
-    const double* coeff;
-    double* out; long ldo;
-};
-
 // sum_b pair_coeff<F, f[b]> c[b] (c[b] = 0 outside block b, as acc_test in extend_kernel)
 template <int L, int F>
 __device__ __forceinline__ double fn_sum(const double (&a)[5], const double (&b)[5], const double (&c)[4]) {
@@ -355,18 +326,6 @@ __global__ __launch_bounds__(256) void pde_residual_nl_kernel(int nonlin, double
     out[t] = -u3 + nl_tau(nonlin, p0, p1, p2, u0) - ft;
 }
 
-// f(std::integral_constant<int, L>) for the layout id: the one place that turns it into a template argument; false: not a layout
-template <class F>
-bool with_layout(int layout, F&& f) {
-    switch (layout) {
-        case GPK_LAYOUT_ELLIPTIC: f(std::integral_constant<int, GPK_LAYOUT_ELLIPTIC>{}); return true;
-        case GPK_LAYOUT_BURGERS:  f(std::integral_constant<int, GPK_LAYOUT_BURGERS>{}); return true;
-        case GPK_LAYOUT_EIKONAL:  f(std::integral_constant<int, GPK_LAYOUT_EIKONAL>{}); return true;
-        case GPK_LAYOUT_DARCY_A:  f(std::integral_constant<int, GPK_LAYOUT_DARCY_A>{}); return true;
-        default: return false;
-    }
-}
-
 template <int L> constexpr int lay_size(int b, int Nd, int Nb) { return b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0; }
 template <int L> constexpr int lay_N(int Nd, int Nb) { return lay_size<L>(0, Nd, Nb) + lay_size<L>(1, Nd, Nb) + lay_size<L>(2, Nd, Nb) + lay_size<L>(3, Nd, Nb); }
 
@@ -375,7 +334,8 @@ template <class Args>
 int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd) return gpk_bad_arg(h, "assemble: sizes/pointers");
     double p[2];
-    GPK_TRY(precisions(h, "assemble: kernel id", kernel, kp, 2, p));
+    if (matern_order(kernel)) GPK_TRY(matern_scales(h, kp, p));      // (the Matern family: inverse length scales)
+    else GPK_TRY(precisions(h, "assemble: kernel id", kernel, kp, 2, p));
     g.p1 = p[0]; g.p2 = p[1];
     const bool known = with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
@@ -413,13 +373,15 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
     if (!h || !Theta) return GPK_ERR_ARG;
     AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    const int matern = matern_order(kernel);                         // the kernel family is chosen here, on the host: 0 = Gaussian
     int nb = 0, N = 0;
     double c[4] = {0, 0, 0, 0};
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         nb = Lay<L>::nb; N = lay_N<L>(Nd, Nb);
-        diag_values<L>(g.p1, g.p2, c);
+        if (!matern) diag_values<L>(g.p1, g.p2, c);
     });
+    if (matern) gpk_i_matern_diag(matern, layout, g.p1, g.p2, c);
     if (ld < N) return gpk_bad_arg(h, "assemble: ld < N");
     // ratio_k = trace(block k) / trace(last block)   (src/PDEs.py:62-66, 256-262, 397-402; IP.py:72-87)
     double r[4] = {0, 0, 0, 1.0};
@@ -432,7 +394,8 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
     const bool pairs = pairs_eligible(h, Theta, ld, g.M, g.size[0], g.size[1], g.size[2], g.size[3]);   // (even sizes: even offsets)
     TimedLaunch timed(h);
     GPK_TRY(timed.start());
-    with_layout(layout, [&](auto l) {
+    if (matern) gpk_i_matern_gram(matern, layout, pairs, h->tune.asm_nt, h->stream, g);
+    else with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP)), grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
         if (!pairs) assemble_kernel<L><<<grid, 256, 0, h->stream>>>(g);
@@ -454,7 +417,8 @@ extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const dou
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
-    with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
+    if (const int matern = matern_order(kernel)) gpk_i_matern_test(matern, layout, h->stream, g);
+    else with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -472,7 +436,8 @@ extern "C" int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const do
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const bool wide = pairs_eligible(h, out, ld, Nt);
     const dim3 grid(gpk_ceil_div(gpk_ceil_div(Nt, 2), 256), gpk_ceil_div(g.M, CROSS_TP));
-    with_layout(layout, [&](auto l) {                                // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
+    if (const int matern = matern_order(kernel)) gpk_i_matern_cross(matern, layout, wide, h->stream, g);
+    else with_layout(layout, [&](auto l) {                           // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
         constexpr int L = decltype(l)::value;
         if (wide) assemble_cross_kernel<L, true><<<grid, 256, 0, h->stream>>>(g);
         else assemble_cross_kernel<L, false><<<grid, 256, 0, h->stream>>>(g);
@@ -526,7 +491,8 @@ extern "C" int gpk_extend(gpk_handle h, int layout, int kernel, const double* kp
     AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = 0; g.tx = Xt; g.Nt = Nt; g.coeff = coeff;
-    with_layout(layout, [&](auto l) { extend_kernel<decltype(l)::value><<<Nt, 256, 0, h->stream>>>(g); });
+    if (const int matern = matern_order(kernel)) gpk_i_matern_extend(matern, layout, h->stream, g);
+    else with_layout(layout, [&](auto l) { extend_kernel<decltype(l)::value><<<Nt, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -542,7 +508,8 @@ extern "C" int gpk_extend_functionals(gpk_handle h, int layout, int kernel, cons
     FnArgs g;
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
-    with_layout(layout, [&](auto l) { launch_extend_fn<decltype(l)::value>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g); });
+    if (const int matern = matern_order(kernel)) gpk_i_matern_extend_fn(matern, layout, fmask, h->stream, g);
+    else with_layout(layout, [&](auto l) { launch_extend_fn<decltype(l)::value>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

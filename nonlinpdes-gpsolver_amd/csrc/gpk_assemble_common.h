@@ -1,4 +1,5 @@
-// gpk_assemble_common.h -- what the five Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts,
+// gpk_assemble_common.h -- what the six Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts,
+// gpk_assemble_matern.hip: their Matern family,
 // gpk_assemble3d.hip, gpk_assemble_bc.hip: Neumann / Robin, gpk_assemble_op.hip: variable-coefficient operator, gpk_assemble_op3d.hip:
 // the operator and the boundary functionals in three dimensions).  The kernels and the
 // per-pair arithmetic that differs between them (pair_coeff in its two roundings, pair_coeff3, the tables of the operator) stay in

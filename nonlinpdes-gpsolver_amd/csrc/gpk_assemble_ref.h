@@ -1,0 +1,78 @@
+// gpk_assemble_ref.h -- what the two translation units of the reference layouts share: gpk_assemble.hip (the Gaussian family, the host
+// side of every entry point) and gpk_assemble_matern.hip (the Matern family: kernels and their launches).  The layouts, the argument
+// structs of the kernels, the layout dispatch, and the launch interface of the Matern kernels.  The kernels themselves stay in their
+// files: each family is compiled on its own, so that nothing added for one changes the code generated for the other.
+#pragma once
+#include "gpk_assemble_common.h"
+
+namespace gpk_asm {
+
+// layouts: functional of each Theta block and whether it lives on domain points only (0) or domain+boundary (1)
+template <int LAYOUT> struct Lay;
+template <> struct Lay<GPK_LAYOUT_ELLIPTIC> { static constexpr int nb = 2; static constexpr int f[4] = {F_LAP, F_DELTA, 0, 0};          static constexpr int db[4] = {0, 1, 0, 0}; };
+template <> struct Lay<GPK_LAYOUT_BURGERS>  { static constexpr int nb = 4; static constexpr int f[4] = {F_D1, F_D2, F_DD2, F_DELTA};   static constexpr int db[4] = {0, 0, 0, 1}; };
+template <> struct Lay<GPK_LAYOUT_EIKONAL>  { static constexpr int nb = 4; static constexpr int f[4] = {F_D1, F_D2, F_LAP, F_DELTA};   static constexpr int db[4] = {0, 0, 0, 1}; };
+template <> struct Lay<GPK_LAYOUT_DARCY_A>  { static constexpr int nb = 3; static constexpr int f[4] = {F_D1, F_D2, F_DELTA, 0};       static constexpr int db[4] = {0, 0, 0, 0}; };
+
+// p1, p2: the precisions of the Gaussian family (gpk_assemble_common.h, precisions), the inverse length scales 1/rho_k of the Matern family
+struct AsmArgs {
+    const double* px; const double* py;   // SoA points: domain first, then boundary
+    int Nd, M;                            // M = number of points visited (Nd+Nb, or Nd for DARCY_A)
+    double p1, p2;
+    double* out; long ld;
+    int off[4]; int size[4];
+    double nug[4];
+    const double* tx; int Nt;             // test mode: (Nt,2) row-major test points
+    const double* coeff;                  // extend mode
+};
+
+struct FnArgs {
+    const double* px; const double* py;   // SoA column points (fill_common)
+    int M;
+    double p1, p2;
+    int off[4]; int size[4];
+    const double* tx; int Nt;
+    const double* coeff;
+    double* out; long ldo;
+};
+
+constexpr int CROSS_TP = 8;               // column points per workgroup: the grid is N_t / 512 wide, so the rows supply the parallelism
+
+// f(std::integral_constant<int, L>) for the layout id: the one place that turns it into a template argument; false: not a layout
+template <class F>
+bool with_layout(int layout, F&& f) {
+    switch (layout) {
+        case GPK_LAYOUT_ELLIPTIC: f(std::integral_constant<int, GPK_LAYOUT_ELLIPTIC>{}); return true;
+        case GPK_LAYOUT_BURGERS:  f(std::integral_constant<int, GPK_LAYOUT_BURGERS>{}); return true;
+        case GPK_LAYOUT_EIKONAL:  f(std::integral_constant<int, GPK_LAYOUT_EIKONAL>{}); return true;
+        case GPK_LAYOUT_DARCY_A:  f(std::integral_constant<int, GPK_LAYOUT_DARCY_A>{}); return true;
+        default: return false;
+    }
+}
+
+// ---- the Matern family (DESIGN.md §K "Matern kernels"): nu = m + 1/2 ------------------------------------------------------------------
+// m of a kernel id (2, 3, 4), 0: not a Matern id
+inline int matern_order(int kernel) {
+    return kernel == GPK_KERNEL_MATERN52 ? 2 : (kernel == GPK_KERNEL_MATERN72 ? 3 : (kernel == GPK_KERNEL_MATERN92 ? 4 : 0));
+}
+
+// inverse length scales r[k] = 1 / rho_k of host_kparams = {rho_1, rho_2}
+inline int matern_scales(gpk_handle h, const double* kp, double (&r)[2]) {
+    for (int k = 0; k < 2; ++k) {
+        if (!(kp[k] > 0.0) || !(kp[k] <= 1.79769313486231570e308)) return gpk_bad_arg(h, "assemble: a Matern kernel needs two finite length scales > 0");
+        r[k] = 1.0 / kp[k];
+    }
+    return 0;
+}
+
+}  // namespace gpk_asm
+
+// Launches of gpk_assemble_matern.hip on stream st (m = matern_order(kernel), layout a valid id, the grids of the Gaussian kernels of
+// the same shape).  gram: pairs as pairs_eligible, nt = 1: non-temporal 16-byte stores (the write-through policies 2 / 3 of key 55: plain).
+void gpk_i_matern_gram(int m, int layout, bool pairs, int nt, hipStream_t st, const gpk_asm::AsmArgs& g);
+void gpk_i_matern_test(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
+void gpk_i_matern_cross(int m, int layout, bool wide, hipStream_t st, const gpk_asm::AsmArgs& g);
+void gpk_i_matern_extend(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
+void gpk_i_matern_extend_fn(int m, int layout, int mask, hipStream_t st, const gpk_asm::FnArgs& g);
+// value of <f_b, f_b> at d = 0 for the blocks of the layout (analytic host values, as diag_values of the Gaussian family)
+void gpk_i_matern_diag(int m, int layout, double r1, double r2, double (&c)[4]);

@@ -10,7 +10,8 @@ from . import _lib as _libmod
 from ._lib import GNProblemStruct, GpkError, load_library
 
 LAYOUT = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_u': 2, 'Darcy_a': 3}
-KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1}
+KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1, 'Matern52': 8, 'Matern72': 9, 'Matern92': 10}      # GPK_KERNEL_*
+MATERN = ('Matern52', 'Matern72', 'Matern92')     # nu = 5/2, 7/2, 9/2: the reference layouts only (assemble .. assemble_cross)
 NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
@@ -48,11 +49,24 @@ def kernel_params(kernel, kernel_parameter):
         return (C.c_double * 2)(float(kernel_parameter), 0.0)
     if kernel == 'anisotropic_Gaussian':
         return (C.c_double * 2)(float(kernel_parameter[0]), float(kernel_parameter[1]))
+    if kernel in MATERN:                                   # {rho_1, rho_2}: a scalar serves both axes
+        kp = [float(v) for v in np.atleast_1d(np.asarray(kernel_parameter, dtype=np.float64))]
+        if len(kp) not in (1, 2):
+            raise ValueError(f'{kernel} needs one length scale or one per axis, got {len(kp)}')
+        return (C.c_double * 2)(kp[0], kp[-1])
     raise ValueError(f'unknown kernel {kernel!r}')
+
+
+def require_gaussian_family(kernel, what):
+    """The 3-D, boundary-functional and operator evaluators serve the Gaussian family only: say so before any device call."""
+    if kernel in MATERN:
+        raise ValueError(f'{what}: the kernel {kernel!r} is available for the layouts Nonlinear_elliptic, Burgers, Eikonal and Darcy '
+                         'only; the 3-D, boundary-functional and operator evaluators take Gaussian or anisotropic_Gaussian')
 
 
 def kernel_params3d(kernel, kernel_parameter):
     """host_kparams of the 3-D calls: Gaussian {sigma}; anisotropic_Gaussian {sigma_1, sigma_2, sigma_3}"""
+    require_gaussian_family(kernel, 'three space dimensions')
     if kernel == 'Gaussian':
         return (C.c_double * 3)(float(kernel_parameter), 0.0, 0.0)
     if kernel == 'anisotropic_Gaussian':
@@ -373,6 +387,8 @@ class Context:
         """The four extend_functionals* calls: functional names `which` through `table` to the mask, points (n, dim) and the expansion
         coefficients to the device, the library `entry` (its arguments: handle, `lead`, kernel, points, the device arrays or None of
         coeffs(Nd, Nb), expansion coefficients, mask, output), then the rows from ascending bit order into the caller's order."""
+        if name != 'extend_functionals':
+            require_gaussian_family(kernel, name)
         which = tuple(which)
         bits = [table[w] for w in which]
         if len(set(bits)) != len(bits):
@@ -400,6 +416,7 @@ class Context:
     def _assemble_two_block(self, entry, dim, kernel, kernel_parameter, Xd, Xb, coeffs, nugget, nugget_type, out):
         """The two-block Gram calls (assemble3d / assemble_bc / assemble_op): points (n, dim) to the device, the library `entry` (its
         arguments: handle, kernel, points, the device arrays or None of coeffs(Nd, Nb), nugget, Theta, ratio) -> (Theta, trace ratio)."""
+        require_gaussian_family(kernel, entry.__name__)
         Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, dim) for X in (Xd, Xb))
         Nd, Nb = Xd.shape[0], Xb.shape[0]
         N = 2 * Nd + Nb

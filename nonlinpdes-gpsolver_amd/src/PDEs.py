@@ -13,6 +13,7 @@ from numpy import random
 
 import gpk
 
+from gpk.device import require_gaussian_family
 from ._runtime import eval_callback, get_context
 from .nonlinearity import Nonlinearity
 from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
@@ -481,6 +482,8 @@ class Nonlinear_elliptic2d(_GPEquation):
         return T, [ratio]
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
+        if self.domain_coeffs is not None or self.boundary_coeffs is not None:
+            require_gaussian_family(kernel, 'Nonlinear_elliptic2d with an operator or boundary conditions')
         ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
         if nugget_type == 'adaptive':
             self.ratio = ratios[0]
@@ -750,6 +753,7 @@ class Nonlinear_elliptic3d(_GPEquation):
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
         """kernel_parameter: sigma (Gaussian) or three length scales (anisotropic_Gaussian); stores the trace ratio in `ratio`"""
+        require_gaussian_family(kernel, 'Nonlinear_elliptic3d')
         if nugget_type not in ('adaptive', 'identity', 'none'):
             raise AttributeError(f"nugget_type {nugget_type!r}: adaptive, identity or none")
         ctx = get_context()
