@@ -98,7 +98,8 @@ int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 int gpk_assemble(gpk_handle h, int layout, int kernel, const double* host_kparams,
                  const double* Xd, int Nd, const double* Xb, int Nb,
                  double nugget, int nugget_type, double* Theta, int ld, double* host_ratios);
-/* construct_Theta_test (src/Gram_matrice.py:190-289): out is Nt x N row-major. */
+/* construct_Theta_test (src/Gram_matrice.py:190-289): out is Nt x N row-major.
+ *      ld >= N (N as for gpk_assemble), else -9001 and nothing is written, as for NULL pointers and Nt <= 0. */
 int gpk_assemble_test(gpk_handle h, int layout, int kernel, const double* host_kparams,
                       const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb,
                       double* out, int ld);

@@ -412,9 +412,14 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
 
 extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const double* kp, const double* Xt, int Nt,
                                  const double* Xd, int Nd, const double* Xb, int Nb, double* out, int ld) {
-    if (!h || !out || !Xt || Nt <= 0) return GPK_ERR_ARG;
+    if (!h) return GPK_ERR_ARG;
+    if (!out || !Xt) return gpk_bad_arg(h, "assemble_test: pointers");
+    if (Nt <= 0) return gpk_bad_arg(h, "assemble_test: Nt <= 0");
     AsmArgs g{};
     GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    int N = 0;
+    with_layout(layout, [&](auto l) { N = lay_N<decltype(l)::value>(Nd, Nb); });
+    if (ld < N) return gpk_bad_arg(h, "assemble_test: ld < N");      // (rows would overlap and the last one leave the Nt x ld region)
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
     if (const int matern = matern_order(kernel)) gpk_i_matern_test(matern, layout, h->stream, g);

@@ -1,7 +1,9 @@
 """GPU parity tests: every entry point of the C ABI (include/gpk.h) against the CPU oracle on identical inputs.
 
 Tolerances (fp64 everywhere):
-  * Gram blocks: |GPU - oracle| <= 4e-15 * max|block|  (one exp + Hermite prefactors; ocml exp vs glibc exp <= 1 ulp)
+  * Gram blocks: |GPU - oracle| <= 4e-15 * max|block|, block by block (one exp + Hermite prefactors; ocml exp vs glibc exp <= 1 ulp;
+    gate_blocks of tests/_gauss_reference.py -- the blocks of one Theta have maxima from 1 to 1.9e6, a bound scaled by the whole
+    matrix would let an error of 1e-9 in the value block pass)
   * GEMM/SYRK: 1e-13 relative to |A||B| row sums (summation order differs: MFMA k-chunks of 4)
   * POTRF / TRSM: backward-error style, ||L L^T - A|| <= 1e-13 ||A||, ||L X - B|| <= 1e-12 ||L|| ||X||
   * Gauss-Newton: solution vectors rel-L2 <= 1e-6 vs oracle / reference fixtures (the north-star bound);
@@ -15,6 +17,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import gp_oracle as O
+
+from _gauss_reference import gate_blocks, offsets
 
 G = os.path.join(os.path.dirname(__file__), 'golden')
 EQN = {'elliptic': 'Nonlinear_elliptic', 'burgers': 'Burgers', 'eikonal': 'Eikonal', 'darcy': 'Darcy_flow2d'}
@@ -51,11 +55,12 @@ def test_assemble_matches_reference_fixtures(ctx):
             T, _ = ctx.assemble(lay, kernel, kp, Xd, Xb)
             got = T.download()
             assert got.shape == want.shape
-            assert np.max(np.abs(got - want)) <= 4e-15 * np.max(np.abs(want)), (name, lay)
+            blocks = offsets(lay, Xd.shape[0], Xb.shape[0])
+            gate_blocks(got, want, None, blocks, blocks, (name, lay))
             assert np.array_equal(got, got.T), (name, lay, 'symmetry')
             want_t = d[f'{name}__{key}_test']
             got_t = ctx.assemble_test(lay, kernel, kp, Xt, Xd, Xb).download()
-            assert np.max(np.abs(got_t - want_t)) <= 4e-15 * np.max(np.abs(want_t)), (name, lay, 'test')
+            gate_blocks(got_t.reshape(want_t.shape), want_t, None, [(0, want_t.shape[0])], blocks, (name, lay, 'test'))
 
 
 @pytest.mark.parametrize('eqn,kernel,kp,Nd,Nb', [
@@ -76,7 +81,7 @@ def test_assemble_vs_oracle_with_nugget(ctx, eqn, kernel, kp, Nd, Nb):
             want, ratios = O.add_nugget(Tref, lay, Nd, Nb, 1e-3, ntype)
             Td, r = ctx.assemble(lay, kernel, kp, Xd, Xb, 1e-3, ntype)
             got = Td.download()
-            assert np.max(np.abs(got - want)) <= 4e-15 * np.max(np.abs(want)), (lay, ntype)
+            gate_blocks(got, want, None, offsets(lay, Nd, Nb), offsets(lay, Nd, Nb), (lay, ntype))
             if ntype == 'adaptive' and ratios:
                 np.testing.assert_allclose(r[:len(ratios)], ratios, rtol=1e-14)
 
@@ -519,4 +524,4 @@ def test_assembly_two_points_per_lane_is_bit_identical(ctx, layout, kernel, kp):
     ref = O.gram_matrix_assembly(Xd, Xb, eqn, kernel, kp)
     ref = ref[1] if layout == 'Darcy_a' else ref
     want, _ = O.add_nugget(ref, layout, Nd, Nb, 1e-6)
-    assert np.max(np.abs(got[0] - want)) <= 4e-15 * np.max(np.abs(want))
+    gate_blocks(got[0], want, None, offsets(layout, Nd, Nb), offsets(layout, Nd, Nb), layout)

@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from _gauss_reference import gate_blocks, offsets
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,10 +41,12 @@ def test_gram_matrix_assembly_function(solves):
     d = np.load(os.path.join(G, 'theta_small.npz'))
     n = 'darcy_gauss'
     Tu, Ta = Gram_matrix_assembly(d[n + '__Xd'], d[n + '__Xb'], eqn='Darcy_flow2d', kernel='Gaussian', kernel_parameter=0.2)
-    assert np.max(np.abs(Tu - d[n + '__Theta_u'])) <= 4e-15 * np.max(np.abs(Tu))
-    assert np.max(np.abs(Ta - d[n + '__Theta_a'])) <= 4e-15 * np.max(np.abs(Ta))
+    Nd, Nb, Nt = d[n + '__Xd'].shape[0], d[n + '__Xb'].shape[0], d[n + '__Xt'].shape[0]
+    bu, ba = offsets('Darcy_u', Nd, Nb), offsets('Darcy_a', Nd, Nb)
+    gate_blocks(Tu, d[n + '__Theta_u'], None, bu, bu, 'Theta_u')       # (per block: 4e-15 max|block|)
+    gate_blocks(Ta, d[n + '__Theta_a'], None, ba, ba, 'Theta_a')
     Ttu, Tta = construct_Theta_test(d[n + '__Xt'], d[n + '__Xd'], d[n + '__Xb'], eqn='Darcy_flow2d')
-    assert np.max(np.abs(Ttu - d[n + '__Theta_u_test'])) <= 4e-15 * np.max(np.abs(Ttu))
+    gate_blocks(Ttu, d[n + '__Theta_u_test'], None, [(0, Nt)], bu, 'Theta_u_test')
     assert Gram_matrix_assembly(d[n + '__Xd'], d[n + '__Xb'], eqn='nonsense') is None       # reference falls through
 
 
