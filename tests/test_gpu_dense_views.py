@@ -22,6 +22,8 @@ Bounds: the ones the project states in tests/test_gpu_parity.py, the same for ev
 L is well conditioned (tril(randn) + diag(U(3, 4) sqrt n), as in test_trsm) so that the residual bounds are sharp.
 Orders follow the dispatch conditions of csrc/gpk_factor.hip: the 256-row strip kernel (n <= 256, n % 16 == 0), the 64-row base kernel,
 the recursion above them, the transposed and right-side base kernels, the single-vector kernel (nrhs == 1, ldb == 1).
+The tight, entry-by-entry gates of the same routines (componentwise backward error on Gram and row-scaled matrices) live in
+tests/test_gpu_dense_componentwise.py; the subject here is views and canaries, so the norm-wise bounds above are kept.
 """
 import ctypes as C
 import functools
