@@ -461,6 +461,32 @@ int gpk_posterior_prepare(gpk_handle h, const gpk_gn_problem* host_prob, const d
 int gpk_posterior_variance(gpk_handle h, const gpk_gn_problem* host_prob, const double* P, int ldp, const double* R, int ldr, int field,
                            double* K, int ldk, int nt, double* W, int ldw, double* var_cond, double* var);
 
+/* ---- Log evidence of a factored problem at its Gauss-Newton iterate, Laplace form ("Log evidence").
+ *      No reference call site: the reference takes the kernel parameter by hand.  With F(z) the stacked measurement vector (s_rows),
+ *      A = dF/dz at the final iterate z*, L_k L_k^T = Theta_k for each factor (one; L_a and L_u for GPK_GN_DARCY),
+ *      J(z) = sum_k ||L_k^{-1} F_k(z)||^2 (+ Darcy: ||v0[:N_data] - data||^2 / gamma^2, what gpk_gn_loss returns) and
+ *      H/2 = A^T Theta^{-1} A = R R^T (what gpk_posterior_prepare forms, Darcy's data rows kept in), the Laplace approximation of
+ *      the integral of N(F(z); 0, Theta) over z around z* is
+ *        log Z = -J(z*)/2 - sum_k sum_i log (L_k)_ii - sum_i log R_ii - N_data log gamma - (s_rows - nz)/2 log 2 pi,
+ *      s_rows - nz = N_d + N_b (+ N_data) being the number of data values f, g (and observations).  When F is affine in z this is exact:
+ *      |Theta| |A^T Theta^{-1} A| = |Theta_dd| makes it the Gaussian log likelihood of the data rows d under their own block Theta_dd,
+ *      whatever z.  Bad arguments: -9001, named in gpk_last_error. */
+/* *host_logdet = 2 sum_i log L_ii = log |L L^T| of the n x n lower factor L (ld ldl >= n, any alignment); only the diagonal is read
+ * (stride ldl + 1).  *host_bad = the number of diagonal entries that are not > 0 (NaN included); the sum is then what IEEE arithmetic
+ * gives (log 0 = -inf, log of a negative number = NaN).  Fixed reduction order -- strided partial sums per lane, wave shuffles, LDS
+ * across the waves of a workgroup, the workgroups' partial sums added in index order -- and no atomics: a repeated call and a fresh handle
+ * give the same bits.  Synchronises, as gpk_gn_loss.  Uses the handle's workspace for the partial sums. */
+int gpk_chol_logdet(gpk_handle h, const double* L, int n, int ldl, double* host_logdet, int* host_bad);
+/* gpk_gn_loss (work: s_rows doubles), gpk_posterior_prepare into the caller's P / R (sizes and leading dimensions:
+ * gpk_posterior_worksize) and gpk_chol_logdet's reduction over every factor and over R.
+ *   host_terms[6] = { log Z,  J(z),  sum_k log |Theta_k|,  log |H/2|,  N_data log gamma,  (s_rows - nz)/2 log 2 pi },
+ *   log Z = -(terms[1] + terms[2] + terms[3]) / 2 - terms[4] - terms[5].
+ * *host_info is prepare's; if it is non-zero, or a diagonal entry of a factor or of R is not > 0, log Z is NaN -- the call still returns 0
+ * and the other five terms are what the arithmetic gave.  P and R are left exactly as gpk_posterior_prepare leaves them (a following
+ * gpk_posterior_variance may use them).  GPK_GN_ELLIPTIC_RELAXED is not served (-9001, prepare's message). */
+int gpk_log_evidence(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, double* P, int ldp, double* R, int ldr,
+                     double* work, double* host_terms, int* host_info);
+
 /* Development switches, phase stamps, probes and the micro-benchmarks behind the roofline denominators: include/gpk_debug.h. */
 
 #ifdef __cplusplus

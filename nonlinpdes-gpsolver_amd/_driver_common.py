@@ -29,6 +29,10 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     parser.add_argument("--test_residual", type=bool, default=False)
     # opt-in: also print the posterior standard deviation of the solution on the test grid (Gauss-Newton / Laplace form)
     parser.add_argument("--test_variance", type=bool, default=False)
+    # opt-in: choose --kernel_parameter among these by the Laplace log evidence (solver_GP.select_kernel_parameter): a comma-separated
+    # list of scalars, or per-axis groups separated by ';' ("0.3,0.05;0.2,0.05"); --select_refine K: K golden-section steps (scalars only)
+    parser.add_argument("--select_kernel_parameter", type=str, default=None)
+    parser.add_argument("--select_refine", type=int, default=0)
 
 
 NL_DEFAULTS = {'exp': (-1.0, 1.0), 'sinh': (1.0, 1.0), 'sin': (1.0, 1.0), 'cubic': (-1.0, 0.0, 1.0)}
@@ -94,6 +98,27 @@ def seed_from(cfg):
     print(f"[Seeds] random seeds: {cfg.randomseed}")
 
 
+def kernel_candidates(text):
+    """--select_kernel_parameter: "0.1,0.2,0.3" -> [0.1, 0.2, 0.3]; "0.3,0.05;0.2,0.05" -> [[0.3, 0.05], [0.2, 0.05]]"""
+    try:
+        groups = [[float(v) for v in g.split(',') if v.strip()] for g in text.split(';') if g.strip()]
+    except ValueError as e:
+        raise SystemExit(f'--select_kernel_parameter: {e}')
+    if not groups or not all(groups):
+        raise SystemExit('--select_kernel_parameter: no candidates')
+    return groups if ';' in text else groups[0]
+
+
+def solve_or_select(cfg, solver, **solve_kwargs):
+    """solver.solve(), or with --select_kernel_parameter the search over its candidates, which leaves the solver solved at the winner"""
+    if getattr(cfg, 'select_kernel_parameter', None):
+        # (its lines are what the flag asks for: printed whatever --print_hist says)
+        solver.select_kernel_parameter(kernel_candidates(cfg.select_kernel_parameter), refine=cfg.select_refine,
+                                       method=solve_kwargs.get('method', 'elimination'), print_option=True)
+    else:
+        solver.solve(**solve_kwargs)
+
+
 def solve_forward(cfg, pde_type, bdy, rhs, domain, solve_kwargs=None, verbose=None):
     """The part every forward-problem driver shares: solver, equation, collocation points, Gauss-Newton solve (+ figures)."""
     import numpy as onp
@@ -105,7 +130,7 @@ def solve_forward(cfg, pde_type, bdy, rhs, domain, solve_kwargs=None, verbose=No
     solver.auto_sample(cfg.N_domain, cfg.N_boundary, sampled_type=cfg.sampled_type, **kw)
     if show:
         solver.show_sample()
-    solver.solve(**dict(solve_kwargs or {}, **kw))
+    solve_or_select(cfg, solver, **dict(solve_kwargs or {}, **kw))
     if show:
         solver.show_loss_hist()
     return solver, show

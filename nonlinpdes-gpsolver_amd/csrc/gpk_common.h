@@ -17,6 +17,7 @@
 #define GPK_ERR_NODEV (-9002)
 
 constexpr int GPK_MAX_TRSV_BLOCKS = 4096;
+constexpr int GPK_SCALARS_EVIDENCE = 16;         // first of the 6 slots of gpk_ctx::d_scalars that gpk_evidence.hip owns
 
 // Piecewise-linear leading-zero profile ("staircase") of a block of right-hand sides: column c (storage order) is known to be zero
 // above row first_row(c).  Segment s covers the columns [c1[s-1], c1[s]) (c1[-1] = 0) with first_row(c) = a[s] + (b[s] - c) / sd[s]
@@ -164,7 +165,9 @@ struct gpk_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int* d_info = nullptr;          // device int: first non-positive pivot (1-based), 0 = none
-    double* d_scalars = nullptr;    // small device scratch for reductions (16 doubles)
+    double* d_scalars = nullptr;    // small device scratch for reductions (64 doubles).  Slots: [0] in-step loss / border pivot, [1] gpk_gn_loss,
+                                    // [2..3] gpk_error_metrics, [8] exact in-step loss (and the development micro-benchmarks),
+                                    // [GPK_SCALARS_EVIDENCE .. + 5] the (log-determinant, bad-pivot count) pairs of gpk_evidence.hip
     double* h_pinned = nullptr;     // 8 doubles of pinned host memory: where the end-of-step scalars (loss, pivot status) land -- a copy into
                                     // pageable memory goes through a staging buffer and a second synchronisation
     int* d_flags = nullptr;         // per-block "solved" epochs of the fused single-vector triangular solve (GPK_MAX_TRSV_BLOCKS ints)

@@ -36,6 +36,7 @@ def dinv_block_for(n):
     return db
 SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4}
 NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
+EVIDENCE_TERMS = ('log_Z', 'J', 'logdet_theta', 'logdet_H', 'gamma_term', 'two_pi_term')   # host_terms[6] of gpk_log_evidence
 
 
 def pad_ld(n, mult=16):
@@ -724,6 +725,27 @@ class Context:
         for a in (K, W, vc, v, dXt, dXd, dXb):
             a.free()
         return out
+
+    # ---- log evidence (gpk_chol_logdet, gpk_log_evidence) ----
+    def chol_logdet(self, L, n=None):
+        """(log |L L^T|, bad) of the lower factor in the DeviceArray L: 2 sum_i log L_ii over its diagonal and the number of diagonal
+        entries that are not > 0 (gpk_chol_logdet).  Fixed reduction order: the same bits on every call."""
+        n = L.rows if n is None else int(n)
+        value, bad = C.c_double(), C.c_int()
+        self._chk(self.lib.gpk_chol_logdet(self.h, L.ptr, n, L.ld, C.byref(value), C.byref(bad)))
+        return value.value, bad.value
+
+    def log_evidence(self, prob, z):
+        """Laplace log evidence at the iterate z (DeviceArray): (terms, P, R, info) with terms = dict(log_Z, J, logdet_theta, logdet_H,
+        gamma_term, two_pi_term), log_Z = -(J + logdet_theta + logdet_H) / 2 - gamma_term - two_pi_term (NaN when info != 0 or a pivot of a
+        factor is not > 0), and P, R, info exactly those of posterior_prepare (gpk_log_evidence)."""
+        ws = self.posterior_worksize(prob, 1)
+        P = DeviceArray(self, prob.rows, prob.nz + 1, ld=ws['ldp'])
+        R = DeviceArray(self, prob.nz, prob.nz, ld=ws['ldr'])
+        _, _, _, work = prob.workspace()
+        terms, info = (C.c_double * 6)(), C.c_int()
+        self._chk(self.lib.gpk_log_evidence(self.h, C.byref(prob.struct), z.ptr, P.ptr, P.ld, R.ptr, R.ld, work.ptr, terms, C.byref(info)))
+        return dict(zip(EVIDENCE_TERMS, (float(t) for t in terms))), P, R, self._chk_info(info.value)
 
     # ---- per-phase timing of gn_step ----
     def prof_enable(self, on=True):

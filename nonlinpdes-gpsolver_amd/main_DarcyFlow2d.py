@@ -6,7 +6,7 @@ import argparse
 import numpy as onp
 from scipy.interpolate import griddata
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, report_test_residual, report_test_variance, seed_from, tensor_grid
+from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, report_test_residual, report_test_variance, seed_from, solve_or_select, tensor_grid
 from reference_solver.FD_for_Darcy_flow import FD_Darcy_flow_2d
 from src.solver import solver_GP
 
@@ -54,7 +54,7 @@ def main(argv=None):
     observed = griddata((XX.flatten(), YY.flatten()), u_grid.reshape(-1, 1), (Xo[:, 0], Xo[:, 1]), method='linear')[:, 0]
     solver.get_observed_data(observed, cfg.noise_level)
 
-    solver.solve()
+    solve_or_select(cfg, solver)
     if show:
         solver.show_loss_hist()
 

@@ -121,6 +121,7 @@ class Darcy_flow2d(_GPEquation):
         return self._hessian(z_old)
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         sol = self._initial(initial_sol, 6 * self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist, check_nan=False)

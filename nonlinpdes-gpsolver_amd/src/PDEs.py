@@ -212,6 +212,10 @@ class _GPEquation(object):
 
     # ---- Gauss-Newton ----------------------------------------------------------------------------------------------
     def _initial(self, initial_sol, n):
+        if isinstance(initial_sol, onp.ndarray):               # a given iterate (solver_GP.select_kernel_parameter: one draw for every candidate)
+            if initial_sol.shape != (n,):
+                raise ValueError(f'initial_sol: {initial_sol.shape} values for {n} unknowns')
+            return onp.array(initial_sol, dtype=onp.float64)
         if initial_sol == 'rdm':
             return random.normal(0.0, 1.0, (n))
         raise UnboundLocalError("local variable 'sol' referenced before assignment")   # as the reference
@@ -376,6 +380,35 @@ class _GPEquation(object):
         self.extended_var = v
         self.extended_std = onp.sqrt(onp.maximum(v, 0.0))
         return self.extended_var
+
+    # ---- log evidence of the kernel at the final iterate (gpk_log_evidence) ----------------------------------------------------------
+    def log_evidence(self):
+        """Laplace approximation of the log evidence log Z of the data f, g (Darcy: and the observations) under the kernel the Gram
+        matrix was built with, at the final iterate z* of GN_method ("Log evidence"):
+            log Z = -J(z*)/2 - sum_k log|Theta_k|/2 - log|H/2|/2 - N_data log gamma - (N_d + N_b + N_data)/2 log 2 pi.
+        Sets log_evidence_terms (log_Z, J, logdet_theta, logdet_H, gamma_term, two_pi_term, info) and returns log Z -- NaN when the
+        factorisation of H/2 fails (info != 0) or a pivot of a factor is not positive.  Served for every class whose Gauss-Newton system
+        gpk_posterior_prepare serves, bc= / operator= and Nonlinear_elliptic3d included (their system is the elliptic one on their own
+        Theta); NotImplementedError after GN_relaxed_method.  P = L^{-1} A(z*) and the factor of H/2 are kept where posterior_variance
+        looks for them, so a following posterior_variance does not prepare again."""
+        star = self.__dict__.get('_z_star')
+        if star is None:
+            raise RuntimeError('log_evidence: call GN_method() first')
+        prob, z = star
+        if prob.struct.system == gpk.SYSTEM['Nonlinear_elliptic_relaxed']:
+            raise NotImplementedError('log_evidence: the relaxed formulation (GN_relaxed_method) has no evidence entry point '
+                                      '(gpk_log_evidence returns -9001 for GPK_GN_ELLIPTIC_RELAXED); solve with GN_method')
+        ctx = get_context()
+        dz = ctx.array(z)
+        terms, P, R, info = ctx.log_evidence(prob, dz)
+        dz.free()
+        if info != 0:                                          # (what _posterior_state says when it prepares: the slot is filled here)
+            print('[Warning] Cholesky factorization of the Gauss-Newton matrix at the final iterate met a non-positive pivot at index',
+                  info, ': the log evidence and the posterior variance are not defined there')
+        self._drop_posterior()
+        self._posterior = (P, R, info, prob)
+        self.log_evidence_terms = dict(terms, info=info)
+        return terms['log_Z']
 
 
 class Nonlinear_elliptic2d(_GPEquation):
@@ -578,6 +611,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         return self._hessian(z_old)          # hessian(GN_loss)(z, z_old) does not depend on z (quadratic in z)
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         sol = self._initial(initial_sol, self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
@@ -612,6 +646,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         return get_context().gn_hessian_grad(self._relaxed_problem(pen_lambda), self._z(z_old))[0]
 
     def GN_relaxed_method(self, max_iter=3, step_size=1, initial_sol='rdm', pen_lambda=1e-10, print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         print(f'Relaxed approach: penalization parameter = {pen_lambda}')
         sol = self._initial(initial_sol, 2 * self.N_domain)
         self.init_sol = sol
@@ -777,6 +812,7 @@ class Nonlinear_elliptic3d(_GPEquation):
         return self._hessian(z_old)          # quadratic in z, as in two dimensions
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         sol = self._initial(initial_sol, self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
@@ -891,6 +927,7 @@ class Burgers(_GPEquation):
         return self._hessian(z)
 
     def GN_method(self, max_iter=10, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         sol = self._initial(initial_sol, 3 * self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
@@ -930,11 +967,12 @@ class Eikonal(_GPEquation):
         return self._hessian(z_old)
 
     def _initial(self, initial_sol, n):
-        if initial_sol == 'zero':
+        if isinstance(initial_sol, str) and initial_sol == 'zero':
             return onp.zeros(n)
         return super()._initial(initial_sol, n)
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw) or 'zero', or an ndarray with one value per unknown: the iterate to start from."""
         sol = self._initial(initial_sol, 3 * self.N_domain)
         self.init_sol = sol
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)

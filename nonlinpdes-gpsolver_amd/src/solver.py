@@ -144,6 +144,9 @@ _LOG = {
     'var_n': '[Testing posterior variance...] Number of test points: {n}',
     'var_mean': '[Test variance] Mean posterior std{tag} {v}',
     'var_max': '[Test variance] Max posterior std{tag} {v}',
+    'evidence': '[Log evidence] log Z {v}, J {J}, log|Theta| {lt}, log|H/2| {lh}',
+    'sel_row': '[Kernel selection] kernel_parameter {p}{how}: log Z {v}, J {J}, info (Cholesky, Gauss-Newton, H/2) {info}',
+    'sel_best': '[Kernel selection] chosen kernel_parameter {p}, log Z {v}{note}',
 }
 
 
@@ -220,6 +223,94 @@ class solver_GP(object):
         elif method == 'relaxation':
             eqn.GN_relaxed_method(pen_lambda=pen_lambda, **gn)
         _say(print_option, 'gn_done')
+
+    # ---- model evidence of the kernel parameter (eqn.log_evidence; no counterpart in the reference) ------------------------------------
+    def log_evidence(self, print_option=True):
+        """Laplace log evidence of the solved problem under cfg.kernel / cfg.kernel_parameter (eqn.log_evidence): returns log Z, the
+        terms are in eqn.log_evidence_terms.  Needs solve(method='elimination')."""
+        v = self.eqn.log_evidence()
+        t = self.eqn.log_evidence_terms
+        _say(print_option, 'evidence', v=v, J=t['J'], lt=t['logdet_theta'], lh=t['logdet_H'])
+        return v
+
+    def _evidence_at(self, parameter, initial, how, print_option):
+        """Gram matrix, Cholesky, GN_method (cfg's settings, the given initial iterate) and log evidence at one kernel parameter: one
+        row of kernel_selection"""
+        c, eqn = self.config, self.eqn
+        eqn.Gram_matrix(kernel=c.kernel, kernel_parameter=parameter, nugget=c.nugget, nugget_type=c.nugget_type)
+        eqn.Gram_Cholesky()
+        chol = int(onp.max(onp.abs(onp.atleast_1d(eqn.chol_info))))   # (Darcy: one status per factor)
+        row = dict(parameter=parameter, log_Z=float('nan'), J=float('nan'), info=(chol, None, None), initial=initial, refined=bool(how))
+        if chol == 0:                                               # (a failed factor: nothing downstream of it is defined)
+            eqn.GN_method(max_iter=c.GNsteps, step_size=c.step_size, initial_sol=c.initial_sol if initial is None else initial,
+                          print_hist=False)
+            row['initial'] = eqn.init_sol
+            log_Z = eqn.log_evidence()
+            t = eqn.log_evidence_terms
+            row.update(log_Z=float(log_Z), J=t['J'], info=(chol, max([0] + [int(i) for i in eqn.step_info]), int(t['info'])))
+        row['ok'] = row['info'] == (0, 0, 0) and not onp.isnan(row['log_Z'])
+        _say(print_option, 'sel_row', p=parameter, how=how, v=row['log_Z'], J=row['J'], info=row['info'])
+        return row
+
+    def select_kernel_parameter(self, candidates, refine=0, method='elimination', print_option=True):
+        """Choose cfg.kernel_parameter among `candidates` -- scalars, or per-axis lists for the anisotropic and per-axis Matern forms --
+        by the Laplace log evidence (eqn.log_evidence).  Every candidate is solved with cfg's settings (Gram_matrix, Gram_Cholesky,
+        GN_method) from ONE initial iterate, drawn for the first candidate as solve() draws it, so the table does not depend on how many
+        candidates there are.  A candidate whose Cholesky factorisation (chol_info), Gauss-Newton steps (any step_info > 0) or
+        factorisation of H/2 fails, or whose log Z is NaN, is listed and never chosen.  refine = k (scalar candidates only, ValueError
+        otherwise): k golden-section steps in log(parameter) between the grid neighbours of the best candidate; skipped, and said so,
+        when the best candidate is an end of the grid.  Sets kernel_selection (candidates, log_Z, J, info, refined, best), sets
+        cfg.kernel_parameter to the winner, leaves the solver solved there (ready for test()) and returns the winner.  The evidence ranks
+        models, not errors."""
+        if method != 'elimination':
+            raise NotImplementedError("select_kernel_parameter: the log evidence is defined for method='elimination' only")
+        cands = [list(map(float, p)) if onp.ndim(p) else float(p) for p in candidates]
+        if not cands:
+            raise ValueError('select_kernel_parameter: no candidates')
+        refine = int(refine)
+        scalar = all(not isinstance(p, list) for p in cands)
+        if refine > 0 and not scalar:
+            raise ValueError('select_kernel_parameter: refine > 0 needs scalar candidates')
+        rows, initial = [], None
+        for p in cands:
+            rows.append(self._evidence_at(p, initial, '', print_option))
+            initial = rows[-1]['initial'] if initial is None else initial
+        value = lambda r: r['log_Z'] if r['ok'] else -onp.inf
+        best = max(range(len(rows)), key=lambda k: value(rows[k]))
+        if not rows[best]['ok']:
+            self.kernel_selection = self._selection_table(rows, None)
+            raise RuntimeError('select_kernel_parameter: no candidate could be solved and factored (kernel_selection has the table)')
+        note = ''
+        if refine > 0:
+            order = sorted(range(len(cands)), key=lambda k: cands[k])
+            at = order.index(best)
+            if at == 0 or at == len(order) - 1:
+                note = ' (an end of the candidate grid: not refined; widen the candidates)'
+            else:
+                # golden section in t = log(parameter) on (a, x, b) with the best value at x: every step evaluates one point of the larger
+                # half and keeps the triple around the best point seen, so the result never leaves the bracket and never gets worse
+                inv_phi2 = (3.0 - 5.0 ** 0.5) / 2.0
+                a, x, b = (float(onp.log(cands[order[k]])) for k in (at - 1, at, at + 1))
+                for _ in range(refine):
+                    t = x + inv_phi2 * (b - x) if b - x >= x - a else x - inv_phi2 * (x - a)
+                    rows.append(self._evidence_at(float(onp.exp(t)), initial, ' (refined)', print_option))
+                    if value(rows[-1]) > value(rows[best]):
+                        a, b = (x, b) if t > x else (a, x)
+                        x, best = t, len(rows) - 1
+                    else:
+                        a, b = (a, t) if t > x else (t, b)
+        winner = rows[best]['parameter']
+        if best != len(rows) - 1:                                    # leave the solver solved at the winner: the same solve again
+            self._evidence_at(winner, initial, '', False)
+        self.config.kernel_parameter = winner
+        self.kernel_selection = self._selection_table(rows, best)
+        _say(print_option, 'sel_best', p=winner, v=rows[best]['log_Z'], note=note)
+        return winner
+
+    @staticmethod
+    def _selection_table(rows, best):
+        return dict(candidates=[r['parameter'] for r in rows], log_Z=onp.array([r['log_Z'] for r in rows]),
+                    J=onp.array([r['J'] for r in rows]), info=[r['info'] for r in rows], refined=[r['refined'] for r in rows], best=best)
 
     # ---- errors (definitions of src/solver.py:175,191: root of the sum of squares over N_domain / N_test), reduced on the device
     # (gpk_error_metrics: |truth - value| per point, its maximum and sqrt(sum of squares / n) in one pass) ------------------------------
