@@ -461,6 +461,36 @@ int gpk_posterior_prepare(gpk_handle h, const gpk_gn_problem* host_prob, const d
 int gpk_posterior_variance(gpk_handle h, const gpk_gn_problem* host_prob, const double* P, int ldp, const double* R, int ldr, int field,
                            double* K, int ldk, int nt, double* W, int ldw, double* var_cond, double* var);
 
+/* ---- Posterior covariance between test points and samples of the posterior ("Posterior covariance and samples").
+ *      No reference call site.  With k_s, k_t the columns of gpk_assemble_cross for the test points x_s, x_t,
+ *        Sigma[s,t] = k(x_s, x_t) - (L^{-1} k_s)^T (L^{-1} k_t) + (L_H^{-1} A^T Theta^{-1} k_s)^T (L_H^{-1} A^T Theta^{-1} k_t),
+ *      whose diagonal is var of the section above.  The value functional, the five kernels of the reference layouts, one batch of test
+ *      points (no blocks between two batches); GPK_GN_ELLIPTIC_RELAXED is not served (-9001).  Bad arguments: -9001, named in gpk_last_error. */
+/* out[i * ld + j] = k(xa_i, xb_j) for the na points Xa and the nb points Xb ((n, 2) row-major, on the device; Xa == Xb allowed), ld >= nb.
+ * host_kparams as for gpk_assemble.  Every entry is computed from its own xa_i - xb_j (nothing is mirrored); k is even in it, so with
+ * Xa == Xb out[i][j] and out[j][i] are the same bits and the diagonal is exactly 1.  Any alignment of out / ld is accepted (16-byte
+ * stores when base, ld and nb allow and gpk_tune key 47 is on; 8-byte stores otherwise, with the same bits); nothing outside the na x nb
+ * view is written.  Write-bound: 8 na nb bytes. */
+int gpk_assemble_prior(gpk_handle h, int kernel, const double* host_kparams, const double* Xa, int na, const double* Xb, int nb,
+                       double* out, int ld);
+/* One batch of nt test points.  On entry C (nt x nt, ld ldc >= nt) holds the prior gpk_assemble_prior(Xt, Xt) and K (N_field x nt, ld
+ * ldk >= nt) the block of gpk_assemble_cross, OVERWRITTEN; W: nz x nt scratch (ld ldw >= nt).  On return
+ *   C = C - V^T V + W^T W,   V = L_field^{-1} K,   W = R^{-1} P_field^T V,
+ * V and W formed by the calls of gpk_posterior_variance (same solve path, same workspace: gpk_posterior_worksize with this nt), the two
+ * products by the routine under gpk_syrk (alpha = -1 / +1, beta = 1, lower triangle), then gpk_symmetrize_lower: both triangles are
+ * written and C[s][t], C[t][s] are the same bits.  with_gn == 0: the conditional covariance C - V^T V alone; P, R and W are not read
+ * and may be NULL.  field as gpk_posterior_variance.  Raw values, nothing is clipped. */
+int gpk_posterior_covariance(gpk_handle h, const gpk_gn_problem* host_prob, const double* P, int ldp, const double* R, int ldr, int field,
+                             double* K, int ldk, int nt, double* W, int ldw, double* C, int ldc, int with_gn);
+/* ns samples of N(mean, C + jitter I) at nt points:  C <- C + jitter I,  C <- its lower Cholesky factor (gpk_potrf, gpk_tril),
+ * out[t * ldo + s] = mean[t] + (L Xi)[t, s]  (out nt x ns, ld ldo >= ns; the product is gpk_gemm with beta = 1 on the broadcast mean).
+ * Xi (nt x ns, ld ldxi >= ns): standard normals SUPPLIED BY THE CALLER -- the library draws nothing, so a sample is a pure function of
+ * its inputs and repeats to the bit.  jitter >= 0 is absolute, in units of the prior variance k(x,x) = 1.  *host_info as gpk_potrf
+ * (may be NULL); the call reads the pivot status back before it writes (it synchronises once): with info != 0 out is left unwritten
+ * and the call returns 0.  C is overwritten either way. */
+int gpk_posterior_sample(gpk_handle h, double* C, int ldc, int nt, double jitter, const double* mean, const double* Xi, int ldxi, int ns,
+                         double* out, int ldo, int* host_info);
+
 /* ---- Log evidence of a factored problem at its Gauss-Newton iterate, Laplace form ("Log evidence").
  *      No reference call site: the reference takes the kernel parameter by hand.  With F(z) the stacked measurement vector (s_rows),
  *      A = dF/dz at the final iterate z*, L_k L_k^T = Theta_k for each factor (one; L_a and L_u for GPK_GN_DARCY),

@@ -31,6 +31,10 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     parser.add_argument("--test_variance", type=bool, default=False)
     # opt-in: choose --kernel_parameter among these by the Laplace log evidence (solver_GP.select_kernel_parameter): a comma-separated
     # list of scalars, or per-axis groups separated by ';' ("0.3,0.05;0.2,0.05"); --select_refine K: K golden-section steps (scalars only)
+    # opt-in: also draw K samples of the solution on the test grid from its joint posterior (solver_GP.test_samples) and print their
+    # spread about the mean; --sample_seed S seeds the standard normals (numpy.random.RandomState(S))
+    parser.add_argument("--posterior_samples", type=int, default=0)
+    parser.add_argument("--sample_seed", type=int, default=None)
     parser.add_argument("--select_kernel_parameter", type=str, default=None)
     parser.add_argument("--select_refine", type=int, default=0)
 
@@ -153,3 +157,9 @@ def report_test_variance(cfg, solver, X_test):
     """--test_variance: the posterior standard deviation of the solution on the driver's test grid (solver_GP.test_variance)"""
     if cfg.test_variance:
         solver.test_variance(X_test)
+
+
+def report_posterior_samples(cfg, solver, X_test):
+    """--posterior_samples K: K draws of the solution on the driver's test grid from its joint posterior (solver_GP.test_samples)"""
+    if getattr(cfg, 'posterior_samples', 0):
+        solver.test_samples(X_test, cfg.posterior_samples, cfg.sample_seed)

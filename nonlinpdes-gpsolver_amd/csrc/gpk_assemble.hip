@@ -208,6 +208,39 @@ __global__ __launch_bounds__(256) void assemble_cross_kernel(AsmArgs g) {
     }
 }
 
+// prior between two point sets (gpk_assemble_prior): out[i * ld + j] = k(xa_i, xb_j), the value functional on both sides.  The shape of
+// assemble_cross_kernel: lanes along j, two columns per lane (16-byte store when WIDE, the same two values as 8-byte stores otherwise),
+// the row point wave-uniform (scalar loads), one exp per pair, a workgroup owns 512 columns x CROSS_TP rows.  Write-bound: 8 na nb bytes.
+// kappa is even in d and every entry is computed from its own d = xa_i - xb_j, with the one fma written out (kappa2_fma): the two
+// columns of a lane and the two triangles of a square call (xa == xb) go through the same roundings, so out[i][j] and out[j][i] are
+// the same bits and the diagonal is exp(-0) = 1.
+__device__ __forceinline__ double prior_value(double p1, double p2, double d1, double d2) {
+    double a[5], b[5];
+    hermite_plain(p1, d1, a);
+    hermite_plain(p2, d2, b);
+    return pair_coeff<F_DELTA, F_DELTA>(a, b) * kappa2_fma(p1, p2, d1, d2);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void assemble_prior_kernel(PriorArgs g) {
+    const int j = 2 * (blockIdx.x * 256 + threadIdx.x);
+    const bool live = j < g.nb;
+    const int jb = min(j + 1, g.nb - 1);                // odd nb: the last lane computes its point twice and stores it once
+    const double y1a = live ? g.xb[2 * j] : 0.0, y2a = live ? g.xb[2 * j + 1] : 0.0;
+    const double y1b = live ? g.xb[2 * jb] : 0.0, y2b = live ? g.xb[2 * jb + 1] : 0.0;
+    const int i0 = blockIdx.y * CROSS_TP;
+    const int iend = min(i0 + CROSS_TP, g.na);
+    for (int i = i0; i < iend; ++i) {
+        const double x1 = g.xa[2 * i], x2 = g.xa[2 * i + 1];   // uniform address -> scalar loads
+        if (!live) continue;
+        const double v0 = prior_value(g.p1, g.p2, x1 - y1a, x2 - y2a);
+        const double v1 = prior_value(g.p1, g.p2, x1 - y1b, x2 - y2b);
+        double* const dst = g.out + (long)i * g.ld + j;
+        if constexpr (WIDE) store2<0>(dst, v0, v1);
+        else { dst[0] = v0; if (j + 1 < g.nb) dst[1] = v1; }
+    }
+}
+
 template <int L, int BJ>
 __device__ __forceinline__ double acc_test(const AsmArgs& g, int q, const double (&a)[5], const double (&b)[5]) {
     return (q < g.size[BJ]) ? pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a, b) * g.coeff[g.off[BJ] + q] : 0.0;
@@ -447,6 +480,30 @@ extern "C" int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const do
         if (wide) assemble_cross_kernel<L, true><<<grid, 256, 0, h->stream>>>(g);
         else assemble_cross_kernel<L, false><<<grid, 256, 0, h->stream>>>(g);
     });
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+// The prior k(xa_i, xb_j) between two sets of points (gpk.h, "Posterior covariance and samples"): no collocation points, no layout.
+extern "C" int gpk_assemble_prior(gpk_handle h, int kernel, const double* kp, const double* Xa, int na, const double* Xb, int nb,
+                                  double* out, int ld) {
+    if (!h) return GPK_ERR_ARG;
+    if (!out || !Xa || !Xb || !kp) return gpk_bad_arg(h, "assemble_prior: pointers");
+    if (na <= 0) return gpk_bad_arg(h, "assemble_prior: na <= 0");
+    if (nb <= 0) return gpk_bad_arg(h, "assemble_prior: nb <= 0");
+    if (ld < nb) return gpk_bad_arg(h, "assemble_prior: ld < nb");
+    PriorArgs g{};
+    double p[2];
+    const int matern = matern_order(kernel);
+    if (matern) GPK_TRY(matern_scales(h, kp, p));
+    else GPK_TRY(precisions(h, "assemble_prior: kernel id", kernel, kp, 2, p));
+    g.p1 = p[0]; g.p2 = p[1];
+    g.xa = Xa; g.na = na; g.xb = Xb; g.nb = nb; g.out = out; g.ld = ld;
+    const bool wide = pairs_eligible(h, out, ld, nb);
+    const dim3 grid(gpk_ceil_div(gpk_ceil_div(nb, 2), 256), gpk_ceil_div(na, CROSS_TP));
+    if (matern) gpk_i_matern_prior(matern, wide, h->stream, g);
+    else if (wide) assemble_prior_kernel<true><<<grid, 256, 0, h->stream>>>(g);
+    else assemble_prior_kernel<false><<<grid, 256, 0, h->stream>>>(g);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

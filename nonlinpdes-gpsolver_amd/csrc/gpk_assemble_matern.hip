@@ -260,6 +260,31 @@ __global__ __launch_bounds__(256) void matern_assemble_cross_kernel(AsmArgs g) {
     }
 }
 
+// ---- prior between two point sets: out[i * ld + j] = k(xa_i, xb_j) (assemble_prior_kernel) ---------------------------------------------
+// Only D[0][0] = G_0 is used, so the rest of matern_partials is dead code here: one sqrt and one exp per pair.  G_0 depends on d through
+// squares alone, so a square call (xa == xb) gives out[i][j] and out[j][i] the same bits, and at d = 0 it is theta_m(0) / theta_m(0) = 1.
+template <int M, bool WIDE>
+__global__ __launch_bounds__(256) void matern_assemble_prior_kernel(PriorArgs g) {
+    const int j = 2 * (blockIdx.x * 256 + threadIdx.x);
+    const bool live = j < g.nb;
+    const int jb = min(j + 1, g.nb - 1);                // odd nb: the last lane computes its point twice and stores it once
+    const double y1a = live ? g.xb[2 * j] : 0.0, y2a = live ? g.xb[2 * j + 1] : 0.0;
+    const double y1b = live ? g.xb[2 * jb] : 0.0, y2b = live ? g.xb[2 * jb + 1] : 0.0;
+    const int i0 = blockIdx.y * CROSS_TP;
+    const int iend = min(i0 + CROSS_TP, g.na);
+    for (int i = i0; i < iend; ++i) {
+        const double x1 = g.xa[2 * i], x2 = g.xa[2 * i + 1];   // uniform address -> scalar loads
+        if (!live) continue;
+        double D0[5][5], D1[5][5];
+        matern_partials<M>(g.p1, g.p2, x1 - y1a, x2 - y2a, D0);
+        matern_partials<M>(g.p1, g.p2, x1 - y1b, x2 - y2b, D1);
+        const double v0 = pair_coeff_m<F_DELTA, F_DELTA>(D0), v1 = pair_coeff_m<F_DELTA, F_DELTA>(D1);
+        double* const dst = g.out + (long)i * g.ld + j;
+        if constexpr (WIDE) store2<0>(dst, v0, v1);
+        else { dst[0] = v0; if (j + 1 < g.nb) dst[1] = v1; }
+    }
+}
+
 // ---- extension: out[t] = sum_c Theta_test[t, c] * coeff[c] (extend_kernel) --------------------------------------------------------------
 template <int L, int BJ>
 __device__ __forceinline__ double acc_test(const AsmArgs& g, int q, const double (&D)[5][5]) {
@@ -370,6 +395,15 @@ void gpk_i_matern_cross(int m, int layout, bool wide, hipStream_t st, const AsmA
         constexpr int M = decltype(mm)::value, L = decltype(l)::value;
         if (wide) matern_assemble_cross_kernel<M, L, true><<<grid, 256, 0, st>>>(g);
         else matern_assemble_cross_kernel<M, L, false><<<grid, 256, 0, st>>>(g);
+    });
+}
+
+void gpk_i_matern_prior(int m, bool wide, hipStream_t st, const PriorArgs& g) {
+    const dim3 grid(gpk_ceil_div(gpk_ceil_div(g.nb, 2), 256), gpk_ceil_div(g.na, CROSS_TP));
+    with_order(m, [&](auto mm) {
+        constexpr int M = decltype(mm)::value;
+        if (wide) matern_assemble_prior_kernel<M, true><<<grid, 256, 0, st>>>(g);
+        else matern_assemble_prior_kernel<M, false><<<grid, 256, 0, st>>>(g);
     });
 }
 

@@ -36,6 +36,14 @@ struct FnArgs {
     double* out; long ldo;
 };
 
+// the prior between two point sets (gpk_assemble_prior): out[i * ld + j] = k(xa_i, xb_j), both (n, 2) row-major; p1, p2 as in AsmArgs
+struct PriorArgs {
+    const double* xa; int na;
+    const double* xb; int nb;
+    double p1, p2;
+    double* out; long ld;
+};
+
 constexpr int CROSS_TP = 8;               // column points per workgroup: the grid is N_t / 512 wide, so the rows supply the parallelism
 
 // f(std::integral_constant<int, L>) for the layout id: the one place that turns it into a template argument; false: not a layout
@@ -72,6 +80,7 @@ inline int matern_scales(gpk_handle h, const double* kp, double (&r)[2]) {
 void gpk_i_matern_gram(int m, int layout, bool pairs, int nt, hipStream_t st, const gpk_asm::AsmArgs& g);
 void gpk_i_matern_test(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
 void gpk_i_matern_cross(int m, int layout, bool wide, hipStream_t st, const gpk_asm::AsmArgs& g);
+void gpk_i_matern_prior(int m, bool wide, hipStream_t st, const gpk_asm::PriorArgs& g);   // (no layout: the value functional on both sides)
 void gpk_i_matern_extend(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
 void gpk_i_matern_extend_fn(int m, int layout, int mask, hipStream_t st, const gpk_asm::FnArgs& g);
 // value of <f_b, f_b> at d = 0 for the blocks of the layout (analytic host values, as diag_values of the Gaussian family)

@@ -9,6 +9,9 @@
 //
 //   gpk_posterior_prepare    once per iterate:  P = L^{-1} A(z) (every row group with its own factor),  R = chol(P^T P)
 //   gpk_posterior_variance   per batch of nt test points:  V = L_f^{-1} K,  W = R^{-1} (P_f^T V),  column sums of squares of V and W
+//   gpk_posterior_covariance the same V and W kept whole:  C <- C - V^T V + W^T W on the prior block of gpk_assemble_prior (nt x nt)
+//   gpk_posterior_sample     out = mean 1^T + chol(C + jitter I) Xi with the caller's standard normals Xi ("Posterior
+//                            covariance and samples")
 //
 // H/2 is formed as P^T P with the rows that have no factor (Darcy's data misfit, 1 / gamma) kept in P: the product
 // gpk_gn_hessian_grad issues on the same block, without its border column and without the factor 2.
@@ -136,6 +139,28 @@ size_t variance_red_bytes(int nf, int nz, int nt) {
     return a > b ? a : b;
 }
 
+// ---- the two kernels of gpk_posterior_sample -----------------------------------------------------------------------------------------------
+// C[i][i] += jitter: one lane per diagonal entry (stride ldc + 1)
+__global__ __launch_bounds__(256) void diag_shift_kernel(double* __restrict__ C, int n, long ldc, double jitter) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) C[(long)i * (ldc + 1)] += jitter;
+}
+
+// out[t][s] = mean[t]: a lane owns two adjacent columns of one row -- one 16-byte store when WIDE (base 16-byte aligned, ldo and ns even),
+// the same values as 8-byte stores otherwise.  npair = ceil(ns / 2) lanes per row.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void bcast_rows_kernel(const double* __restrict__ mean, int nt, int ns, int npair, double* __restrict__ out,
+                                                         long ldo) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)nt * npair) return;
+    const int t = (int)(idx / npair), s = 2 * (int)(idx % npair);
+    const double m = mean[t];
+    double* const dst = out + (long)t * ldo + s;
+    if constexpr (WIDE) *reinterpret_cast<d2*>(dst) = (d2){m, m};
+    else { dst[0] = m; if (s + 1 < ns) dst[1] = m; }
+}
+
 }  // namespace
 
 extern "C" int gpk_col_sumsq(gpk_handle h, const double* V, int rows, int cols, int ldv, double alpha, const double* base, double* out) {
@@ -261,4 +286,73 @@ extern "C" int gpk_posterior_variance(gpk_handle h, const gpk_gn_problem* p, con
     GPK_TRY(gpk_i_gemm(h, true, false, d.nz, nt, g.n, 1.0, P + (long)g.off * ldp, ldp, V, ldk, 0.0, W, ldw, false));
     GPK_TRY(gpk_trsm(h, 0, R, d.nz, ldr, W, nt, ldw));
     return col_sumsq(h, W, d.nz, nt, ldw, 1.0, cond, 0.0, var, scratch);
+}
+
+// C <- C - V^T V (+ W^T W): the products of gpk_posterior_variance kept whole instead of reduced to their column sums of squares.  V and
+// W are formed by the very calls of gpk_posterior_variance; the two products are the routine under gpk_syrk (lower triangle, beta = 1)
+// and ONE gpk_symmetrize_lower at the end copies the finished lower triangle up, so C[s][t] and C[t][s] are the same bits.
+extern "C" int gpk_posterior_covariance(gpk_handle h, const gpk_gn_problem* p, const double* P, int ldp, const double* R, int ldr, int field,
+                                        double* K, int ldk, int nt, double* W, int ldw, double* C, int ldc, int with_gn) {
+    if (!h) return GPK_ERR_ARG;
+    Layout d;
+    GPK_TRY(check_problem(h, p, d));
+    if (field != 0 && field != 1) return gpk_bad_arg(h, "posterior_covariance: field must be 0 (u) or 1 (a)");
+    if (field == 1 && p->system != GPK_GN_DARCY) return gpk_bad_arg(h, "posterior_covariance: field 1 (a) exists for GPK_GN_DARCY only");
+    if (nt <= 0) return gpk_bad_arg(h, "posterior_covariance: nt <= 0");
+    if (!K || ldk < nt) return gpk_bad_arg(h, "posterior_covariance: K / ldk < nt");
+    if (!C || ldc < nt) return gpk_bad_arg(h, "posterior_covariance: C / ldc < nt");
+    if (with_gn && (!P || !R || !W)) return gpk_bad_arg(h, "posterior_covariance: with_gn needs P, R and W");
+    if (with_gn && (ldp < d.nz || ldr < d.nz || ldw < nt)) return gpk_bad_arg(h, "posterior_covariance: ldp / ldr < nz or ldw < nt");
+    const Group& g = d.g[p->system == GPK_GN_DARCY ? 1 - field : 0];
+    const bool dinv = use_dinv(h, p, g);
+    if (dinv && !dinv_block_valid(p->dinv_block)) return gpk_bad_arg(h, "posterior_covariance: dinv_block must be 256, 512, 1024 or 2048");
+    double* ws = nullptr;
+    GPK_TRY(gpk_i_workspace(h, variance_v_bytes(g.n, ldk, dinv), &ws));   // (no reduction scratch: within gpk_posterior_worksize's figure)
+    h->work_sig[0] = -1;
+    // 1. V = L_f^{-1} K
+    const double* V = K;
+    if (dinv) {
+        GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, p->dinv_block, g.n, g.ldl, K, ldk, ws, ldk, nt, GpkLz()));
+        V = ws;
+    } else {
+        GPK_TRY(gpk_trsm(h, 0, g.L, g.n, g.ldl, K, nt, ldk));
+    }
+    // 2. C <- C - V^T V (lower)
+    GPK_TRY(gpk_i_gemm(h, true, false, nt, nt, g.n, -1.0, V, ldk, V, ldk, 1.0, C, ldc, true));
+    if (with_gn) {
+        // 3. W = P_f^T V    4. W <- R^{-1} W    5. C <- C + W^T W (lower)
+        GPK_TRY(gpk_i_gemm(h, true, false, d.nz, nt, g.n, 1.0, P + (long)g.off * ldp, ldp, V, ldk, 0.0, W, ldw, false));
+        GPK_TRY(gpk_trsm(h, 0, R, d.nz, ldr, W, nt, ldw));
+        GPK_TRY(gpk_i_gemm(h, true, false, nt, nt, d.nz, 1.0, W, ldw, W, ldw, 1.0, C, ldc, true));
+    }
+    return gpk_symmetrize_lower(h, C, nt, ldc);
+}
+
+// out = mean 1^T + chol(C + jitter I) Xi.  The normals are the caller's: nothing is drawn here, so a sample is a function of its inputs.
+// The pivot status is read back (one synchronisation) before anything is written to out: a failed factorisation leaves out untouched.
+extern "C" int gpk_posterior_sample(gpk_handle h, double* C, int ldc, int nt, double jitter, const double* mean, const double* Xi, int ldxi,
+                                    int ns, double* out, int ldo, int* host_info) {
+    if (!h) return GPK_ERR_ARG;
+    if (nt <= 0 || ns <= 0) return gpk_bad_arg(h, "posterior_sample: nt / ns <= 0");
+    if (!C || ldc < nt) return gpk_bad_arg(h, "posterior_sample: C / ldc < nt");
+    if (!mean || !Xi || !out) return gpk_bad_arg(h, "posterior_sample: null mean / Xi / out");
+    if (ldxi < ns || ldo < ns) return gpk_bad_arg(h, "posterior_sample: ldxi / ldo < ns");
+    if (!(jitter >= 0.0)) return gpk_bad_arg(h, "posterior_sample: jitter must be >= 0");
+    diag_shift_kernel<<<gpk_ceil_div(nt, 256), 256, 0, h->stream>>>(C, nt, ldc, jitter);
+    GPK_LAUNCH_CHECK(h);
+    GPK_HIP(h, hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
+    GPK_TRY(gpk_i_potrf(h, C, nt, ldc, 0));
+    GPK_TRY(gpk_tril(h, C, nt, ldc));
+    int info = 0;
+    GPK_HIP(h, hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipStreamSynchronize(h->stream));
+    if (host_info) *host_info = info;
+    if (info != 0) return 0;
+    const int npair = gpk_ceil_div(ns, 2);
+    const long lanes = (long)nt * npair;
+    const int grid = (int)((lanes + 255) / 256);
+    if ((ldo % 2 == 0) && (ns % 2 == 0) && (((uintptr_t)out & 15) == 0)) bcast_rows_kernel<true><<<grid, 256, 0, h->stream>>>(mean, nt, ns, npair, out, ldo);
+    else bcast_rows_kernel<false><<<grid, 256, 0, h->stream>>>(mean, nt, ns, npair, out, ldo);
+    GPK_LAUNCH_CHECK(h);
+    return gpk_i_gemm(h, false, false, nt, ns, nt, 1.0, C, ldc, Xi, ldxi, 1.0, out, ldo, false);
 }

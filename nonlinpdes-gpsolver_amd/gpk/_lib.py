@@ -125,6 +125,9 @@ PROTOTYPES = {
     'gpk_posterior_worksize': (_i, [_pp, _i, _i, _i, _i, _pi, _pi, _pi] + [C.POINTER(_sz)] * 5),
     'gpk_posterior_prepare': (_i, [_vp, _pp, _vp, _vp, _i, _vp, _i, _pi]),
     'gpk_posterior_variance': (_i, [_vp, _pp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    'gpk_assemble_prior': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_posterior_covariance': (_i, [_vp, _pp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i]),
+    'gpk_posterior_sample': (_i, [_vp, _vp, _i, _i, _d, _vp, _vp, _i, _i, _vp, _i, _pi]),
     'gpk_chol_logdet': (_i, [_vp, _vp, _i, _i, _pd, _pi]),
     'gpk_log_evidence': (_i, [_vp, _pp, _vp, _vp, _i, _vp, _i, _vp, _pd, _pi]),
     'gpk_tune': (_i, [_vp, _i, _i]),

@@ -726,6 +726,99 @@ class Context:
             a.free()
         return out
 
+    # ---- posterior covariance and samples (gpk_assemble_prior, gpk_posterior_covariance, gpk_posterior_sample) ----
+    def assemble_prior(self, kernel, kernel_parameter, Xa, Xb=None, out=None):
+        """Prior k(xa_i, xb_j) between two sets of 2-D points as an (na, nb) DeviceArray (gpk_assemble_prior).  Xb=None: Xa against
+        itself -- bitwise symmetric, unit diagonal.  out: a DeviceArray to write into (rows >= na, leading dimension >= nb)."""
+        Xa = np.ascontiguousarray(Xa, dtype=np.float64).reshape(-1, 2)
+        dXa = self.points(Xa)
+        if Xb is None:
+            dXb, nb = dXa, Xa.shape[0]
+        else:
+            Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+            dXb, nb = self.points(Xb), Xb.shape[0]
+        Cm = out if out is not None else DeviceArray(self, Xa.shape[0], nb)
+        self._chk(self.lib.gpk_assemble_prior(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXa.ptr, Xa.shape[0],
+                                              dXb.ptr, nb, Cm.ptr, Cm.ld))
+        self.synchronize()
+        for a in {id(dXa): dXa, id(dXb): dXb}.values():
+            a.free()
+        return Cm
+
+    def posterior_covariance(self, prob, P, R, K, Cm, field=0, nt=None, W=None, with_gn=True):
+        """One batch of test points: Cm (nt, nt) holds the prior on entry and C - V^T V (+ W^T W with with_gn) on return, both triangles,
+        bitwise symmetric; K (N_field, nt) from assemble_cross is overwritten (gpk_posterior_covariance).  field: 0 = u, 1 = a (Darcy
+        only).  with_gn=False: P, R and W may be None.  Returns Cm."""
+        nt = K.cols if nt is None else int(nt)
+        if W is None and with_gn:
+            W = DeviceArray(self, prob.nz, nt)
+        opt = lambda a: (a.ptr, a.ld) if a is not None else (None, 0)
+        (pp, ldp), (rp, ldr), (wp, ldw) = opt(P), opt(R), opt(W)
+        self._chk(self.lib.gpk_posterior_covariance(self.h, C.byref(prob.struct), pp, ldp, rp, ldr, int(field), K.ptr, K.ld, nt,
+                                                    wp, ldw, Cm.ptr, Cm.ld, int(bool(with_gn))))
+        return Cm
+
+    def posterior_sample(self, Cm, mean, xi, jitter, nt=None, out=None, return_factor=False):
+        """Samples of N(mean, Cm + jitter I): (samples, info), samples an (nt, ns) numpy array -- mean[t] + (L xi)[t, s] with L the lower
+        Cholesky factor, computed on the device (gpk_posterior_sample) -- or None when info != 0 (potrf's info: the first non-positive
+        pivot).  Cm (DeviceArray, nt x nt) is overwritten with the factor; xi: (nt, ns) standard normals, the caller's.  out: a
+        DeviceArray to write into (left untouched when info != 0).  return_factor=True: (samples, info, L) with L the factor as a numpy
+        array."""
+        nt = Cm.rows if nt is None else int(nt)
+        xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(nt, -1)
+        ns = xi.shape[1]
+        dxi = DeviceArray(self, nt, ns, ld=pad_ld(ns)).upload(xi)
+        dmean = mean if isinstance(mean, DeviceArray) else self.array(np.asarray(mean, dtype=np.float64).ravel())
+        dout = out if out is not None else DeviceArray(self, nt, ns, ld=pad_ld(ns))
+        info = C.c_int()
+        self._chk(self.lib.gpk_posterior_sample(self.h, Cm.ptr, Cm.ld, nt, float(jitter), dmean.ptr, dxi.ptr, dxi.ld, ns, dout.ptr, dout.ld,
+                                                C.byref(info)))
+        self.synchronize()
+        code = self._chk_info(info.value)
+        samples = dout.download(nt, ns).reshape(nt, ns) if code == 0 else None
+        dxi.free()
+        if dmean is not mean:
+            dmean.free()
+        if dout is not out:
+            dout.free()
+        if return_factor:
+            return samples, code, Cm.download(nt, nt)
+        return samples, code
+
+    def posterior_covariance_points(self, prob, P, R, field, layout, kernel, kernel_parameter, X_test, Xd, Xb, keep=False):
+        """(cov_cond, cov) as (N_t, N_t) numpy arrays at all of X_test in ONE batch (the covariance couples every pair of test points):
+        prior, cross-covariances and gpk_posterior_covariance twice, without and with the Gauss-Newton term.  ValueError when the
+        (N + n_z + N_t) N_t doubles of K, W and the covariance do not fit the device.  keep=True: (cov_cond, cov, dC) with dC the
+        DeviceArray of cov (for posterior_sample; the caller frees it)."""
+        X_test = np.ascontiguousarray(X_test, dtype=np.float64).reshape(-1, 2)
+        Xb = np.ascontiguousarray(Xb, dtype=np.float64).reshape(-1, 2)
+        Nt, Nd, Nb = X_test.shape[0], np.asarray(Xd).shape[0], Xb.shape[0]
+        lay = LAYOUT[layout]
+        N = {0: 2 * Nd + Nb, 1: 4 * Nd + Nb, 2: 4 * Nd + Nb, 3: 3 * Nd}[lay]
+        need, have = 8 * (N + prob.nz + Nt) * Nt, self.device_info()['hbm_bytes']
+        if need > have:
+            raise ValueError(f'posterior_covariance: one batch of {Nt} test points needs (N + n_z + N_t) N_t doubles = {need} bytes '
+                             f'(N = {N}, n_z = {prob.nz}) and the device has {have} bytes; the covariance is not computed in '
+                             'pieces -- use fewer test points')
+        dXt, dXd, dXb = self.points(X_test), self.points(Xd), self.points(Xb)
+        ldk = self.posterior_worksize(prob, Nt)['ldk']
+        K, W = DeviceArray(self, N, Nt, ld=ldk), DeviceArray(self, prob.nz, Nt, ld=ldk)
+        Cc, Cg = DeviceArray(self, Nt, Nt, ld=ldk), DeviceArray(self, Nt, Nt, ld=ldk)
+        kp = kernel_params(kernel, kernel_parameter)
+        for Cm, gn in ((Cc, 0), (Cg, 1)):
+            self._chk(self.lib.gpk_assemble_prior(self.h, KERNEL[kernel], kp, dXt.ptr, Nt, dXt.ptr, Nt, Cm.ptr, Cm.ld))
+            self._chk(self.lib.gpk_assemble_cross(self.h, lay, KERNEL[kernel], kp, dXt.ptr, Nt, dXd.ptr, Nd, dXb.ptr, Nb, K.ptr, K.ld))
+            self._chk(self.lib.gpk_posterior_covariance(self.h, C.byref(prob.struct), P.ptr, P.ld, R.ptr, R.ld, int(field), K.ptr, K.ld, Nt,
+                                                        W.ptr, W.ld, Cm.ptr, Cm.ld, gn))
+        self.synchronize()
+        out = Cc.download(Nt, Nt), Cg.download(Nt, Nt)
+        for a in (K, W, Cc, dXt, dXd, dXb):
+            a.free()
+        if keep:
+            return out + (Cg,)
+        Cg.free()
+        return out
+
     # ---- log evidence (gpk_chol_logdet, gpk_log_evidence) ----
     def chol_logdet(self, L, n=None):
         """(log |L L^T|, bad) of the lower factor in the DeviceArray L: 2 sum_i log L_ii over its diagonal and the number of diagonal

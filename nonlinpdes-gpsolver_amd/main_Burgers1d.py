@@ -5,7 +5,7 @@ import argparse
 
 import numpy as onp
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, report_test_variance, seed_from, solve_forward, tensor_grid
+from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, report_test_variance, report_posterior_samples, seed_from, solve_forward, tensor_grid
 
 SPACE_TIME = [[0, 1], [-1, 1]]
 
@@ -44,6 +44,7 @@ def main(argv=None):
     report_test_error(solver, show, XX, YY, X_test, cole_hopf_truth(cfg.nu)(X_test[:, 0], X_test[:, 1]))
     report_test_residual(cfg, solver, X_test)
     report_test_variance(cfg, solver, X_test)
+    report_posterior_samples(cfg, solver, X_test)
 
 
 if __name__ == '__main__':

@@ -6,7 +6,7 @@ import argparse
 import numpy as onp
 from scipy.interpolate import griddata
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, report_test_residual, report_test_variance, seed_from, solve_or_select, tensor_grid
+from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, report_test_residual, report_test_variance, report_posterior_samples, seed_from, solve_or_select, tensor_grid
 from reference_solver.FD_for_Darcy_flow import FD_Darcy_flow_2d
 from src.solver import solver_GP
 
@@ -67,6 +67,7 @@ def main(argv=None):
     print(f'[Test error] a: L2 error {rms(a_gp - a_true)}, max error {onp.max(abs(a_gp - a_true))}')
     report_test_residual(cfg, solver, X_grid)
     report_test_variance(cfg, solver, X_grid)
+    report_posterior_samples(cfg, solver, X_grid)
 
     if show:
         import matplotlib.pyplot as plt

@@ -3,7 +3,7 @@
 Same command line as the reference's main_Eikonal2d.py."""
 import argparse
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, report_test_variance, solve_forward, tensor_grid
+from _driver_common import add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, report_test_variance, report_posterior_samples, solve_forward, tensor_grid
 from reference_solver.Cole_Hopf_for_Eikonal import solve_Eikonal
 
 UNIT_SQUARE = [[0, 1], [0, 1]]
@@ -27,6 +27,7 @@ def main(argv=None):
     report_test_error(solver, show, XX, YY, X_test, truth.flatten())
     report_test_residual(cfg, solver, X_test)
     report_test_variance(cfg, solver, X_test)
+    report_posterior_samples(cfg, solver, X_test)
 
 
 if __name__ == '__main__':

@@ -18,7 +18,7 @@ import argparse
 import numpy as onp
 
 from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, add_nonlinearity, nonlinearity_from, report_test_error,
-                            report_test_residual, report_test_variance, solve_forward, tensor_grid)
+                            report_test_residual, report_test_variance, report_posterior_samples, solve_forward, tensor_grid)
 
 UNIT_SQUARE = [[0, 1], [0, 1]]
 
@@ -126,6 +126,7 @@ def main(argv=None):
     report_test_error(solver, show, XX, YY, X_test, u(X_test[:, 0], X_test[:, 1]))
     report_test_residual(cfg, solver, X_test)
     report_test_variance(cfg, solver, X_test)
+    report_posterior_samples(cfg, solver, X_test)
 
 
 if __name__ == '__main__':

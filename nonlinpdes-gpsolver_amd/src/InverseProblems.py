@@ -180,3 +180,22 @@ class Darcy_flow2d(_GPEquation):
             setattr(self, 'extended_var' + tag, v)
             setattr(self, 'extended_std' + tag, onp.sqrt(onp.maximum(v, 0.0)))
         return self.extended_var_u, self.extended_var_a
+
+    def posterior_covariance(self, X_test):
+        """Joint posterior covariance of u and of the log-permeability a at the points X_test, each field with its own matrix (see
+        _GPEquation.posterior_covariance; the covariance between u and a is not formed).  Sets extended_cov_u, extended_cov_a and their
+        _cond companions (N_test x N_test, raw values); returns (extended_cov_u, extended_cov_a)."""
+        res = self._posterior_cov_compute(X_test)
+        for tag in ('_u', '_a'):
+            cc, c = res[tag]
+            setattr(self, 'extended_cov_cond' + tag, cc)
+            setattr(self, 'extended_cov' + tag, c)
+        return self.extended_cov_u, self.extended_cov_a
+
+    def posterior_sample(self, X_test, n_samples=1, seed=None, xi=None, jitter=None):
+        """n_samples draws of u and of a at X_test (see _GPEquation.posterior_sample), each field from its own N(mean, Sigma + jitter I).
+        xi: a pair (xi_u, xi_a) of (N_test, n_samples) arrays; None: one numpy.random.RandomState(seed) draws u first, then a.  Sets
+        extended_samples_u, extended_samples_a (n_samples x N_test) and returns them as a pair."""
+        res = self._posterior_sample_compute(X_test, n_samples, seed, xi, jitter)
+        self.extended_samples_u, self.extended_samples_a = res['_u'], res['_a']
+        return self.extended_samples_u, self.extended_samples_a

@@ -20,6 +20,11 @@ from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_gri
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
 
+# Default jitter of posterior_sample, absolute, in units of the prior variance k(x,x) = 1: the next power of ten above
+# 32 * N_t * (largest entrywise error of the device's Sigma against long double) at N_t = 1024 -- measured, DESIGN.md section K
+# ("Posterior covariance and samples").
+POSTERIOR_JITTER = 1e-5
+
 
 def divergence_form(a, a_x1, a_x2, v1, v2, c):
     """The six coefficients (c0, b1, b2, a11, a12, a22) of psi = a Laplace + (grad a - v) . grad - c, for which
@@ -380,6 +385,87 @@ class _GPEquation(object):
         self.extended_var = v
         self.extended_std = onp.sqrt(onp.maximum(v, 0.0))
         return self.extended_var
+
+    # ---- joint posterior covariance and samples at test points (gpk_assemble_prior, gpk_posterior_covariance, gpk_posterior_sample) ----
+    def _posterior_cov_compute(self, X_test, keep=False):
+        """{suffix: (cov_cond, cov[, device array of cov])} for every field of the equation, all of X_test in one batch"""
+        P, R, _, prob = self._posterior_state()
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        out = {}
+        for tag, field, layout in self._posterior_fields:
+            out[tag] = get_context().posterior_covariance_points(prob, P, R, field, layout or self._layout, self.kernel,
+                                                                 self.kernel_parameter, X_test, self.X_domain, self.X_boundary, keep=keep)
+        return out
+
+    def posterior_covariance(self, X_test):
+        """Joint posterior covariance of the GP solution u at the points X_test, Gauss-Newton (Laplace) form at the final iterate of
+        GN_method: Sigma = Sigma_cond + Sigma_gn, the matrix whose diagonal posterior_variance returns ("Posterior
+        covariance and samples").  Sets extended_cov and extended_cov_cond (N_test x N_test, raw values, bitwise symmetric); returns
+        extended_cov.  All of X_test is one batch: (N + n_z + N_test) N_test doubles on the device, ValueError if they do not fit.
+        Served and refused exactly as posterior_variance.  No attribute of extend_sol, posterior_variance or GN_method is touched."""
+        cc, c = self._posterior_cov_compute(X_test)['']
+        self.extended_cov_cond = cc
+        self.extended_cov = c
+        return self.extended_cov
+
+    def _posterior_means(self, X_test):
+        """{suffix: posterior mean at X_test} through the class's own extend_sol, whose attributes are then put back as they were"""
+        names = ('X_test', 'N_test') + tuple('extended_sol' + tag for tag, _, _ in self._posterior_fields)
+        before = {n: self.__dict__[n] for n in names if n in self.__dict__}
+        try:
+            self.extend_sol(X_test)
+            return {tag: onp.array(getattr(self, 'extended_sol' + tag), dtype=onp.float64).ravel() for tag, _, _ in self._posterior_fields}
+        finally:
+            for n in names:
+                self.__dict__.pop(n, None)
+            self.__dict__.update(before)
+
+    def _posterior_xi(self, xi, n_fields, N_test, n_samples, seed):
+        """the standard normals of posterior_sample, one (N_test, n_samples) array per field, in the order of _posterior_fields"""
+        if xi is None:
+            rng = onp.random.RandomState(seed)
+            return [rng.standard_normal((N_test, n_samples)) for _ in range(n_fields)]
+        xs = [onp.asarray(xi, dtype=onp.float64)] if n_fields == 1 else [onp.asarray(x, dtype=onp.float64) for x in xi]
+        if len(xs) != n_fields or any(x.shape != (N_test, n_samples) for x in xs):
+            raise ValueError(f'posterior_sample: xi must be {"one array" if n_fields == 1 else f"{n_fields} arrays (u, a)"} of shape '
+                             f'({N_test}, {n_samples}) = (N_test, n_samples); got {[x.shape for x in xs]}')
+        return xs
+
+    def _posterior_sample_compute(self, X_test, n_samples, seed, xi, jitter):
+        """{suffix: (n_samples, N_test) samples}"""
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        n_samples, N_test = int(n_samples), X_test.shape[0]
+        if n_samples < 1:
+            raise ValueError('posterior_sample: n_samples must be at least 1')
+        jitter = POSTERIOR_JITTER if jitter is None else float(jitter)
+        self._posterior_state()                                # (refusals first: before anything is computed or drawn)
+        xs = self._posterior_xi(xi, len(self._posterior_fields), N_test, n_samples, seed)
+        means = self._posterior_means(X_test)
+        covs = self._posterior_cov_compute(X_test, keep=True)
+        out, failed = {}, None
+        for (tag, _, _), x in zip(self._posterior_fields, xs):
+            dC = covs[tag][2]
+            if failed is None:
+                samples, info = get_context().posterior_sample(dC, means[tag], x, jitter, nt=N_test)
+                if info != 0:
+                    failed = (tag, info)
+                else:
+                    out[tag] = onp.ascontiguousarray(samples.T)
+            dC.free()
+        if failed is not None:
+            raise RuntimeError(f'posterior_sample: the Cholesky factorisation of the posterior covariance{" of " + failed[0][1:] if failed[0] else ""} '
+                               f'met a non-positive pivot at index {failed[1]} with jitter = {jitter:g}; pass a larger jitter')
+        return out
+
+    def posterior_sample(self, X_test, n_samples=1, seed=None, xi=None, jitter=None):
+        """n_samples draws of the GP solution at X_test from N(mean, Sigma + jitter I): mean the extension of extend_sol (whose
+        attributes are left as they are), Sigma of posterior_covariance, sample = mean + L xi with L L^T = Sigma + jitter I on the device.
+        xi: the (N_test, n_samples) standard normals to use; None: numpy.random.RandomState(seed).standard_normal((N_test, n_samples)) --
+        nothing is drawn on the device, so the same seed (or xi) gives the same bits.  jitter: absolute, in units of the prior variance
+        k(x,x) = 1; None: POSTERIOR_JITTER.  Sets and returns extended_samples (n_samples x N_test).
+        RuntimeError when the factorisation meets a non-positive pivot; served and refused exactly as posterior_variance."""
+        self.extended_samples = self._posterior_sample_compute(X_test, n_samples, seed, xi, jitter)['']
+        return self.extended_samples
 
     # ---- log evidence of the kernel at the final iterate (gpk_log_evidence) ----------------------------------------------------------
     def log_evidence(self):

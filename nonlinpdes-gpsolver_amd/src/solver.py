@@ -144,6 +144,8 @@ _LOG = {
     'var_n': '[Testing posterior variance...] Number of test points: {n}',
     'var_mean': '[Test variance] Mean posterior std{tag} {v}',
     'var_max': '[Test variance] Max posterior std{tag} {v}',
+    'smp_n': '[Testing posterior samples...] Number of test points: {n}',
+    'smp': '[Test samples] {k} samples, RMS spread {rms}, max spread {mx}{tag}',
     'evidence': '[Log evidence] log Z {v}, J {J}, log|Theta| {lt}, log|H/2| {lh}',
     'sel_row': '[Kernel selection] kernel_parameter {p}{how}: log Z {v}, J {J}, info (Cholesky, Gauss-Newton, H/2) {info}',
     'sel_best': '[Kernel selection] chosen kernel_parameter {p}, log Z {v}{note}',
@@ -355,6 +357,23 @@ class solver_GP(object):
             label = ' of ' + tag[1:] if tag else ''
             _say(print_option, 'var_mean', tag=label, v=self.test_std_mean[tag])
             _say(print_option, 'var_max', tag=label, v=self.test_std_max[tag])
+
+    def test_samples(self, X_test, n_samples=1, seed=None, print_option=True):
+        """Draws of plausible solutions between the collocation points: n_samples samples of the joint posterior at X_test
+        (eqn.posterior_sample, standard normals from numpy.random.RandomState(seed)), reduced to the RMS and the maximum of their
+        spread |sample - mean| over the test points.  Darcy flow: both fields u and a.  extend_sol's attributes stay as they are."""
+        _say(print_option, 'smp_n', n=X_test.shape[0])
+        self.eqn.posterior_sample(X_test, n_samples=n_samples, seed=seed)
+        means = self.eqn._posterior_means(X_test)
+        self.test_spread_rms, self.test_spread_max = {}, {}
+        for tag in ('', '_u', '_a'):
+            smp = getattr(self.eqn, 'extended_samples' + tag, None)
+            if smp is None or tag not in means:
+                continue
+            spread = onp.abs(smp - means[tag][None, :])
+            self.test_spread_rms[tag], self.test_spread_max[tag] = float(onp.sqrt(onp.mean(spread ** 2))), float(onp.max(spread))
+            _say(print_option, 'smp', k=smp.shape[0], tag=f' (field {tag[1:]})' if tag else '', rms=self.test_spread_rms[tag],
+                 mx=self.test_spread_max[tag])
 
     # ---- figures (cosmetic; need matplotlib only): src/_figures.py ---------------------------------------------------------
     def _planar_only(self):
