@@ -1,5 +1,7 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
-same elliptic equation on a box in three space dimensions (no counterpart in the reference).
+same elliptic equation on a box in three space dimensions (no counterpart in the reference).  Four classes on _GPEquation; the two
+elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
+_family() what sets it apart.
 
 Same constructor arguments, methods and attributes; no JAX.  The Gram matrix, its Cholesky factor and the Gauss-Newton
 iterate live in GPU memory (libgpk.so); `Theta`, `L`, ... are materialised as numpy arrays only when read.
@@ -54,11 +56,16 @@ def parabolic_form(nu, v1=0.0, v2=0.0, c=0.0):
 
 
 class _GPEquation(object):
-    """Machinery shared by the three PDE classes (and by InverseProblems.Darcy_flow2d)."""
+    """Machinery shared by every equation class: Burgers, Eikonal, the two elliptic classes (through _EllipticEquation) and
+    InverseProblems.Darcy_flow2d -- points and user callbacks, the Gram matrix and its factor on the device, loss / gradient / Hessian,
+    the Gauss-Newton iteration, extension to test points, posterior and log evidence."""
     _layout = None              # Gram layout name
     _system = None              # Gauss-Newton system name
     _time_dependent = False
     _blocks_per_point = 1       # unknown groups per collocation point
+    _dim = 2                    # columns of a point
+    _structured_optin = True    # _problem() honours GPK_STRUCTURED
+    _bad_nugget_type = 'the reference leaves self.Theta unset here'
 
     # ---- user data -------------------------------------------------------------------------------------------------
     def get_bd(self, x1, x2):
@@ -67,13 +74,21 @@ class _GPEquation(object):
     def get_rhs(self, x1, x2):
         return self.rhs(x1, x2)
 
+    @staticmethod
+    def _pts(X):
+        """points as the class takes them: an array, its shape unchecked as in the reference"""
+        return onp.asarray(X, dtype=onp.float64)
+
+    def _columns(self, X):
+        return [X[:, k] for k in range(self._dim)]
+
     def _set_points(self, X_domain, X_boundary):
-        self.X_domain = onp.asarray(X_domain, dtype=onp.float64)
+        self.X_domain = self._pts(X_domain)
         self.N_domain = self.X_domain.shape[0]
-        self.X_boundary = onp.asarray(X_boundary, dtype=onp.float64)
+        self.X_boundary = self._pts(X_boundary)
         self.N_boundary = self.X_boundary.shape[0]
-        self.rhs_f = eval_callback(self.get_rhs, self.X_domain[:, 0], self.X_domain[:, 1])
-        self.bdy_g = eval_callback(self.get_bd, self.X_boundary[:, 0], self.X_boundary[:, 1])
+        self.rhs_f = eval_callback(self.get_rhs, *self._columns(self.X_domain))
+        self.bdy_g = eval_callback(self.get_bd, *self._columns(self.X_boundary))
         self._drop_device_state()
 
     def sampled_pts(self, N_domain, N_boundary, sampled_type='random'):
@@ -133,8 +148,9 @@ class _GPEquation(object):
             # GPK_STRUCTURED=1 / 2 (opt-in, elliptic system only; 2 adds the Gram level, gpk_gn_gram_prepare): the z-independent solves are done once and every step forms
             # [L^{-1}A(z) | L^{-1}F(z)] from them (gpk_gn_structured_prepare) -- same iterates, about half the time per step
             # (round 6: GPK_STRUCTURED=1 also for the Burgers and Eikonal systems, and the Darcy system in InverseProblems.py: A(z) = A1 diag(d(z)) + A2)
-            structured = int(os.environ.get('GPK_STRUCTURED', '0') or 0)
-            # (2 = the Gram level: since round 6 for every system with a structured form)
+            # (2 = the Gram level: since round 6 for every system with a structured form).  A class with _structured_optin = False
+            # ignores the variable: every step runs the reference's operation sequence.
+            structured = int(os.environ.get('GPK_STRUCTURED', '0') or 0) if self._structured_optin else False
             self._prob = gpk.GNProblem(get_context(), self._system, self.N_domain, self.N_boundary, self.rhs_f, self.bdy_g,
                                        self._dL, **dict(dict(p0=p0, p1=p1), **self._nl_args()), pen_lambda=lam, structured=structured)
         return self._prob
@@ -142,7 +158,7 @@ class _GPEquation(object):
     # ---- Gram matrix + Cholesky ------------------------------------------------------------------------------------
     def _assemble(self, kernel, kernel_parameter, nugget, nugget_type):
         if nugget_type not in ('adaptive', 'identity', 'none'):
-            raise AttributeError(f"nugget_type {nugget_type!r}: the reference leaves self.Theta unset here")
+            raise AttributeError(f"nugget_type {nugget_type!r}: {self._bad_nugget_type}")
         ctx = get_context()
         self._drop_device_state()
         self.nugget_type = nugget_type
@@ -338,26 +354,36 @@ class _GPEquation(object):
         """why posterior_variance is not available for this object, or None"""
         return None
 
+    def _final_iterate(self, caller, what, entry):
+        """(prob, z*) of the last GN_method for `caller` (the prefix of its messages); the relaxed system, which the device entry point
+        `entry` does not serve, is refused as having no `what` entry point"""
+        star = self.__dict__.get('_z_star')
+        if star is None:
+            raise RuntimeError(f'{caller}: call GN_method() first')
+        prob, z = star
+        if prob.struct.system == gpk.SYSTEM['Nonlinear_elliptic_relaxed']:
+            raise NotImplementedError(f'{caller}: the relaxed formulation (GN_relaxed_method) has no {what} entry point '
+                                      f'({entry} returns -9001 for GPK_GN_ELLIPTIC_RELAXED); solve with GN_method')
+        return prob, z
+
+    @staticmethod
+    def _warn_pivot(info, undefined):
+        if info != 0:
+            print('[Warning] Cholesky factorization of the Gauss-Newton matrix at the final iterate met a non-positive pivot at index',
+                  info, f': the {undefined} not defined there')
+
     def _posterior_state(self):
         """(P, R, info, prob): prepared once per final iterate, dropped with the device state and at the next GN_method"""
         reason = self._posterior_unserved()
         if reason is not None:
             raise NotImplementedError('posterior_variance: ' + reason)
-        star = self.__dict__.get('_z_star')
-        if star is None:
-            raise RuntimeError('posterior_variance: call GN_method() first')
-        prob, z = star
-        if prob.struct.system == gpk.SYSTEM['Nonlinear_elliptic_relaxed']:
-            raise NotImplementedError('posterior_variance: the relaxed formulation (GN_relaxed_method) has no variance entry point '
-                                      '(gpk_posterior_prepare returns -9001 for GPK_GN_ELLIPTIC_RELAXED); solve with GN_method')
+        prob, z = self._final_iterate('posterior_variance', 'variance', 'gpk_posterior_prepare')
         if self.__dict__.get('_posterior') is None:
             ctx = get_context()
             dz = ctx.array(z)
             P, R, info = ctx.posterior_prepare(prob, dz)
             dz.free()
-            if info != 0:
-                print('[Warning] Cholesky factorization of the Gauss-Newton matrix at the final iterate met a non-positive pivot at index',
-                      info, ': the posterior variance is not defined there')
+            self._warn_pivot(info, 'posterior variance is')
             self._posterior = (P, R, info, prob)
         return self._posterior
 
@@ -477,50 +503,39 @@ class _GPEquation(object):
         gpk_posterior_prepare serves, bc= / operator= and Nonlinear_elliptic3d included (their system is the elliptic one on their own
         Theta); NotImplementedError after GN_relaxed_method.  P = L^{-1} A(z*) and the factor of H/2 are kept where posterior_variance
         looks for them, so a following posterior_variance does not prepare again."""
-        star = self.__dict__.get('_z_star')
-        if star is None:
-            raise RuntimeError('log_evidence: call GN_method() first')
-        prob, z = star
-        if prob.struct.system == gpk.SYSTEM['Nonlinear_elliptic_relaxed']:
-            raise NotImplementedError('log_evidence: the relaxed formulation (GN_relaxed_method) has no evidence entry point '
-                                      '(gpk_log_evidence returns -9001 for GPK_GN_ELLIPTIC_RELAXED); solve with GN_method')
+        prob, z = self._final_iterate('log_evidence', 'evidence', 'gpk_log_evidence')
         ctx = get_context()
         dz = ctx.array(z)
         terms, P, R, info = ctx.log_evidence(prob, dz)
         dz.free()
-        if info != 0:                                          # (what _posterior_state says when it prepares: the slot is filled here)
-            print('[Warning] Cholesky factorization of the Gauss-Newton matrix at the final iterate met a non-positive pivot at index',
-                  info, ': the log evidence and the posterior variance are not defined there')
+        self._warn_pivot(info, 'log evidence and the posterior variance are')   # (the posterior slot is filled here: said for both)
         self._drop_posterior()
         self._posterior = (P, R, info, prob)
         self.log_evidence_terms = dict(terms, info=info)
         return terms['log_Z']
 
 
-class Nonlinear_elliptic2d(_GPEquation):
-    """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208); with operator=... / set_domain_operator() the semilinear
-    equation -psi[u] + alpha*u^m = f for any second-order linear operator psi with variable coefficients (no counterpart in the reference)."""
-    _layout = 'Nonlinear_elliptic'
+class _EllipticEquation(_GPEquation):
+    """-psi[u] + tau(u) = f on a box, B u = g on its faces: everything Nonlinear_elliptic2d and Nonlinear_elliptic3d share.  psi is the
+    Laplacian, or any second-order linear operator with variable coefficients (operator= / set_domain_operator: a row of len(_op_names)
+    coefficients per domain point, kept in domain_coeffs); B is the identity, or a first-order functional (bc= / set_boundary_operator: a
+    row of _dim + 1 coefficients per boundary point, kept in boundary_coeffs); tau is alpha u^m, or the `nonlinearity` given.
+    A subclass gives the attributes below, its __init__ and Gram_matrix (their defaults and docstrings), _posterior_unserved, and ONE
+    routing point: _family() names the evaluator family that serves the object as it stands -- 'plain', 'bc' or 'op' -- and
+    _evaluate_gram and _fields turn that name into the device calls.  No other method chooses an evaluator; where one below reads
+    domain_coeffs, it asks whether psi is the Laplacian (which rows to return, which coefficients to expect), not whom to call."""
     _system = 'Nonlinear_elliptic'
-
     _BC = ('dirichlet', 'neumann', 'robin')
+    _op_names = None            # rows of the operator evaluator: value, the _dim first derivatives, the second derivatives
+    _laplacian_row = None       # the Laplacian as a coefficient row over _op_names
+    _normals = None             # outward unit normals: f(X_boundary, domain)
+    _xs = _count = _coeff_names = None      # fragments of the messages: callback arguments, len(_op_names) in words, the coefficients
 
-    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
-                 operator=None, nonlinearity=None):
-        """nonlinearity (no counterpart in the reference): the reaction term tau of -psi[u] + tau(u) = f as (name, parameters...) --
-        ('exp', p0, p1) p0 exp(p1 u); ('sinh', p0, p1); ('sin', p0, p1); ('cubic', c1, c2, c3) c1 u + c2 u^2 + c3 u^3; ('power', alpha, m)
-        -- or None: alpha u^m with the arguments alpha, m, and every call goes the way it always went (src/nonlinearity.py).
-        bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
-        g = B u is what `bdy(x1, x2)` returns -- 'dirichlet' B u = u; 'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the
-        outward unit normal (sample_points.boundary_normals).  set_boundary_operator() takes an arbitrary first-order operator per
-        boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went.
-        operator (no counterpart in the reference either): a callable operator(x1, x2) returning the six coefficient arrays
-        (c0, b1, b2, a11, a12, a22) of psi = c0 + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2; the equation solved is then
-        -psi[u] + alpha u^m = f (divergence_form() gives the coefficients of -div(a grad u) + v . grad u + c u; a12 multiplies the mixed
-        derivative once).  Evaluated at the domain points when they are set and at the test points by PDE_residual.  None: the
-        Laplacian, and every call goes the way it always went."""
+    def __init__(self, alpha, m, bdy, rhs, domain, bc, robin_beta, operator, nonlinearity):
         if bc not in self._BC:
             raise ValueError(f'bc {bc!r}: one of {self._BC}')
+        if operator is not None and not callable(operator):
+            raise ValueError(f'operator {operator!r}: a callable operator{self._xs} returning {self._count} coefficient arrays, or None')
         self.alpha = alpha
         self.m = m
         self.bdy = bdy
@@ -528,10 +543,8 @@ class Nonlinear_elliptic2d(_GPEquation):
         self.domain = domain
         self.bc = bc
         self.robin_beta = robin_beta
-        self.boundary_coeffs = None
-        if operator is not None and not callable(operator):
-            raise ValueError(f'operator {operator!r}: a callable operator(x1, x2) returning six coefficient arrays, or None')
         self.operator = operator
+        self.boundary_coeffs = None
         self.domain_coeffs = None
         self.nonlinearity = None if nonlinearity is None else Nonlinearity.make(nonlinearity)
 
@@ -542,152 +555,54 @@ class Nonlinear_elliptic2d(_GPEquation):
         """the reaction term: the one given, or the power law of the current alpha, m"""
         return self.nonlinearity if self.nonlinearity is not None else Nonlinearity.power(self.alpha, self.m)
 
-    def _posterior_unserved(self):
-        if self.bc != 'dirichlet' or self.boundary_coeffs is not None:
-            return ('boundary functionals (bc / set_boundary_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
-                    'gpk_assemble_bc yet')
-        if self.operator is not None or self.domain_coeffs is not None:
-            return ('domain operator (operator / set_domain_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
-                    'gpk_assemble_op yet')
-        return None
+    # ---- the routing point and the two methods that act on it: each subclass's own -------------------------------------------------
+    def _family(self):
+        raise NotImplementedError
 
-    # ---- boundary operator: (N_boundary, 3) coefficients (c0, c1, c2) of c0 u + c1 u_x1 + c2 u_x2, or None = Dirichlet, today's path ----
+    def _fields(self, X_test, which):
+        """rows `which` of the extension at X_test, from the evaluator of _family(): a (len(which), Nt) DeviceArray"""
+        raise NotImplementedError
+
+    # ---- boundary operator (N_boundary, _dim + 1), domain operator (N_domain, len(_op_names)); None = Dirichlet / the Laplacian ----
     def _set_points(self, X_domain, X_boundary):
         super()._set_points(X_domain, X_boundary)
-        self.boundary_coeffs = None                        # a custom operator belongs to the points it was set for
+        self.boundary_coeffs = None                        # custom operators belong to the points they were set for
         if self.bc != 'dirichlet':
-            n = boundary_normals(self.X_boundary, self.domain)
+            n = self._normals(self.X_boundary, self.domain)
             beta = float(self.robin_beta) if self.bc == 'robin' else 0.0
             self.boundary_coeffs = onp.concatenate([onp.full((self.N_boundary, 1), beta), n], axis=1)
-        self.domain_coeffs = None                          # likewise
+        self.domain_coeffs = None
         if self.operator is not None:
             self.domain_coeffs = self._operator_at(self.X_domain)
 
-    # ---- domain operator: (N_domain, 6) coefficients (c0, b1, b2, a11, a12, a22) of psi, or None = the Laplacian, today's path ----
     def _operator_at(self, X):
-        """the callable `operator` at the points X (n,2) as an (n,6) array"""
-        rows = self.operator(X[:, 0], X[:, 1])
-        if len(rows) != 6:
-            raise ValueError(f'operator must return six coefficient arrays (c0, b1, b2, a11, a12, a22), got {len(rows)}')
+        """the callable `operator` at the points X (n, _dim) as an (n, len(_op_names)) array"""
+        rows = self.operator(*self._columns(X))
+        if len(rows) != len(self._op_names):
+            raise ValueError(f'operator must return {self._count} coefficient arrays {self._coeff_names}, got {len(rows)}')
         return onp.stack([onp.broadcast_to(onp.asarray(r, dtype=onp.float64), (X.shape[0],)) for r in rows], axis=1)
 
     def set_domain_operator(self, coeffs):
-        """Row i of coeffs (N_domain, 6) = (c0, b1, b2, a11, a12, a22): the equation at domain point i reads -psi_i[u] + alpha u^m = rhs_f[i]
-        with psi_i = c0 + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2.  Call after the points are set; dropped when they
+        """Row i of coeffs (N_domain, len(_op_names)) holds the coefficients of psi_i over _op_names -- (c0, b1, b2, a11, a12, a22) in two
+        dimensions, (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) in three; a mixed coefficient multiplies its mixed derivative once --
+        and the equation at domain point i reads -psi_i[u] + alpha u^m = rhs_f[i].  Call after the points are set; dropped when they
         change.  Discards the Gram matrix and everything derived from it."""
         coeffs = onp.array(coeffs, dtype=onp.float64)
-        if coeffs.shape != (self.N_domain, 6):
-            raise ValueError(f'coeffs must have shape ({self.N_domain}, 6), got {coeffs.shape}')
+        if coeffs.shape != (self.N_domain, len(self._op_names)):
+            raise ValueError(f'coeffs must have shape ({self.N_domain}, {len(self._op_names)}), got {coeffs.shape}')
         self.domain_coeffs = coeffs
         self._drop_device_state()
 
     def set_boundary_operator(self, coeffs):
-        """Row b of coeffs (N_boundary, 3) = (c0, c1, c2): the condition at boundary point b reads c0 u + c1 u_x1 + c2 u_x2 = bdy_g[b].
+        """Row b of coeffs (N_boundary, _dim + 1) = (c0, c1, ..): the condition at boundary point b reads c0 u + c . grad u = bdy_g[b].
         Call after the points are set; dropped when they change.  Discards the Gram matrix and everything derived from it."""
         coeffs = onp.array(coeffs, dtype=onp.float64)
-        if coeffs.shape != (self.N_boundary, 3):
-            raise ValueError(f'coeffs must have shape ({self.N_boundary}, 3), got {coeffs.shape}')
+        if coeffs.shape != (self.N_boundary, self._dim + 1):
+            raise ValueError(f'coeffs must have shape ({self.N_boundary}, {self._dim + 1}), got {coeffs.shape}')
         self.boundary_coeffs = coeffs
         self._drop_device_state()
 
-    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
-        if self.domain_coeffs is not None:
-            T, ratio = ctx.assemble_op(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs, self.boundary_coeffs,
-                                       nugget, nugget_type)
-            return T, [ratio]
-        if self.boundary_coeffs is None:
-            return super()._evaluate_gram(ctx, kernel, kernel_parameter, nugget, nugget_type)
-        T, ratio = ctx.assemble_bc(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.boundary_coeffs, nugget, nugget_type)
-        return T, [ratio]
-
-    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
-        if self.domain_coeffs is not None or self.boundary_coeffs is not None:
-            require_gaussian_family(kernel, 'Nonlinear_elliptic2d with an operator or boundary conditions')
-        ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
-        if nugget_type == 'adaptive':
-            self.ratio = ratios[0]
-
-    def _fields_bc(self, X_test, which):
-        return get_context().extend_functionals_bc(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
-                                                   self.boundary_coeffs, self._coeff(self._dL, self.sol_vec), which=which)
-
-    _op_names = ('value', 'd1', 'd2', 'd11', 'd12', 'd22')      # rows of gpk_extend_functionals_op
-
-    def _fields_op(self, X_test, which):
-        return get_context().extend_functionals_op(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
-                                                   self.domain_coeffs, self.boundary_coeffs, self._coeff(self._dL, self.sol_vec),
-                                                   which=which)
-
-    def extend_sol(self, X_test):
-        if self.boundary_coeffs is None and self.domain_coeffs is None:
-            return super().extend_sol(X_test)
-        X_test = onp.asarray(X_test, dtype=onp.float64)
-        self.X_test = X_test
-        self.N_test = X_test.shape[0]
-        fields = self._fields_op if self.domain_coeffs is not None else self._fields_bc
-        self.extended_sol = fields(X_test, ('value',)).download().reshape(-1)
-
-    def _derivative_fields(self, X_test, coeffs_t=None):
-        """with a domain operator: rows value, d1, d2 and psi_t[u] (in the Laplacian's place), psi_t from coeffs_t (Nt,6) or the callable"""
-        if self.domain_coeffs is not None:
-            if coeffs_t is None:
-                if self.operator is None:
-                    raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
-                                     'points as coeffs_t (Nt,6)')
-                coeffs_t = self._operator_at(X_test)
-            coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
-            if coeffs_t.shape != (X_test.shape[0], 6):
-                raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, 6), got {coeffs_t.shape}')
-            rows = self._fields_op(X_test, self._op_names).download().reshape(6, -1)
-            psi = (coeffs_t.T * rows).sum(axis=0)                 # psi_t[u]: a combination of the six rows, per test point
-            return {'u': get_context().array(onp.stack([rows[0], rows[1], rows[2], psi]))}
-        if self.boundary_coeffs is None:
-            return super()._derivative_fields(X_test)
-        return {'u': self._fields_bc(X_test, self._deriv_names)}
-
-    def extend_derivatives(self, X_test):
-        """as the base class; with a domain operator additionally d11, d12, d22 (laplacian = d11 + d22)"""
-        if self.domain_coeffs is None:
-            return super().extend_derivatives(X_test)
-        X_test = onp.asarray(X_test, dtype=onp.float64)
-        r = self._rows(self._fields_op(X_test, self._op_names), self._op_names)
-        self.extended_derivatives = {'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'laplacian': r['d11'] + r['d22'],
-                                     'd11': r['d11'], 'd12': r['d12'], 'd22': r['d22']}
-        return self.extended_derivatives
-
-    def PDE_residual(self, X_test, coeffs_t=None):
-        """pointwise residual at X_test; with a domain operator -psi_t[u] + alpha u^m - f, psi_t from the callable `operator` or from
-        coeffs_t (Nt,6) (needed when the operator was set per point; ValueError otherwise)"""
-        if self.domain_coeffs is None:
-            if coeffs_t is not None:
-                raise ValueError('coeffs_t given, but no domain operator is set')
-            return super().PDE_residual(X_test)
-        X_test = onp.asarray(X_test, dtype=onp.float64)
-        fields = self._derivative_fields(X_test, coeffs_t)
-        rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
-        self.test_residual = self._residual(fields['u'], None, rhs)
-        return self.test_residual
-
-    def boundary_residual(self, X_bt, coeffs_t, g_t):
-        """c0 u + c1 u_x1 + c2 u_x2 - g of the GP solution at the points X_bt (n,2), with coeffs_t (n,3) = (c0, c1, c2) and g_t (n,) given
-        per point: how well the boundary condition holds between the boundary collocation points (numpy array, also `bdy_residual`)."""
-        X_bt = onp.asarray(X_bt, dtype=onp.float64).reshape(-1, 2)
-        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64).reshape(-1, 3)
-        g_t = onp.asarray(g_t, dtype=onp.float64).ravel()
-        if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
-            raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
-        names = ('value', 'd1', 'd2')
-        if self.domain_coeffs is not None:
-            d = self._fields_op(X_bt, names)
-        elif self.boundary_coeffs is None:
-            d = get_context().extend_functionals(self._layout, self.kernel, self.kernel_parameter, X_bt, self.X_domain, self.X_boundary,
-                                                 self._coeff(self._dL, self.sol_vec), which=names)
-        else:
-            d = self._fields_bc(X_bt, names)
-        r = self._rows(d, names)
-        self.bdy_residual = coeffs_t[:, 0] * r['value'] + coeffs_t[:, 1] * r['d1'] + coeffs_t[:, 2] * r['d2'] - g_t
-        return self.bdy_residual
-
+    # ---- Gauss-Newton (elimination formulation) --------------------------------------------------------------------------------------
     def GN_loss(self, z, z_old):
         z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
         zz = onp.concatenate([self._tau().dtau(z_old) * (z - z_old), z, self.bdy_g])
@@ -703,6 +618,167 @@ class Nonlinear_elliptic2d(_GPEquation):
         sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
         self.sol_vec = onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g])
         self.sol_sampled_pts = sol
+
+    # ---- the solution away from the collocation points -------------------------------------------------------------------------------
+    def extend_sol(self, X_test):
+        X_test = self._pts(X_test)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = self._fields(X_test, ('value',)).download().reshape(-1)
+
+    def _laplacian(self, r):
+        lap = r['d11'] + r['d22']
+        return lap if self._dim == 2 else lap + r['d33']
+
+    def extend_derivatives(self, X_test):
+        """the rows _deriv_names of the GP solution at X_test (numpy arrays): value, first derivatives, laplacian; with a domain operator
+        additionally every second derivative of _op_names (laplacian = their trace)"""
+        X_test = self._pts(X_test)
+        first, second = self._op_names[:self._dim + 1], self._op_names[self._dim + 1:]
+        if self.domain_coeffs is not None:
+            r = self._rows(self._fields(X_test, self._op_names), self._op_names)
+            self.extended_derivatives = dict({n: r[n] for n in first}, laplacian=self._laplacian(r), **{n: r[n] for n in second})
+        elif self._family() == 'op':         # a boundary condition served by the operator family (3-D), which has no laplacian row
+            names = first + tuple(n for n in second if n[1] == n[2])      # d11, d22, d33: the pure second derivatives
+            r = self._rows(self._fields(X_test, names), names)
+            self.extended_derivatives = dict({n: r[n] for n in first}, laplacian=self._laplacian(r))
+        else:
+            self.extended_derivatives = self._rows(self._fields(X_test, self._deriv_names), self._deriv_names)
+        return self.extended_derivatives
+
+    _residual_rows = ('value', 'd1', 'd2', 'laplacian')         # the rows gpk_pde_residual takes; it reads value and laplacian
+
+    def _psi_fields(self, X_test, coeffs_t):
+        """_residual_rows with psi_t[u] in the Laplacian's place, from the operator family: psi_t from coeffs_t (Nt, len(_op_names)), from
+        the callable `operator`, or the Laplacian when only the boundary condition is general"""
+        n = len(self._op_names)
+        if coeffs_t is None:
+            if self.domain_coeffs is None:
+                coeffs_t = onp.tile(self._laplacian_row, (X_test.shape[0], 1))
+            elif self.operator is None:
+                raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
+                                 f'points as coeffs_t (Nt,{n})')
+            else:
+                coeffs_t = self._operator_at(X_test)
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
+        if coeffs_t.shape != (X_test.shape[0], n):
+            raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, {n}), got {coeffs_t.shape}')
+        rows = self._fields(X_test, self._op_names).download().reshape(n, -1)
+        psi = (coeffs_t.T * rows).sum(axis=0)                     # psi_t[u]: a combination of the rows, per test point
+        return get_context().array(onp.stack([rows[0], rows[1], rows[2], psi]))
+
+    def _derivative_fields(self, X_test, coeffs_t=None):
+        """{'u': the rows _residual_rows at X_test as a DeviceArray}"""
+        if self._family() == 'op':
+            return {'u': self._psi_fields(X_test, coeffs_t)}
+        return {'u': self._fields(X_test, self._residual_rows)}
+
+    def PDE_residual(self, X_test, coeffs_t=None):
+        """pointwise residual -Delta u + tau(u) - f at X_test from the derivatives of the GP solution (rhs evaluated at X_test); with a
+        domain operator -psi_t[u] + tau(u) - f, psi_t from the callable `operator` or from coeffs_t (Nt, len(_op_names)) (needed when the
+        operator was set per point; ValueError otherwise)"""
+        X_test = self._pts(X_test)
+        if self.domain_coeffs is None and coeffs_t is not None:
+            raise ValueError('coeffs_t given, but no domain operator is set')
+        fields = self._derivative_fields(X_test, coeffs_t)
+        rhs = eval_callback(self.get_rhs, *self._columns(X_test))
+        self.test_residual = self._residual(fields['u'], None, rhs)
+        return self.test_residual
+
+    def boundary_residual(self, X_bt, coeffs_t, g_t):
+        """c0 u + c . grad u - g of the GP solution at the points X_bt (n, _dim), with coeffs_t (n, _dim + 1) = (c0, c1, ..) and g_t (n,)
+        given per point: how well the boundary condition holds between the boundary collocation points (numpy array, also `bdy_residual`)."""
+        X_bt = self._pts(onp.asarray(X_bt, dtype=onp.float64).reshape(-1, self._dim))
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64).reshape(-1, self._dim + 1)
+        g_t = onp.asarray(g_t, dtype=onp.float64).ravel()
+        if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
+            raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
+        names = self._op_names[:self._dim + 1]                  # value, d1, .. d_dim
+        r = self._rows(self._fields(X_bt, names), names)
+        res = coeffs_t[:, 0] * r['value']
+        for k in range(1, self._dim + 1):
+            res = res + coeffs_t[:, k] * r[names[k]]
+        self.bdy_residual = res - g_t
+        return self.bdy_residual
+
+
+class Nonlinear_elliptic2d(_EllipticEquation):
+    """-Delta u + alpha*u^m = f on a rectangle (reference src/PDEs.py:18-208); with operator=... / set_domain_operator() the semilinear
+    equation -psi[u] + alpha*u^m = f for any second-order linear operator psi with variable coefficients (no counterpart in the reference).
+    Three evaluator families (_family); the plain one is the reference's layout, which alone takes the Matern kernels, stores `ratio`
+    only for the adaptive nugget, honours GPK_STRUCTURED and serves the posterior.  The relaxed formulation exists here only."""
+    _layout = 'Nonlinear_elliptic'
+    _op_names = ('value', 'd1', 'd2', 'd11', 'd12', 'd22')      # rows of gpk_extend_functionals_op
+    _laplacian_row = (0.0, 0.0, 0.0, 1.0, 0.0, 1.0)
+    _normals = staticmethod(boundary_normals)
+    _xs, _count, _coeff_names = '(x1, x2)', 'six', '(c0, b1, b2, a11, a12, a22)'
+
+    def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
+                 operator=None, nonlinearity=None):
+        """nonlinearity (no counterpart in the reference): the reaction term tau of -psi[u] + tau(u) = f as (name, parameters...) --
+        ('exp', p0, p1) p0 exp(p1 u); ('sinh', p0, p1); ('sin', p0, p1); ('cubic', c1, c2, c3) c1 u + c2 u^2 + c3 u^3; ('power', alpha, m)
+        -- or None: alpha u^m with the arguments alpha, m, and every call goes the way it always went (src/nonlinearity.py).
+        bc (no counterpart in the reference, which imposes Dirichlet data only): the operator B on the boundary, whose prescribed value
+        g = B u is what `bdy(x1, x2)` returns -- 'dirichlet' B u = u; 'neumann' B u = du/dn; 'robin' B u = robin_beta u + du/dn, n the
+        outward unit normal (sample_points.boundary_normals).  set_boundary_operator() takes an arbitrary first-order operator per
+        boundary point.  With 'dirichlet' and no custom operator every call goes the way it always went.
+        operator (no counterpart in the reference either): a callable operator(x1, x2) returning the six coefficient arrays
+        (c0, b1, b2, a11, a12, a22) of psi = c0 + b1 d_1 + b2 d_2 + a11 d_1 d_1 + a12 d_1 d_2 + a22 d_2 d_2; the equation solved is then
+        -psi[u] + alpha u^m = f (divergence_form() gives the coefficients of -div(a grad u) + v . grad u + c u; a12 multiplies the mixed
+        derivative once).  Evaluated at the domain points when they are set and at the test points by PDE_residual.  None: the
+        Laplacian, and every call goes the way it always went."""
+        super().__init__(alpha, m, bdy, rhs, domain, bc, robin_beta, operator, nonlinearity)
+
+    # ---- which evaluator serves this object: decided here and nowhere else -----------------------------------------------------------
+    def _family(self):
+        """'op': gpk_assemble_op / gpk_extend_functionals_op, with a domain operator (and whatever boundary condition);
+        'bc': gpk_assemble_bc / gpk_extend_functionals_bc, with a boundary functional alone;
+        'plain': the reference's layout through gpk_assemble / gpk_extend / gpk_extend_functionals"""
+        if self.domain_coeffs is not None:
+            return 'op'
+        return 'plain' if self.boundary_coeffs is None else 'bc'
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        family = self._family()
+        if family == 'plain':
+            return super()._evaluate_gram(ctx, kernel, kernel_parameter, nugget, nugget_type)
+        if family == 'op':
+            T, ratio = ctx.assemble_op(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs, self.boundary_coeffs,
+                                       nugget, nugget_type)
+        else:
+            T, ratio = ctx.assemble_bc(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.boundary_coeffs, nugget, nugget_type)
+        return T, [ratio]
+
+    def _fields(self, X_test, which):
+        ctx, family = get_context(), self._family()
+        args = (self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary)
+        coeff = self._coeff(self._dL, self.sol_vec)
+        if family == 'op':
+            return ctx.extend_functionals_op(*args, self.domain_coeffs, self.boundary_coeffs, coeff, which=which)
+        if family == 'bc':
+            return ctx.extend_functionals_bc(*args, self.boundary_coeffs, coeff, which=which)
+        return ctx.extend_functionals(self._layout, *args, coeff, which=which)
+
+    def extend_sol(self, X_test):
+        if self._family() == 'plain':
+            return _GPEquation.extend_sol(self, X_test)           # gpk_extend, as the reference's other layouts
+        return super().extend_sol(X_test)
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
+        if self._family() != 'plain':
+            require_gaussian_family(kernel, 'Nonlinear_elliptic2d with an operator or boundary conditions')
+        ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
+        if nugget_type == 'adaptive':
+            self.ratio = ratios[0]
+
+    def _posterior_unserved(self):
+        if self.bc != 'dirichlet' or self.boundary_coeffs is not None:      # (what was asked for, points set or not: not the routing)
+            return ('boundary functionals (bc / set_boundary_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
+                    'gpk_assemble_bc yet')
+        if self.operator is not None or self.domain_coeffs is not None:
+            return ('domain operator (operator / set_domain_operator): gpk_assemble_cross has no rectangular evaluator for the layout of '
+                    'gpk_assemble_op yet')
+        return None
 
     # ---- relaxed (penalised) formulation, reference src/PDEs.py:137-201 ----
     def _relaxed_problem(self, pen_lambda):
@@ -741,7 +817,7 @@ class Nonlinear_elliptic2d(_GPEquation):
         self.sol_sampled_pts = sol[self.N_domain:]
 
 
-class Nonlinear_elliptic3d(_GPEquation):
+class Nonlinear_elliptic3d(_EllipticEquation):
     """-Delta u + alpha*u^m = f on a box in R^3, u = g on its six faces.  Same methods and attributes as Nonlinear_elliptic2d (elimination
     formulation only; the relaxed formulation is not offered); points are (n,3), callbacks take (x1, x2, x3).  The Gram matrix has the
     2-D elliptic block structure -- Laplacian on the domain points, delta on domain + boundary points, N = 2 N_domain + N_boundary --
@@ -751,12 +827,18 @@ class Nonlinear_elliptic3d(_GPEquation):
     With operator=... / set_domain_operator() the equation is -psi[u] + alpha*u^m = f for any second-order linear operator psi with
     variable coefficients, and with bc='neumann' / 'robin' / set_boundary_operator() the boundary rows are first-order functionals
     (gpk_assemble_op3d, gpk_extend_functionals_op3d).  With axis 3 as time this covers u_t - nu Laplace_x u + alpha u^m = f in two space
-    dimensions (parabolic_form(), sampled_pts(time_dependent=True))."""
+    dimensions (parabolic_form(), sampled_pts(time_dependent=True)).
+    Against Nonlinear_elliptic2d: two evaluator families (_family), points checked to be (n,3), the Gaussian kernels only, `ratio`
+    stored for every nugget type, its own sampled_pts, no posterior variance, covariance or samples."""
     _layout = 'Nonlinear_elliptic3d'
-    _system = 'Nonlinear_elliptic'
+    _dim = 3
     _deriv_names = ('value', 'd1', 'd2', 'd3', 'laplacian')
-    _BC = ('dirichlet', 'neumann', 'robin')
     _op_names = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')    # rows of gpk_extend_functionals_op3d
+    _laplacian_row = (0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 1.0)
+    _normals = staticmethod(boundary_normals3d)
+    _xs, _count, _coeff_names = '(x1, x2, x3)', 'ten', '(c0, b1, b2, b3, a11, a12, a13, a22, a23, a33)'
+    _structured_optin = False
+    _bad_nugget_type = 'adaptive, identity or none'
 
     def __init__(self, alpha=1.0, m=3, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]]), bc='dirichlet', robin_beta=1.0,
                  operator=None, nonlinearity=None):
@@ -767,26 +849,7 @@ class Nonlinear_elliptic3d(_GPEquation):
         operator: a callable operator(x1, x2, x3) returning the ten coefficient arrays (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33) of
         psi; the equation solved is then -psi[u] + alpha u^m = f (divergence_form3d(), parabolic_form(); a mixed coefficient multiplies
         its mixed derivative once).  With 'dirichlet' and None every call goes the way it always went."""
-        if bc not in self._BC:
-            raise ValueError(f'bc {bc!r}: one of {self._BC}')
-        if operator is not None and not callable(operator):
-            raise ValueError(f'operator {operator!r}: a callable operator(x1, x2, x3) returning ten coefficient arrays, or None')
-        self.alpha = alpha
-        self.m = m
-        self.bdy = bdy
-        self.rhs = rhs
-        self.domain = domain
-        self.bc = bc
-        self.robin_beta = robin_beta
-        self.operator = operator
-        self.boundary_coeffs = None
-        self.domain_coeffs = None
-        self.nonlinearity = None if nonlinearity is None else Nonlinearity.make(nonlinearity)
-
-    _tau = Nonlinear_elliptic2d._tau
-
-    def _posterior_unserved(self):
-        return 'Nonlinear_elliptic3d: gpk_assemble_cross has no rectangular evaluator for the three-dimensional layouts yet'
+        super().__init__(alpha, m, bdy, rhs, domain, bc, robin_beta, operator, nonlinearity)
 
     def get_bd(self, x1, x2, x3):
         return self.bdy(x1, x2, x3)
@@ -801,23 +864,6 @@ class Nonlinear_elliptic3d(_GPEquation):
             raise ValueError(f'points must have shape (n, 3), got {X.shape}')
         return X
 
-    def _set_points(self, X_domain, X_boundary):
-        self.X_domain = self._pts(X_domain)
-        self.N_domain = self.X_domain.shape[0]
-        self.X_boundary = self._pts(X_boundary)
-        self.N_boundary = self.X_boundary.shape[0]
-        self.rhs_f = eval_callback(self.get_rhs, *self.X_domain.T)
-        self.bdy_g = eval_callback(self.get_bd, *self.X_boundary.T)
-        self._drop_device_state()
-        self.boundary_coeffs = None                        # custom operators belong to the points they were set for
-        if self.bc != 'dirichlet':
-            n = boundary_normals3d(self.X_boundary, self.domain)
-            beta = float(self.robin_beta) if self.bc == 'robin' else 0.0
-            self.boundary_coeffs = onp.concatenate([onp.full((self.N_boundary, 1), beta), n], axis=1)
-        self.domain_coeffs = None
-        if self.operator is not None:
-            self.domain_coeffs = self._operator_at(self.X_domain)
-
     def sampled_pts(self, N_domain, N_boundary, sampled_type='random', time_dependent=False):
         """time_dependent: axis 3 is time -- no boundary points on the face x3 = max (sample_points.sampled_pts_rdm3d)"""
         kw = {'time_dependent': True} if time_dependent else {}
@@ -829,160 +875,35 @@ class Nonlinear_elliptic3d(_GPEquation):
             raise ValueError(f'sampled_type {sampled_type!r}: random or grid')
         self._set_points(X_domain, X_boundary)
 
-    # ---- domain operator (N_domain, 10) and boundary operator (N_boundary, 4), or None = the Laplacian / Dirichlet: today's path ----
-    def _operator_at(self, X):
-        """the callable `operator` at the points X (n,3) as an (n,10) array"""
-        rows = self.operator(X[:, 0], X[:, 1], X[:, 2])
-        if len(rows) != 10:
-            raise ValueError(f'operator must return ten coefficient arrays (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33), got {len(rows)}')
-        return onp.stack([onp.broadcast_to(onp.asarray(r, dtype=onp.float64), (X.shape[0],)) for r in rows], axis=1)
+    # ---- which evaluator serves this object: decided here and nowhere else -----------------------------------------------------------
+    def _family(self):
+        """'op': gpk_assemble_op3d / gpk_extend_functionals_op3d, with a domain operator or any non-Dirichlet condition (there is no
+        'bc' family in three dimensions); 'plain': gpk_assemble3d / gpk_extend_functionals3d"""
+        return 'plain' if self.domain_coeffs is None and self.boundary_coeffs is None else 'op'
 
-    def set_domain_operator(self, coeffs):
-        """Row i of coeffs (N_domain, 10) = (c0, b1, b2, b3, a11, a12, a13, a22, a23, a33): the equation at domain point i reads
-        -psi_i[u] + alpha u^m = rhs_f[i].  Call after the points are set; dropped when they change.  Discards the Gram matrix and
-        everything derived from it."""
-        coeffs = onp.array(coeffs, dtype=onp.float64)
-        if coeffs.shape != (self.N_domain, 10):
-            raise ValueError(f'coeffs must have shape ({self.N_domain}, 10), got {coeffs.shape}')
-        self.domain_coeffs = coeffs
-        self._drop_device_state()
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        if self._family() == 'op':
+            T, ratio = ctx.assemble_op3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs, self.boundary_coeffs,
+                                         nugget, nugget_type)
+        else:
+            T, ratio = ctx.assemble3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+        return T, [ratio]
 
-    def set_boundary_operator(self, coeffs):
-        """Row b of coeffs (N_boundary, 4) = (c0, c1, c2, c3): the condition at boundary point b reads c0 u + c . grad u = bdy_g[b].
-        Call after the points are set; dropped when they change.  Discards the Gram matrix and everything derived from it."""
-        coeffs = onp.array(coeffs, dtype=onp.float64)
-        if coeffs.shape != (self.N_boundary, 4):
-            raise ValueError(f'coeffs must have shape ({self.N_boundary}, 4), got {coeffs.shape}')
-        self.boundary_coeffs = coeffs
-        self._drop_device_state()
-
-    def _general(self):
-        """an operator or a non-Dirichlet condition is set: the calls go to gpk_assemble_op3d / gpk_extend_functionals_op3d"""
-        return self.domain_coeffs is not None or self.boundary_coeffs is not None
-
-    def _gn_params(self):
-        return float(self.alpha), float(self.m), 0.0
-
-    def _problem(self):
-        if getattr(self, '_prob', None) is None:
-            if getattr(self, '_dL', None) is None:
-                raise RuntimeError('call Gram_matrix() and Gram_Cholesky() first')
-            p0, p1, lam = self._gn_params()
-            self._prob = gpk.GNProblem(get_context(), self._system, self.N_domain, self.N_boundary, self.rhs_f, self.bdy_g,
-                                       self._dL, **dict(dict(p0=p0, p1=p1), **self._nl_args()), pen_lambda=lam, structured=False)
-        return self._prob
+    def _fields(self, X_test, which):
+        ctx = get_context()
+        args = (self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary)
+        coeff = self._coeff(self._dL, self.sol_vec)
+        if self._family() == 'op':
+            return ctx.extend_functionals_op3d(*args, self.domain_coeffs, self.boundary_coeffs, coeff, which=which)
+        return ctx.extend_functionals3d(*args, coeff, which=which)
 
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
         """kernel_parameter: sigma (Gaussian) or three length scales (anisotropic_Gaussian); stores the trace ratio in `ratio`"""
         require_gaussian_family(kernel, 'Nonlinear_elliptic3d')
-        if nugget_type not in ('adaptive', 'identity', 'none'):
-            raise AttributeError(f"nugget_type {nugget_type!r}: adaptive, identity or none")
-        ctx = get_context()
-        self._drop_device_state()
-        self.nugget_type = nugget_type
-        self.nugget = nugget
-        self.kernel = kernel
-        self.kernel_parameter = kernel_parameter
-        if self._general():
-            self._dTheta, self.ratio = ctx.assemble_op3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs,
-                                                         self.boundary_coeffs, nugget, nugget_type)
-        else:
-            self._dTheta, self.ratio = ctx.assemble3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+        self.ratio = self._assemble(kernel, kernel_parameter, nugget, nugget_type)[0]
 
-    def GN_loss(self, z, z_old):
-        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        zz = onp.concatenate([self._tau().dtau(z_old) * (z - z_old), z, self.bdy_g])
-        return self._tri_loss(zz)
-
-    def Hessian_GN(self, z, z_old):
-        return self._hessian(z_old)          # quadratic in z, as in two dimensions
-
-    def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
-        """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        self.sol_vec = onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g])
-        self.sol_sampled_pts = sol
-
-    def _fields(self, X_test, which):
-        return get_context().extend_functionals3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
-                                                  self._coeff(self._dL, self.sol_vec), which=which)
-
-    def _fields_op(self, X_test, which):
-        return get_context().extend_functionals_op3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
-                                                     self.domain_coeffs, self.boundary_coeffs, self._coeff(self._dL, self.sol_vec),
-                                                     which=which)
-
-    def extend_sol(self, X_test):
-        X_test = self._pts(X_test)
-        self.X_test = X_test
-        self.N_test = X_test.shape[0]
-        fields = self._fields_op if self._general() else self._fields
-        self.extended_sol = fields(X_test, ('value',)).download().reshape(-1)
-
-    def extend_derivatives(self, X_test):
-        """value, d1, d2, d3 and laplacian of the GP solution at X_test (numpy arrays); with a domain operator additionally the six
-        second derivatives d11 .. d33 (laplacian = d11 + d22 + d33)"""
-        X_test = self._pts(X_test)
-        if self.domain_coeffs is not None:
-            r = self._rows(self._fields_op(X_test, self._op_names), self._op_names)
-            self.extended_derivatives = dict({'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'd3': r['d3'],
-                                              'laplacian': r['d11'] + r['d22'] + r['d33']}, **{n: r[n] for n in self._op_names[4:]})
-        elif self._general():
-            names = ('value', 'd1', 'd2', 'd3', 'd11', 'd22', 'd33')
-            r = self._rows(self._fields_op(X_test, names), names)
-            self.extended_derivatives = {'value': r['value'], 'd1': r['d1'], 'd2': r['d2'], 'd3': r['d3'],
-                                         'laplacian': r['d11'] + r['d22'] + r['d33']}
-        else:
-            self.extended_derivatives = self._rows(self._fields(X_test, self._deriv_names), self._deriv_names)
-        return self.extended_derivatives
-
-    def _psi_fields(self, X_test, coeffs_t):
-        """rows value, d1, d2 and psi_t[u] (in the Laplacian's place) for gpk_pde_residual, psi_t from coeffs_t (Nt,10), the callable, or
-        the Laplacian when only the boundary condition is general"""
-        if coeffs_t is None:
-            if self.domain_coeffs is None:
-                coeffs_t = onp.tile((0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 1.0), (X_test.shape[0], 1))
-            elif self.operator is None:
-                raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
-                                 'points as coeffs_t (Nt,10)')
-            else:
-                coeffs_t = self._operator_at(X_test)
-        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
-        if coeffs_t.shape != (X_test.shape[0], 10):
-            raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, 10), got {coeffs_t.shape}')
-        rows = self._fields_op(X_test, self._op_names).download().reshape(10, -1)
-        psi = (coeffs_t.T * rows).sum(axis=0)                     # psi_t[u]: a combination of the ten rows, per test point
-        return get_context().array(onp.stack([rows[0], rows[1], rows[2], psi]))
-
-    def PDE_residual(self, X_test, coeffs_t=None):
-        """pointwise residual -Delta u + alpha u^m - f at X_test from the derivatives of the GP solution (rhs evaluated at X_test); with
-        a domain operator -psi_t[u] + alpha u^m - f, psi_t from the callable `operator` or from coeffs_t (Nt,10) (needed when the
-        operator was set per point; ValueError otherwise)"""
-        X_test = self._pts(X_test)
-        if self.domain_coeffs is None and coeffs_t is not None:
-            raise ValueError('coeffs_t given, but no domain operator is set')
-        if self._general():
-            fields = self._psi_fields(X_test, coeffs_t)
-        else:
-            fields = self._fields(X_test, ('value', 'd1', 'd2', 'laplacian'))  # the rows gpk_pde_residual takes; it reads value and laplacian
-        rhs = eval_callback(self.get_rhs, *X_test.T)
-        self.test_residual = self._residual(fields, None, rhs)
-        return self.test_residual
-
-    def boundary_residual(self, X_bt, coeffs_t, g_t):
-        """c0 u + c . grad u - g of the GP solution at the points X_bt (n,3), with coeffs_t (n,4) = (c0, c1, c2, c3) and g_t (n,) given
-        per point: how well the boundary condition holds between the boundary collocation points (numpy array, also `bdy_residual`)."""
-        X_bt = self._pts(onp.asarray(X_bt, dtype=onp.float64).reshape(-1, 3))
-        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64).reshape(-1, 4)
-        g_t = onp.asarray(g_t, dtype=onp.float64).ravel()
-        if coeffs_t.shape[0] != X_bt.shape[0] or g_t.size != X_bt.shape[0]:
-            raise ValueError(f'{X_bt.shape[0]} points against {coeffs_t.shape[0]} coefficient rows and {g_t.size} values')
-        names = ('value', 'd1', 'd2', 'd3')
-        r = self._rows((self._fields_op if self._general() else self._fields)(X_bt, names), names)
-        self.bdy_residual = coeffs_t[:, 0] * r['value'] + coeffs_t[:, 1] * r['d1'] + coeffs_t[:, 2] * r['d2'] + coeffs_t[:, 3] * r['d3'] - g_t
-        return self.bdy_residual
+    def _posterior_unserved(self):
+        return 'Nonlinear_elliptic3d: gpk_assemble_cross has no rectangular evaluator for the three-dimensional layouts yet'
 
 
 class Burgers(_GPEquation):
