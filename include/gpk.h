@@ -43,7 +43,13 @@ enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 
 /* nugget_type of src/PDEs.py:56,250,391 / src/InverseProblems.py:66 */
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
-enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4 };
+enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5 };
+/* GPK_GN_SEMILINEAR (no counterpart in the reference; DESIGN.md section K, "Gradient-dependent nonlinearity"):
+ *   -eps Delta u + N(u, grad u) = f,   N(u, p, q) = u (a1 p + a2 q) + b (p^2 + q^2) + c1 u + c3 u^3,   p = d_1 u, q = d_2 u,
+ * on the rows of GPK_LAYOUT_EIKONAL ([d_1 u; d_2 u; Delta u; u] per domain point, then the boundary values), unknowns z = [v0 = u | v1 = p | v2 = q]:
+ *   F(z) = [v1; v2; (N(v0, v1, v2) - f) / eps; v0; g],   A(z): 1 at (t, v1_t), (N_d + t, v2_t), (3 N_d + t, v0_t) and
+ *   N_u / eps, N_p / eps, N_q / eps at (2 N_d + t, v0_t / v1_t / v2_t);  N_u = a1 p + a2 q + c1 + 3 c3 u^2, N_p = a1 u + 2 b p, N_q = a2 u + 2 b q.
+ * gpk_gn_problem: p0 = eps (finite, not 0: -9001 otherwise), the five coefficients in gq_a1 .. gq_c3; nonlin must be 0 (-9001). */
 /* Reaction term tau(u) of the elliptic systems, -psi[u] + tau(u) = f ("Reaction terms"); parameters p0, p1, p2:
  *   POWER  p0 pow(u, p1)              (alpha u^m: the reference's equation, and what a zeroed gpk_gn_problem means)
  *   EXP    p0 exp(p1 u)               SINH   p0 sinh(p1 u)              SIN   p0 sin(p1 u)
@@ -134,6 +140,11 @@ int gpk_pde_residual(gpk_handle h, int system, const double* host_params3, int N
  * rows 1 and 2 are not read.  nonlin = GPK_NL_POWER gives the numbers of gpk_pde_residual(GPK_GN_ELLIPTIC).  nonlin outside the enum: -9001. */
 int gpk_pde_residual_nl(gpk_handle h, int nonlin, const double* host_params3, int Nt,
                         const double* fields_u, int ldu, const double* rhs, double* out);
+/* The same for the equation of GPK_GN_SEMILINEAR, host_gq5 = (a1, a2, b, c1, c3):
+ *   r = -eps u3 + N(u0, u1, u2) - f,   rows 0..3 of fields (ld ldf >= Nt) = value, d1, d2, laplacian, as for gpk_pde_residual.
+ * One fixed order of operations: a repeated call gives bit-identical output.  eps 0 or not finite, NULL pointers, Nt <= 0, ldf < Nt: -9001. */
+int gpk_pde_residual_sl(gpk_handle h, double eps, const double* host_gq5, int Nt,
+                        const double* fields, int ldf, const double* rhs, double* out);
 /* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
  *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
  *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
@@ -308,7 +319,7 @@ int gpk_syrk(gpk_handle h, int n, int k, double alpha, const double* A, int lda,
 typedef struct {
     int system;              /* GPK_GN_* */
     int Nd, Nb, Ndata;
-    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, - */
+    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, - */
     double pen_lambda;       /* ELLIPTIC_RELAXED only */
     const double* rhs_f;     /* (Nd,)  */
     const double* bdy_g;     /* (Nb,)  */
@@ -324,6 +335,8 @@ typedef struct {
     const double* G; int ldg; const double* pvec;
     /* optional (may be NULL), GPK_GN_DARCY only -- see gpk_gn_darcy_prepare */
     const double* Wa; int ldwa; const double* Ha; int ldha;
+    /* GPK_GN_SEMILINEAR only: the coefficients (a1, a2, b, c1, c3) of N(u, grad u); five consecutive doubles */
+    double gq_a1, gq_a2, gq_b, gq_c1, gq_c3;
     /* reaction term of ELLIPTIC(_RELAXED): GPK_NL_* with the parameters p0, p1 above and p2 (CUBIC only); 0 = alpha u^m.  Any other
      * system takes 0 only (-9001 otherwise) */
     int nonlin; double p2;

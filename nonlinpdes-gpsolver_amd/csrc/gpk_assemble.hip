@@ -359,6 +359,16 @@ __global__ __launch_bounds__(256) void pde_residual_nl_kernel(int nonlin, double
     out[t] = -u3 + nl_tau(nonlin, p0, p1, p2, u0) - ft;
 }
 
+// the equation of GPK_GN_SEMILINEAR (gpk.h, gpk_pde_residual_sl): r = -eps u3 + N(u0, u1, u2) - f
+struct SlCoeff { double v[5]; };
+__global__ __launch_bounds__(256) void pde_residual_sl_kernel(double eps, SlCoeff gq, int Nt, const double* __restrict__ u, long ldu,
+                                                              const double* __restrict__ f, double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Nt) return;
+    const double u0 = u[t], u1 = u[ldu + t], u2 = u[2 * ldu + t], u3 = u[3 * ldu + t], ft = f[t];
+    out[t] = (sl_N(gq.v, u0, u1, u2) - eps * u3) - ft;
+}
+
 template <int L> constexpr int lay_size(int b, int Nd, int Nb) { return b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0; }
 template <int L> constexpr int lay_N(int Nd, int Nb) { return lay_size<L>(0, Nd, Nb) + lay_size<L>(1, Nd, Nb) + lay_size<L>(2, Nd, Nb) + lay_size<L>(3, Nd, Nb); }
 
@@ -602,6 +612,20 @@ extern "C" int gpk_pde_residual_nl(gpk_handle h, int nonlin, const double* param
         pde_residual_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(GPK_GN_ELLIPTIC, params3[0], params3[1], Nt, fields_u, ldu, nullptr, 0, rhs, out);
     else
         pde_residual_nl_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(nonlin, params3[0], params3[1], params3[2], Nt, fields_u, ldu, rhs, out);
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+extern "C" int gpk_pde_residual_sl(gpk_handle h, double eps, const double* gq5, int Nt, const double* fields, int ldf,
+                                   const double* rhs, double* out) {
+    if (!h) return GPK_ERR_ARG;
+    if (!(std::isfinite(eps) && eps != 0.0)) return gpk_bad_arg(h, "pde_residual_sl: eps must be finite and not 0");
+    if (!gq5) return gpk_bad_arg(h, "pde_residual_sl: host_gq5");
+    if (Nt <= 0) return gpk_bad_arg(h, "pde_residual_sl: Nt <= 0");
+    if (!fields || !rhs || !out || ldf < Nt) return gpk_bad_arg(h, "pde_residual_sl: fields / rhs / out / ldf");
+    SlCoeff gq;
+    for (int k = 0; k < 5; ++k) gq.v[k] = gq5[k];
+    pde_residual_sl_kernel<<<gpk_ceil_div(Nt, 256), 256, 0, h->stream>>>(eps, gq, Nt, fields, ldf, rhs, out);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

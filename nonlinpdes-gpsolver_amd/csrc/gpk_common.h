@@ -344,3 +344,19 @@ __device__ __forceinline__ double nl_dtau(int kind, double p0, double p1, double
     }
 }
 static inline bool gpk_nl_valid(int kind) { return kind >= GPK_NL_POWER && kind <= GPK_NL_CUBIC; }
+
+// Gradient-dependent nonlinearity of GPK_GN_SEMILINEAR (gpk.h; DESIGN.md section K, "Gradient-dependent nonlinearity"), gq = (a1, a2, b,
+// c1, c3):  N(u, p, q) = u (a1 p + a2 q) + b (p p + q q) + u (c1 + c3 u u)  and its partial derivatives (N_u, N_p, N_q).  The one place
+// that knows the form: gn_build_kernel and pde_residual_sl_kernel call it.  Every sum and product is written in ONE order, left to right
+// as spelled (the compiler may fuse a product into the sum that follows it, never reassociate): a repeated call is bit-identical.
+__host__ __device__ __forceinline__ double sl_N(const double* gq, double u, double p, double q) {
+    const double conv = u * (gq[0] * p + gq[1] * q);
+    const double grad = gq[2] * (p * p + q * q);
+    const double reac = u * (gq[3] + gq[4] * (u * u));
+    return (conv + grad) + reac;
+}
+__host__ __device__ __forceinline__ void sl_dN(const double* gq, double u, double p, double q, double* Nu, double* Np, double* Nq) {
+    *Nu = (gq[0] * p + gq[1] * q) + (gq[3] + 3.0 * gq[4] * (u * u));
+    *Np = gq[0] * u + 2.0 * gq[2] * p;
+    *Nq = gq[1] * u + 2.0 * gq[2] * q;
+}

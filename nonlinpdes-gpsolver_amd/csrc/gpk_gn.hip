@@ -27,6 +27,7 @@ int gn_dims(const gpk_gn_problem* p, Dims& d) {
             d.nz = Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 2 * Nd + Nb, 0, p->Dinv}; d.rows = 2 * Nd + Nb; break;
         case GPK_GN_BURGERS:
         case GPK_GN_EIKONAL:
+        case GPK_GN_SEMILINEAR:
             d.nz = 3 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 4 * Nd + Nb, 0, p->Dinv}; d.rows = 4 * Nd + Nb; break;
         case GPK_GN_DARCY:
             if (p->Ndata < 0 || p->Ndata > Nd) return GPK_ERR_ARG;
@@ -56,11 +57,13 @@ struct BuildArgs {
     int system, Nd, Nb, Ndata;
     double p0, p1, lam;
     int nonlin; double p2;   // reaction term of the elliptic systems (GPK_NL_*; nl_tau / nl_dtau of gpk_common.h)
+    double gq[5];            // GPK_GN_SEMILINEAR: (a1, a2, b, c1, c3) of N(u, grad u) (sl_N / sl_dN of gpk_common.h)
     const double* f; const double* gb; const double* data; const double* z;
     double* S; long lds; int fcol; int write_A;
     int rev;           // leading-zero layout of gn_step: unknown j is stored in column nz-1-pos(j), and that column of A(z) is zero above
                        // row pos(j).  1: pos(j) = j (elliptic systems).  2: Eikonal, unknown groups [v0 | v1 | v2] taken in the
-                       // order v1, v2, v0: their first non-zeros sit in rows t, N_d + t, 3 N_d + t >= pos.  3: Burgers, the three
+                       // order v1, v2, v0: their first non-zeros sit in rows t, N_d + t, 3 N_d + t >= pos (the semilinear system runs the
+                       // same order; its v0 columns start in row 2 N_d + t = pos, see step_profile).  3: Burgers, the three
                        // unknowns of point t (columns t, N_d + t, 2 N_d + t all start in row t) interleaved: pos(j) = 3t + group,
                        // a staircase of slope 1/3 (column zero above row pos/3; GpkLz::div = 3).  4: Darcy (round 4), unknown groups
                        // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below
@@ -177,6 +180,19 @@ __global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
             putF(a, 2 * Nd + t, -(ft * ft - v1 * v1 - v2 * v2) / eps);
             putF(a, 3 * Nd + t, v0);
         } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
+    } else if (a.system == GPK_GN_SEMILINEAR) {             // gpk.h, GPK_GN_SEMILINEAR: the Eikonal rows, PDE row (N(v0, v1, v2) - f) / eps
+        const double eps = a.p0;
+        if (t < Nd) {
+            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t];
+            double Nu, Np, Nq;
+            sl_dN(a.gq, v0, v1, v2, &Nu, &Np, &Nq);
+            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0);
+            putA(a, 2 * Nd + t, t, Nu / eps); putA(a, 2 * Nd + t, Nd + t, Np / eps); putA(a, 2 * Nd + t, 2 * Nd + t, Nq / eps);
+            putA(a, 3 * Nd + t, t, 1.0);
+            putF(a, t, v1); putF(a, Nd + t, v2);
+            putF(a, 2 * Nd + t, (sl_N(a.gq, v0, v1, v2) - a.f[t]) / eps);
+            putF(a, 3 * Nd + t, v0);
+        } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
     } else if (a.system == GPK_GN_DARCY) {                  // src/InverseProblems.py:106-117 (F), :127-143 (A)
         const double gam = a.p0;                            // noise_level
         const int U = 3 * Nd, D = 7 * Nd + Nb;
@@ -247,6 +263,7 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     a.system = p->system; a.Nd = p->Nd; a.Nb = p->Nb; a.Ndata = p->Ndata;
     a.p0 = p->p0; a.p1 = p->p1; a.lam = p->pen_lambda;
     a.nonlin = p->nonlin; a.p2 = p->p2;
+    a.gq[0] = p->gq_a1; a.gq[1] = p->gq_a2; a.gq[2] = p->gq_b; a.gq[3] = p->gq_c1; a.gq[4] = p->gq_c3;
     a.f = p->rhs_f; a.gb = p->bdy_g; a.data = p->data_u; a.z = z;
     a.S = S; a.lds = lds; a.fcol = fcol; a.write_A = write_A;
     gn_build_kernel<<<gpk_ceil_div(p->Nd + p->Nb, 256), 256, 0, h->stream>>>(a);
@@ -254,9 +271,13 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     return 0;
 }
 
-// the reaction term is one of the family, and only the elliptic systems have one
+// the reaction term is one of the family, and only the elliptic systems have one; the semilinear system divides its PDE row by eps
 int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
     if (!gpk_nl_valid(p->nonlin)) return gpk_bad_arg(h, "gn: nonlin is not one of GPK_NL_POWER .. GPK_NL_CUBIC");
+    if (p->system == GPK_GN_SEMILINEAR) {
+        if (p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR takes nonlin = 0 only (its nonlinearity is gq_a1 .. gq_c3)");
+        if (!(std::isfinite(p->p0) && p->p0 != 0.0)) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR needs a finite eps (p0) other than 0");
+    }
     if (p->nonlin != GPK_NL_POWER && p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_ELLIPTIC_RELAXED)
         return gpk_bad_arg(h, "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED");
     return 0;
@@ -348,15 +369,18 @@ int exact_loss_chain(gpk_handle h, const Dims& d, bool after_main, bool* on_side
 int step_layout(gpk_handle h, const gpk_gn_problem* p) {
     const bool darcy_lz = p->system == GPK_GN_DARCY && h->tune.eikonal_lz && h->tune.use_dinv && p->Dinv && p->Dinv2 && p->dinv_block > 0;
     return (p->system == GPK_GN_ELLIPTIC || p->system == GPK_GN_ELLIPTIC_RELAXED) ? 1
-         : (p->system == GPK_GN_EIKONAL && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
+         : ((p->system == GPK_GN_EIKONAL || p->system == GPK_GN_SEMILINEAR) && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
 }
 
 // The leading-zero profile of [A(z) | F] under that layout, a pure function of the problem and the handle's switches: the closed form
 // with lead = n_z (slope 1/3 for Burgers); for Eikonal on the GEMM-only solve path the exact two-segment profile for the solve and the
 // products (the substitution path keeps the conservative closed form).  Dense for the layouts 0 and 4: Darcy's two factors have a
 // profile each (darcy_u_profile; the a-part's closed form on its own columns), passed where they are used.
+// The semilinear system shares Eikonal's layout 2 but NEVER its two-segment profile: its v0 columns carry N_u / eps in row 2 N_d + t, N_d
+// rows above Eikonal's first entry, which the second segment would skip -- dropping dN/du from H with no other symptom.  Its exact
+// profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row 2 N_d + t = n_z - 1 - c).
 GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
-    if (rev == 2 && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
+    if (rev == 2 && p->system == GPK_GN_EIKONAL && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
     return (rev >= 1 && rev <= 3) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
@@ -628,7 +652,7 @@ enum class StepProduct { None, SyrkPotrf, Darcy };
 // No side effects.  A mode is chosen only when everything it reads has been prepared; an incomplete preparation falls through to the
 // next line and in the end to Plain.  (The elliptic system has layout 1, and its relaxed form is a system of its own: always Plain.)
 StepMode select_mode(gpk_handle h, const gpk_gn_problem* p, const Dims& d, int rev) {
-    if (!h->tune.structured) return StepMode::Plain;
+    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR) return StepMode::Plain;   // (the semilinear system has no structured form yet)
     const bool ops = p->W1 && p->W2 && p->ldw >= d.nz + 1;           // gpk_gn_structured_prepare
     const bool gram = p->G && p->ldg >= d.nz;                        // gpk_gn_gram_prepare
     if (p->system == GPK_GN_ELLIPTIC && ops && p->v0) return gram && p->pvec ? StepMode::GramElliptic : StepMode::StructuredElliptic;
@@ -791,6 +815,7 @@ extern "C" int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* p, 
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
     if (p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "structured solve: not for the relaxed system");
+    if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR is not served (its PDE row has three z-dependent entries per point)");
     if (elliptic && !v0) return GPK_ERR_ARG;
     const int nc = d.nz + 1;
     if (lds < nc || ldw < nc) return gpk_bad_arg(h, "structured solve: lds/ldw < nz+1");
@@ -826,6 +851,7 @@ extern "C" int gpk_gn_gram_prepare(gpk_handle h, const gpk_gn_problem* p, double
     Dims d;
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
+    if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR is not served (it has no structured form)");
     if (p->system == GPK_GN_ELLIPTIC_RELAXED || !p->W1 || !p->W2 || (elliptic && !p->v0))
         return gpk_bad_arg(h, "gram_prepare: needs W1/W2 (and v0 for the elliptic system) of gpk_gn_structured_prepare; not for the relaxed system");
     const int nz = d.nz;

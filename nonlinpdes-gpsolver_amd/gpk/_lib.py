@@ -21,6 +21,7 @@ class GNProblemStruct(C.Structure):
                 ('W1', C.c_void_p), ('W2', C.c_void_p), ('v0', C.c_void_p), ('ldw', C.c_int),
                 ('G', C.c_void_p), ('ldg', C.c_int), ('pvec', C.c_void_p),
                 ('Wa', C.c_void_p), ('ldwa', C.c_int), ('Ha', C.c_void_p), ('ldha', C.c_int),
+                ('gq_a1', C.c_double), ('gq_a2', C.c_double), ('gq_b', C.c_double), ('gq_c1', C.c_double), ('gq_c3', C.c_double),
                 ('nonlin', C.c_int), ('p2', C.c_double)]
 
 
@@ -92,6 +93,7 @@ PROTOTYPES = {
     'gpk_extend_functionals_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     'gpk_pde_residual': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'gpk_pde_residual_nl': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _vp]),
+    'gpk_pde_residual_sl': (_i, [_vp, _d, _pd, _i, _vp, _i, _vp, _vp]),
     'gpk_potrf': (_i, [_vp, _vp, _i, _i, _pi]),
     'gpk_tril': (_i, [_vp, _vp, _i, _i]),
     'gpk_symmetrize_lower': (_i, [_vp, _vp, _i, _i]),

@@ -34,7 +34,7 @@ def dinv_block_for(n):
     while db > 256 and db > n // 4:
         db //= 2
     return db
-SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4}
+SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4, 'Semilinear2d': 5}
 NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
 EVIDENCE_TERMS = ('log_Z', 'J', 'logdet_theta', 'logdet_H', 'gamma_term', 'two_pi_term')   # host_terms[6] of gpk_log_evidence
 
@@ -139,9 +139,10 @@ class GNProblem:
     """Device-side description of one equation's Gauss-Newton system (gpk_gn_problem)."""
 
     def __init__(self, ctx, system, Nd, Nb, rhs_f, bdy_g, L, p0=0.0, p1=0.0, pen_lambda=0.0, data_u=None, L2=None, dinv=True, structured=False,
-                 cache_a=None, nonlin=0, p2=0.0):
+                 cache_a=None, nonlin=0, p2=0.0, gq=None):
         """nonlin, p2 (elliptic systems only): the reaction term tau(u) -- a GPK_NL_* id or its name in NONLIN -- with the parameters
         p0, p1, p2; 0 / 'power' is p0 u^p1, the reference's equation.
+        gq ('Semilinear2d' only): the coefficients (a1, a2, b, c1, c3) of N(u, grad u); p0 is eps there.
         structured: False (default: the reference's operation sequence every step), True / 1 (prepare_structured), 2 (+ prepare_gram).
         cache_a (Darcy only): keep the iteration-independent a-part of the step (prepare_darcy: bit-identical iterates, less work per step);
         None = on unless GPK_DARCY_CACHE=0.
@@ -163,6 +164,11 @@ class GNProblem:
         s.Ndata = 0 if data_u is None else int(np.asarray(data_u).size)
         s.p0, s.p1, s.pen_lambda = float(p0), float(p1), float(pen_lambda)
         s.nonlin, s.p2 = (NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)), float(p2)
+        if gq is not None:
+            gq = [float(v) for v in gq]
+            if len(gq) != 5:
+                raise ValueError(f'gq: the five coefficients (a1, a2, b, c1, c3), got {len(gq)}')
+            s.gq_a1, s.gq_a2, s.gq_b, s.gq_c1, s.gq_c3 = gq
         s.rhs_f, s.bdy_g = self.rhs_f.ptr, self.bdy_g.ptr
         s.data_u = self.data_u.ptr if self.data_u is not None else None
         s.L, s.ldl = L.ptr, L.ld
@@ -549,6 +555,20 @@ class Context:
         p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]])
         kind = NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)
         self._chk(self.lib.gpk_pde_residual_nl(self.h, kind, p, Nt, du.ptr, du.ld, dr.ptr, out.ptr))
+        self.synchronize()
+        return out
+
+    def pde_residual_sl(self, eps, gq, fields, rhs):
+        """Pointwise residual -eps u3 + N(u0, u1, u2) - f of the semilinear equation with gq = (a1, a2, b, c1, c3)
+        (gpk_pde_residual_sl), as an (Nt,) DeviceArray.  fields: (4, Nt) value, d1, d2, laplacian; rhs as for pde_residual."""
+        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
+        Nt = du.cols
+        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        out = DeviceArray(self, Nt)
+        gq = [float(v) for v in gq]
+        if len(gq) != 5:
+            raise ValueError(f'gq: the five coefficients (a1, a2, b, c1, c3), got {len(gq)}')
+        self._chk(self.lib.gpk_pde_residual_sl(self.h, float(eps), (C.c_double * 5)(*gq), Nt, du.ptr, du.ld, dr.ptr, out.ptr))
         self.synchronize()
         return out
 

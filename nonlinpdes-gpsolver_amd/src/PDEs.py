@@ -1,5 +1,6 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
-same elliptic equation on a box in three space dimensions (no counterpart in the reference).  Four classes on _GPEquation; the two
+same elliptic equation on a box in three space dimensions, and Semilinear2d, the semilinear equation with a gradient-dependent
+nonlinearity on the Eikonal layout (neither has a counterpart in the reference).  Five classes on _GPEquation; the two
 elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
 _family() what sets it apart.
 
@@ -17,7 +18,7 @@ import gpk
 
 from gpk.device import require_gaussian_family
 from ._runtime import eval_callback, get_context
-from .nonlinearity import Nonlinearity
+from .nonlinearity import GradientNonlinearity, Nonlinearity
 from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
@@ -988,3 +989,74 @@ class Eikonal(_GPEquation):
         v3 = -(self.rhs_f ** 2 - v1 ** 2 - v2 ** 2) / self.eps
         self.sol_vec = onp.concatenate([v1, v2, v3, v0, self.bdy_g])
         self.sol_sampled_pts = v0
+
+
+class Semilinear2d(_GPEquation):
+    """-eps Laplace(u) + N(u, grad u) = f on a rectangle, u = g on its boundary, with the gradient-dependent nonlinearity
+    N(u, p, q) = u (a1 p + a2 q) + b (p^2 + q^2) + c1 u + c3 u^3 (src/nonlinearity.py, GradientNonlinearity): steady viscous Burgers /
+    convection, viscous Hamilton-Jacobi and stationary KPZ, the regularised Eikonal equation (b = 1, f -> f^2), Allen-Cahn-type reaction
+    terms next to any of them.  No counterpart in the reference.  The Gram matrix is the Eikonal layout's (rows d_1 u, d_2 u, Laplace(u),
+    u per domain point), so all five kernels serve it; the Gauss-Newton system is GPK_GN_SEMILINEAR with unknowns [u | d_1 u | d_2 u].
+    posterior_variance, posterior_covariance, posterior_sample and log_evidence are the base class's and work as for Eikonal
+    (tests/test_gpu_semilinear.py).  GPK_STRUCTURED is ignored: the system has no structured form yet.
+    Plain Gauss-Newton steps: convection-dominated settings (eps well below 0.1 with |a| = O(1)) do not converge; use eps >= 0.1."""
+    _layout = 'Eikonal'
+    _system = 'Semilinear2d'
+    _blocks_per_point = 3
+    _structured_optin = False
+
+    def __init__(self, eps=0.1, nonlinearity=('burgers', 1.0, 1.0), bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]])):
+        """nonlinearity: a GradientNonlinearity, the five coefficients (a1, a2, b, c1, c3), or a preset -- ('burgers', a1, a2),
+        ('hamilton_jacobi', b, c1), ('eikonal',).  eps: the viscosity, finite and not 0 (ValueError)."""
+        if not (onp.isfinite(eps) and eps != 0):
+            raise ValueError(f'Semilinear2d: eps must be finite and not 0 (the PDE row is divided by it), got {eps!r}')
+        self.eps = eps
+        self.nonlinearity = GradientNonlinearity.make(nonlinearity)
+        self.bdy = bdy
+        self.rhs = rhs
+        self.domain = domain
+
+    def _gn_params(self):
+        return float(self.eps), 0.0, 0.0
+
+    def _nl_args(self):
+        return dict(gq=self.nonlinearity.params)
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
+        """kernel: Gaussian, anisotropic_Gaussian, Matern52, Matern72 or Matern92 (the Eikonal layout takes all five)"""
+        self._assemble(kernel, kernel_parameter, nugget, nugget_type)
+
+    def _split(self, z):
+        Nd = self.N_domain
+        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:]
+
+    def GN_loss(self, z, z_old):
+        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
+        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
+        v0, v1, v2 = self._split(z)
+        u, p, q = self._split(z_old)
+        Nu, Np, Nq = self.nonlinearity.dN(u, p, q)
+        v3 = (self.nonlinearity.N(u, p, q) + Nu * (v0 - u) + Np * (v1 - p) + Nq * (v2 - q) - self.rhs_f) / self.eps
+        return self._tri_loss(onp.concatenate([v1, v2, v3, v0, self.bdy_g]))
+
+    def Hessian_GN(self, z, z_old):
+        return self._hessian(z_old)
+
+    def _initial(self, initial_sol, n):
+        if isinstance(initial_sol, str) and initial_sol == 'zero':
+            return onp.zeros(n)
+        return super()._initial(initial_sol, n)
+
+    def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
+        """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
+        sol = self._initial(initial_sol, 3 * self.N_domain)
+        self.init_sol = sol
+        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
+        v0, v1, v2 = self._split(sol)
+        v3 = (self.nonlinearity.N(v0, v1, v2) - self.rhs_f) / self.eps
+        self.sol_vec = onp.concatenate([v1, v2, v3, v0, self.bdy_g])
+        self.sol_sampled_pts = v0
+
+    def _residual(self, fields_u, fields_a, rhs):
+        """-eps Laplace(u) + N(u, grad u) - f on rows of the extension (gpk_pde_residual_sl)"""
+        return get_context().pde_residual_sl(self.eps, self.nonlinearity.params, fields_u, rhs).download().reshape(-1)

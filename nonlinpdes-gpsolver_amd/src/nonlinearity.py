@@ -71,3 +71,56 @@ class Nonlinearity(object):
     def describe(self):
         """tau(u) as text, e.g. -1.0*exp(1.0*u)"""
         return _FORM[self.name].format(*self.params)
+
+
+class GradientNonlinearity(object):
+    """N(u, p, q) = u (a1 p + a2 q) + b (p^2 + q^2) + c1 u + c3 u^3 of the semilinear equation -eps Laplace(u) + N(u, grad u) = f
+    (p = d_1 u, q = d_2 u) and its partial derivatives on the host (numpy): the mirror of sl_N / sl_dN of csrc/gpk_common.h, written in
+    the same order of operations.  params = (a1, a2, b, c1, c3), what gpk_gn_problem carries as gq_a1 .. gq_c3.
+
+        ('burgers', a1, a2)           u (a1 p + a2 q)              steady viscous Burgers / convection along (a1, a2)
+        ('hamilton_jacobi', b, c1)    b (p^2 + q^2) + c1 u         viscous Hamilton-Jacobi, stationary KPZ
+        ('eikonal',)                  p^2 + q^2                    the regularised Eikonal equation (with f^2 as right-hand side)
+    """
+    PRESETS = {'burgers': 2, 'hamilton_jacobi': 2, 'eikonal': 0}
+
+    def __init__(self, a1=0.0, a2=0.0, b=0.0, c1=0.0, c3=0.0):
+        self.params = tuple(float(v) for v in (a1, a2, b, c1, c3))
+        if not all(onp.isfinite(self.params)):
+            raise ValueError(f'GradientNonlinearity: the coefficients must be finite, got {self.params}')
+        self.a1, self.a2, self.b, self.c1, self.c3 = self.params
+
+    @classmethod
+    def make(cls, spec):
+        """spec: a GradientNonlinearity, the five coefficients (a1, a2, b, c1, c3), or a preset (name, parameters...) of PRESETS"""
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str) or not hasattr(spec, '__len__') or len(spec) < 1:
+            raise ValueError(f"nonlinearity {spec!r}: a GradientNonlinearity, (a1, a2, b, c1, c3) or a preset such as ('burgers', 1.0, 1.0)")
+        if isinstance(spec[0], str):
+            name, args = spec[0], tuple(spec[1:])
+            if name not in cls.PRESETS:
+                raise ValueError(f'nonlinearity preset {name!r}: one of {tuple(cls.PRESETS)}')
+            if len(args) != cls.PRESETS[name]:
+                raise ValueError(f'nonlinearity preset {name!r} takes {cls.PRESETS[name]} parameters, got {len(args)}')
+            if name == 'burgers':
+                return cls(a1=args[0], a2=args[1])
+            if name == 'hamilton_jacobi':
+                return cls(b=args[0], c1=args[1])
+            return cls(b=1.0)
+        if len(spec) != 5:
+            raise ValueError(f'nonlinearity {spec!r}: five coefficients (a1, a2, b, c1, c3), got {len(spec)}')
+        return cls(*spec)
+
+    def N(self, u, p, q):
+        a1, a2, b, c1, c3 = self.params
+        return (u * (a1 * p + a2 * q) + b * (p * p + q * q)) + u * (c1 + c3 * (u * u))
+
+    def dN(self, u, p, q):
+        """(N_u, N_p, N_q)"""
+        a1, a2, b, c1, c3 = self.params
+        return (a1 * p + a2 * q) + (c1 + 3.0 * c3 * (u * u)), a1 * u + 2.0 * b * p, a2 * u + 2.0 * b * q
+
+    def describe(self):
+        a1, a2, b, c1, c3 = self.params
+        return f'u*({a1}*u_x1 + {a2}*u_x2) + {b}*|grad u|^2 + {c1}*u + {c3}*u^3'

@@ -4,8 +4,8 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d
-from .nonlinearity import Nonlinearity
+from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d
+from .nonlinearity import GradientNonlinearity, Nonlinearity
 
 
 def _operator_of(c):
@@ -36,6 +36,15 @@ def _tau_of(c):
     if spec is None or (isinstance(spec, str) and spec == 'power'):
         return None
     return Nonlinearity.make(spec)
+
+
+def _gradient_nl_of(c):
+    """the GradientNonlinearity of a Semilinear2d configuration: cfg.nonlinearity (an instance, five coefficients or a preset), else
+    cfg.nl_params = (a1, a2, b, c1, c3), else the class's default ('burgers', 1, 1)"""
+    spec = getattr(c, 'nonlinearity', None)
+    if spec is None:
+        spec = getattr(c, 'nl_params', None)
+    return GradientNonlinearity.make(('burgers', 1.0, 1.0) if spec is None else spec)
 
 
 def _form_line(c, default):
@@ -106,6 +115,12 @@ _EQUATIONS = {
         lambda c, **k: Eikonal(eps=c.eps, **k),
         lambda c: ['[Equation type] Eikonal equation', '[Equation form] |grad u|^2 = f + eps*Delta u'],
         lambda c: f'[Equation parameter] eps = {c.eps}'),
+    'Semilinear2d': (
+        # (cfg.eps; cfg.nonlinearity: a GradientNonlinearity, five coefficients or a preset; or cfg.nl_params = (a1, a2, b, c1, c3))
+        lambda c, **k: Semilinear2d(eps=c.eps, nonlinearity=_gradient_nl_of(c), **k),
+        lambda c: ['[Equation type] Semilinear equation with a gradient-dependent nonlinearity',
+                   f'[Equation form] - eps*Delta u + N(u, grad u) = f, N = {_gradient_nl_of(c).describe()}'],
+        lambda c: f'[Equation parameter] eps = {c.eps}, (a1, a2, b, c1, c3) = {_gradient_nl_of(c).params}'),
     'Darcy_flow2d': (
         lambda c, **k: Darcy_flow2d(**k),
         lambda c: ['[Inverse problem type] Darcy flow 2d', '[Inverse problem form] -div(a grad u) = f, infer a from f and some observed u'],
