@@ -371,6 +371,42 @@ int gpk_gn_worksize(const gpk_gn_problem* host_prob, int lds, int* host_lds, siz
  * reference's GN_method loop (Hessian, gradient, solve, update, one loss evaluation). */
 int gpk_gn_step(gpk_handle h, const gpk_gn_problem* host_prob, double* z, double step_size,
                 double* S, int lds, double* Hb, int ldh, double* delta, double* host_loss_in, int* host_info);
+/* ---- Backtracking line search for the Gauss-Newton iteration ("Line search").  No reference call site: the
+ *      reference's loop takes a fixed step size.  With delta = H^{-1} g and y = L_H^{-1} g / 2 (the last row of the factored Hb),
+ *        J(z - t delta) ~ J(z) - 2 t |y|^2 + t^2 |y|^2     (the Gauss-Newton model along delta; g . delta = 2 |y|^2),
+ *      and a trial loss J(z - t_k delta) is a measurement vector pushed through the fixed factor(s) of Theta: K trials are ONE K-column
+ *      forward solve.  All entries refuse bad arguments with -9001 (named in gpk_last_error) before anything is launched, serve every
+ *      system gpk_gn_loss serves and take the GEMM-only solve when the problem carries Dinv / Dinv2. */
+#define GPK_LS_MAX_TRIALS 16
+typedef struct { int K; double t0, beta, c1; } gpk_ls_options;   /* zeros mean the defaults 8, 1.0, 0.5, 1e-4 */
+/* gpk_gn_step with the update left out: the same mode selection, the same launches, the same side-stream loss chain.  z is not written;
+ * delta, *host_loss_in and *host_info are what gpk_gn_step returns (bit for bit), *host_pred = |y|^2 = g . delta / 2 (a device dot product
+ * over the last row of the factored Hb): J - pred is the minimum of the linearised loss.  One host synchronisation. */
+int gpk_gn_direction(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, double* S, int lds, double* Hb, int ldh,
+                     double* delta, double* host_loss_in, double* host_pred, int* host_info);
+/* Workspace query (pure host function) for K trials: ldw = the leading dimension the caller intends to use for W (0 = K rounded up to
+ * 16 doubles; returned in *host_ldw); *bytes = what W must hold: the K right-hand sides (s_rows x ldw), the out-of-place result of the
+ * GEMM-only solve (the same again, when every factor comes with its inverted diagonal blocks) and the partial sums of the reduction. */
+int gpk_gn_trial_worksize(const gpk_gn_problem* host_prob, int K, int ldw, int* host_ldw, size_t* bytes);
+/* dev_losses[k] = J(z - host_t[k] delta), k < K, 1 <= K <= GPK_LS_MAX_TRIALS: one launch writes the K measurement vectors F(z - t_k delta)
+ * as the columns of W (the step sizes travel in the kernel arguments; the trial point is formed by the expression the update uses, so an
+ * accepted iterate is bit for bit the point that was measured), one K-column forward solve per factor, column sums of squares.  Of W only
+ * the first K columns of its rows are written, of dev_losses only K doubles.  host_losses may be NULL: then nothing is downloaded and the
+ * call does not synchronise. */
+int gpk_gn_trial_losses(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, const double* delta, const double* host_t, int K,
+                        double* W, int ldw, double* dev_losses, double* host_losses);
+/* Acceptance on the device: trials in the order given; the first k whose loss is finite and <= loss_in - 2 c1 t_k pred; if there is none,
+ * the k of the smallest finite loss provided that loss is < loss_in; otherwise k = -1.  Then z <- z - t_k delta (k = -1: z is not
+ * touched).  *host_k, *host_t_acc (0 for k = -1) come back with one download. */
+int gpk_gn_trial_accept(gpk_handle h, int nz, double* z, const double* delta, const double* dev_losses, const double* host_t, int K,
+                        double loss_in, double pred, double c1, int* host_k, double* host_t_acc);
+/* One line-searched step = gpk_gn_direction + gpk_gn_trial_losses + gpk_gn_trial_accept with t_k = t0 beta^k (t_{k+1} = t_k * beta, one
+ * rounding per trial), all on the device with ONE host synchronisation; the Armijo test uses the substituted loss of the input iterate
+ * (the side-stream chain is joined in front of the acceptance).  opt may be NULL (all defaults).  host_losses: K doubles (may be NULL).
+ * *host_info != 0 (the factorisation of H failed) gives *host_k = -1 and no update. */
+int gpk_gn_step_ls(gpk_handle h, const gpk_gn_problem* host_prob, double* z, const gpk_ls_options* opt, double* S, int lds, double* Hb, int ldh,
+                   double* delta, double* W, int ldw, double* host_loss_in, double* host_losses, int* host_k, double* host_t_acc,
+                   int* host_info);
 /* OPTIONAL structured solve of the elliptic system (not what the reference does per step; off unless W1/W2/v0 are set).  A(z) =
  * [diag(alpha m z^(m-1)); I; 0] has its non-zeros in fixed places and the solve is linear in the right-hand sides, so with
  *   W1 = L^{-1} [I; 0; 0],  W2 = L^{-1} [0; I; 0]   (s_rows x nz each, leading dimension ldw >= nz+1, columns in the internal order of

@@ -56,6 +56,9 @@ int gpk_debug_first_rows(gpk_handle h, const gpk_gn_problem* host_prob, int* out
  * mode: 0 nothing (the Gram levels factor the bordered matrix themselves), 1 the pipelined product + Cholesky, 2 Darcy's two-factor
  * product.  Nothing is launched and no device pointer is dereferenced. */
 int gpk_debug_step_mode(gpk_handle h, const gpk_gn_problem* host_prob, int* mode, int* product);
+/* The first launch of gpk_gn_trial_losses alone: column k < K of W (s_rows x ldw) <- F(z - host_t[k] delta), built and not solved. */
+int gpk_debug_gn_trial_build(gpk_handle h, const gpk_gn_problem* host_prob, const double* z, const double* delta, const double* host_t, int K,
+                             double* W, int ldw);
 /* *host_bytes = current size of the handle's workspace (gpk_i_workspace: the out-of-place solve buffers, partial sums of gpk_col_sumsq): what
  * tests hold against the handle_bytes of gpk_gn_worksize / gpk_posterior_worksize. */
 int gpk_debug_workspace_bytes(gpk_handle h, size_t* host_bytes);

@@ -33,6 +33,11 @@ def add_gn_and_logs(parser, initial_sol, GNsteps, method_choices=None):
     # list of scalars, or per-axis groups separated by ';' ("0.3,0.05;0.2,0.05"); --select_refine K: K golden-section steps (scalars only)
     # opt-in: also draw K samples of the solution on the test grid from its joint posterior (solver_GP.test_samples) and print their
     # spread about the mean; --sample_seed S seeds the standard normals (numpy.random.RandomState(S))
+    # opt-in: backtracking line search in every Gauss-Newton step (src/linesearch.py): K trial steps step_size * shrink^k, Armijo constant c1
+    parser.add_argument("--line_search", type=bool, default=False)
+    parser.add_argument("--ls_trials", type=int, default=8)
+    parser.add_argument("--ls_shrink", type=float, default=0.5)
+    parser.add_argument("--ls_c1", type=float, default=1e-4)
     parser.add_argument("--posterior_samples", type=int, default=0)
     parser.add_argument("--sample_seed", type=int, default=None)
     parser.add_argument("--select_kernel_parameter", type=str, default=None)

@@ -59,3 +59,16 @@ extern "C" int gpk_debug_step_mode(gpk_handle h, const gpk_gn_problem* p, int* m
     *product = (int)select_product(m, rev);
     return 0;
 }
+
+// The first launch of gpk_gn_trial_losses alone: W[:, k] <- F(z - host_t[k] delta), built and NOT solved (tests hold the accepted column
+// against gpk_gn_measurement of the accepted iterate, bit for bit).
+extern "C" int gpk_debug_gn_trial_build(gpk_handle h, const gpk_gn_problem* p, const double* z, const double* delta, const double* host_t, int K,
+                                        double* W, int ldw) {
+    if (!h || !z || !delta || !W) return GPK_ERR_ARG;
+    Dims d;
+    GPK_TRY(check_prob(h, p, d));
+    TrialT ts;
+    GPK_TRY(trial_steps(h, host_t, K, ts));
+    if (ldw < K) return gpk_bad_arg(h, "debug_gn_trial_build: ldw < K");
+    return trial_build(h, p, z, delta, ts, K, W, ldw);
+}

@@ -166,10 +166,12 @@ struct gpk_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int* d_info = nullptr;          // device int: first non-positive pivot (1-based), 0 = none
     double* d_scalars = nullptr;    // small device scratch for reductions (64 doubles).  Slots: [0] in-step loss / border pivot, [1] gpk_gn_loss,
-                                    // [2..3] gpk_error_metrics, [8] exact in-step loss (and the development micro-benchmarks),
+                                    // [2..3] gpk_error_metrics, [8] exact in-step loss (and the development micro-benchmarks), [9] pred = |y|^2 of gpk_gn_direction,
+                                    // [10] accepted t, [11] accepted index (int) and [32 .. 47] the trial losses of gpk_gn_step_ls,
                                     // [GPK_SCALARS_EVIDENCE .. + 5] the (log-determinant, bad-pivot count) pairs of gpk_evidence.hip
-    double* h_pinned = nullptr;     // 8 doubles of pinned host memory: where the end-of-step scalars (loss, pivot status) land -- a copy into
-                                    // pageable memory goes through a staging buffer and a second synchronisation
+    double* h_pinned = nullptr;     // 32 doubles of pinned host memory: where the end-of-step scalars (loss, pivot status) land -- a copy into
+                                    // pageable memory goes through a staging buffer and a second synchronisation.  The line search
+                                    // (gpk_gn.hip) adds [2] pred, [3] accepted index (int), [4] accepted t, [8 .. 23] the trial losses
     int* d_flags = nullptr;         // per-block "solved" epochs of the fused single-vector triangular solve (GPK_MAX_TRSV_BLOCKS ints)
     int trsv_epoch = 0;
     void* d_trsv_gran = nullptr;    // {value, epoch} granules of the fused triangular solve with data-tagged hand-offs (64 per block), allocated on first use
@@ -305,6 +307,8 @@ int gpk_i_workspace(gpk_handle h, size_t bytes, double** out);                  
 int gpk_i_trsm_right_lt(gpk_handle h, const double* L, int n, int ldl, double* X, int m, int ldx);
 int gpk_i_trsv(gpk_handle h, bool trans, const double* L, int n, int ldl, double* x);   // x contiguous
 int gpk_i_dot(gpk_handle h, const double* x, const double* y, int n, double* d_out);    // d_out device scalar
+size_t gpk_i_col_sumsq_scratch_bytes(int rows, int cols);                               // gpk_posterior.hip: partial sums of the reduction below
+int gpk_i_col_sumsq(gpk_handle h, const double* V, int rows, int cols, int ldv, double* out, double* scratch);   // out[t] = sum_r V[r, t]^2 (gpk_col_sumsq's kernels, caller's scratch)
 int gpk_i_ensure_points(gpk_handle h, size_t doubles);
 // pieces of the Gauss-Newton step used by the multi-GPU schedule (gpk_gn.hip)
 int gpk_i_gn_dims(gpk_handle h, const gpk_gn_problem* p, int* nz, int* rows);
@@ -317,7 +321,7 @@ GpkLz gpk_i_gn_darcy_u_profile(int Nd);
 int gpk_i_gn_darcy_add_a(gpk_handle h, const gpk_gn_problem* p, double* Hb, int ldh, int r0, int r1, const double* aF, int ldaf);
 int gpk_i_gn_exact_loss(gpk_handle h, const gpk_gn_problem* p, const double* z, double** d_out);   // gpk_tune key 52: loss(z) by substitution on h->stream
 int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, const double* Hb, int ldh, double* scratch, double* delta,
-                    double* z, double step_size);
+                    double* z, double step_size, bool update = true);   // update = false: delta only, z is not written (line search)
 
 static inline int gpk_ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline bool dinv_block_ok(int db) { return db == 256 || db == 512 || db == 1024 || db == 2048; }   // block sizes of gpk_i_trtri_diag / gpk_i_trsm_left_dinv

@@ -31,7 +31,7 @@ extern "C" int gpk_create(int device, gpk_handle* out) {
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_info, sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_scalars, 64 * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_pinned, 8 * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_pinned, 32 * sizeof(double), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemset(h->d_info, 0, sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_obflags, 64 * sizeof(int));
     if (e == hipSuccess) e = hipMemset(h->d_obflags, 0, 64 * sizeof(int));

@@ -116,11 +116,25 @@ __device__ __forceinline__ void putA(const BuildArgs& a, int r, int c, double v)
 }
 __device__ __forceinline__ void putF(const BuildArgs& a, int r, double v) { a.S[(long)r * a.lds + a.fcol] = v; }
 
-// one thread per collocation index: writes the few non-zeros of A(z) and the entries of F(z) it owns
-__global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+// The ONE expression of an updated point z - t delta (alpha = -t), as the update kernels have always written it (y += alpha x): the
+// update kernels below, the trial points of the line search (ZTrial) and its accepting update all go through it, so that an accepted
+// iterate is bit for bit the point whose loss was measured.
+__device__ __forceinline__ double gn_point(double y, double alpha, double x) { return y + alpha * x; }
+
+// how the build reads the iterate: z itself (gn_build_kernel), or the trial point z - t_k delta formed in registers (gn_trial_build_kernel)
+struct ZPlain {
+    const double* z;
+    __device__ __forceinline__ double operator[](int i) const { return z[i]; }
+};
+struct ZTrial {
+    const double* z; const double* delta; double alpha;
+    __device__ __forceinline__ double operator[](int i) const { return gn_point(z[i], alpha, delta[i]); }
+};
+
+// collocation index t: writes the few non-zeros of A(z) and the entries of F(z) it owns
+template <class Z>
+__device__ __forceinline__ void gn_build_rows(const BuildArgs& a, const int t, const Z z) {
     const int Nd = a.Nd, Nb = a.Nb;
-    const double* z = a.z;
     if (a.system == GPK_GN_ELLIPTIC) {                      // src/PDEs.py:84-85 (F), :95-96 (A)
         if (a.family == 1) {
             if (t < Nd) putA(a, t, t, 1.0);
@@ -236,15 +250,70 @@ __global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
     }
 }
 
+// one thread per collocation index
+__global__ __launch_bounds__(256) void gn_build_kernel(BuildArgs a) {
+    gn_build_rows(a, blockIdx.x * 256 + threadIdx.x, ZPlain{a.z});
+}
+
+// ---- line search: the K trial measurement vectors F(z - t_k delta) in one launch -----------------------------------------------------
+// W (rows x ldw, row-major) receives them as its columns k < K: the right-hand-side layout of the multi-RHS solves.  One thread per
+// (collocation index, trial), the trial running fastest: the K lanes of an index share its loads of z, delta, f and write K adjacent
+// doubles of a row.  No LDS, nothing but the F entries is written (write_A = 0).  The step sizes travel by value in the kernel arguments.
+constexpr int LS_MAX = GPK_LS_MAX_TRIALS;
+struct TrialT { double t[LS_MAX]; };
+
+__global__ __launch_bounds__(256) void gn_trial_build_kernel(BuildArgs a, const double* __restrict__ delta, TrialT ts, int K) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int k = (int)(idx % K);
+    const long t = idx / K;
+    if (t >= (long)a.Nd + a.Nb) return;
+    BuildArgs b = a;
+    b.fcol = k;                                                      // (putF: column k of row r)
+    gn_build_rows(b, (int)t, ZTrial{a.z, delta, -ts.t[k]});
+}
+
 __global__ void axpy_kernel(int n, double alpha, const double* __restrict__ x, double* __restrict__ y) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] += alpha * x[i];
+    if (i < n) y[i] = gn_point(y[i], alpha, x[i]);
 }
 
 // y[j] += alpha * x[n-1-pos(j)]  (back from the staircase order of gn_step to the natural order of the unknowns)
 __global__ void axpy_rev_kernel(int n, double alpha, const double* __restrict__ x, double* __restrict__ y, int rev, int Nd) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] += alpha * x[n - 1 - stair_pos(rev, Nd, i)];
+    if (i < n) y[i] = gn_point(y[i], alpha, x[n - 1 - stair_pos(rev, Nd, i)]);
+}
+
+// Acceptance rule of the line search ("Line search"): trials in the order given; the first k whose loss is finite
+// and <= loss_in - 2 c1 t_k pred; else the k of the smallest finite loss if that is < loss_in; else -1.  A failed factorisation of H
+// (d_info set: neither 0 nor the border pivot nzp1) gives -1.  One lane; K <= 16.
+__global__ void ls_select_kernel(const double* __restrict__ losses, TrialT ts, int K, const double* d_loss_in, const double* d_pred,
+                                 double loss_in, double pred, double c1, const int* d_info, int nzp1, int* __restrict__ d_k,
+                                 double* __restrict__ d_t) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (d_loss_in) loss_in = *d_loss_in;
+    if (d_pred) pred = *d_pred;
+    int k = -1;
+    const int info = d_info ? *d_info : 0;
+    if (info == 0 || info == nzp1) {
+        int best = -1;
+        for (int i = 0; i < K; ++i) {
+            const double l = losses[i];
+            if (!isfinite(l)) continue;
+            if (l <= loss_in - 2.0 * c1 * ts.t[i] * pred) { k = i; break; }
+            if (best < 0 || l < losses[best]) best = i;
+        }
+        if (k < 0 && best >= 0 && losses[best] < loss_in) k = best;
+    }
+    *d_k = k;
+    *d_t = k >= 0 ? ts.t[k] : 0.0;
+}
+
+// z <- z - t_k delta for the accepted k (device scalar; -1: z is not touched), delta in the natural order of the unknowns
+__global__ void ls_update_kernel(int n, const int* __restrict__ d_k, TrialT ts, const double* __restrict__ delta, double* __restrict__ z) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int k = *d_k;
+    if (k < 0 || i >= n) return;
+    z[i] = gn_point(z[i], -ts.t[k], delta[i]);
 }
 
 __global__ void reverse_copy_kernel(int n, const double* __restrict__ x, double* __restrict__ y, int rev, int Nd) {
@@ -257,7 +326,7 @@ __global__ void scale_kernel(int n, double alpha, double* __restrict__ x) {
     if (i < n) x[i] *= alpha;
 }
 
-int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, long lds, int fcol, int write_A, int rev = 0, int family = 0) {
+BuildArgs build_args(const gpk_gn_problem* p, const double* z, double* S, long lds, int fcol, int write_A, int rev, int family) {
     BuildArgs a;
     a.rev = rev; a.nz = fcol; a.family = family;
     a.system = p->system; a.Nd = p->Nd; a.Nb = p->Nb; a.Ndata = p->Ndata;
@@ -266,6 +335,11 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     a.gq[0] = p->gq_a1; a.gq[1] = p->gq_a2; a.gq[2] = p->gq_b; a.gq[3] = p->gq_c1; a.gq[4] = p->gq_c3;
     a.f = p->rhs_f; a.gb = p->bdy_g; a.data = p->data_u; a.z = z;
     a.S = S; a.lds = lds; a.fcol = fcol; a.write_A = write_A;
+    return a;
+}
+
+int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, long lds, int fcol, int write_A, int rev = 0, int family = 0) {
+    const BuildArgs a = build_args(p, z, S, lds, fcol, write_A, rev, family);
     gn_build_kernel<<<gpk_ceil_div(p->Nd + p->Nb, 256), 256, 0, h->stream>>>(a);
     GPK_LAUNCH_CHECK(h);
     return 0;
@@ -925,9 +999,33 @@ extern "C" int gpk_gn_worksize(const gpk_gn_problem* p, int lds, int* host_lds, 
     return 0;
 }
 
-extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, double step_size, double* S, int lds,
-                           double* Hb, int ldh, double* delta, double* host_loss_in, int* host_info) {
-    if (!h || !z || !S || !Hb || !delta) return GPK_ERR_ARG;
+namespace {
+
+// What a caller of step_core wants of the step: gpk_gn_step {update, no pred, finish}; gpk_gn_direction {no update, pred, finish};
+// gpk_gn_step_ls {no update, pred, no finish: it goes on issuing work and reads the scalars itself after ITS one synchronisation}.
+struct StepWant { bool update; double step_size; bool pred; bool finish; };
+
+// after the step's synchronisation: the per-phase timings of a handle with profiling on
+int step_read_prof(gpk_handle h) {
+    if (!h->prof) return 0;
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0.f;
+        GPK_HIP(h, hipEventElapsedTime(&ms, h->pev[i], h->pev[i + 1]));
+        h->prof_ms[i] += (double)ms;
+    }
+    h->prof_cnt += 1;
+    for (int i = 0; i + 1 < h->pipe_tev_used; i += 2) {              // SYRK launches of the pipelined product (GEMM stream)
+        float ms = 0.f;
+        GPK_HIP(h, hipEventElapsedTime(&ms, h->pipe_tev[i], h->pipe_tev[i + 1]));
+        h->prof_syrk_ms += (double)ms;
+    }
+    return 0;
+}
+
+// One Gauss-Newton step up to (want.update: and including) the update of z.  *d_loss_out: the device scalar that holds the loss of the
+// input iterate once the handle's stream has passed the point where this function returns (want.finish == false), h->d_scalars[9]: pred.
+int step_core(gpk_handle h, const gpk_gn_problem* p, double* z, const StepWant& want, double* S, int lds, double* Hb, int ldh, double* delta,
+              double* host_loss_in, double* host_pred, int* host_info, const double** d_loss_out) {
     Dims d;
     GPK_TRY(check_prob(h, p, d));
     const int nz = d.nz;
@@ -967,32 +1065,212 @@ extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, dou
         GPK_TRY(exact_loss_chain(h, d, !h->prof_pipelined, &chain_on_side));
         chain_guard.armed = chain_on_side;
     }
-    GPK_TRY(gpk_i_gn_finish(h, p, nz, rev, Hb, ldh, S, delta, z, step_size));   // (S is free now: scratch for the reversed-order solution)
+    GPK_TRY(gpk_i_gn_finish(h, p, nz, rev, Hb, ldh, S, delta, z, want.step_size, want.update));   // (S is free now: scratch for the reversed-order solution)
+    // pred = |y|^2 = g . delta / 2 over the last row of the factored Hb (the backward solve above worked on a copy of it)
+    if (want.pred) GPK_TRY(gpk_i_dot(h, Hb + (long)nz * ldh, Hb + (long)nz * ldh, nz, h->d_scalars + 9));
     GPK_PROF_MARK(h, 4);
+    const double* d_loss_final = o.exact ? h->d_scalars + 8 : d_loss;
+    if (d_loss_out) *d_loss_out = d_loss_final;
+    if (!want.finish) {
+        // the caller goes on on the handle's stream: join the chain there (everything issued later, the next call's memset of d_loss_work
+        // included, is ordered behind it) and leave the scalars on the device
+        if (chain_on_side) GPK_HIP(h, hipStreamWaitEvent(h->stream, h->ev_loss[1], 0));
+        chain_guard.armed = false;
+        return 0;
+    }
     // the two host scalars of the step through pinned memory (h_pinned[0] = loss, the int behind h_pinned[1] = pivot status)
     GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (want.pred) GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 2, h->d_scalars + 9, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (chain_on_side) GPK_HIP(h, hipStreamWaitEvent(h->stream, h->ev_loss[1], 0));
-    GPK_HIP(h, hipMemcpyAsync(h->h_pinned, o.exact ? h->d_scalars + 8 : d_loss, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned, d_loss_final, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     GPK_HIP(h, hipStreamSynchronize(h->stream));
     chain_guard.armed = false;                                       // the main stream waited for the chain's event: it is complete
     int info = *reinterpret_cast<const int*>(h->h_pinned + 1);
     const double loss = h->h_pinned[0];
-    if (h->prof) {
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.f;
-            GPK_HIP(h, hipEventElapsedTime(&ms, h->pev[i], h->pev[i + 1]));
-            h->prof_ms[i] += (double)ms;
-        }
-        h->prof_cnt += 1;
-        for (int i = 0; i + 1 < h->pipe_tev_used; i += 2) {          // SYRK launches of the pipelined product (GEMM stream)
-            float ms = 0.f;
-            GPK_HIP(h, hipEventElapsedTime(&ms, h->pipe_tev[i], h->pipe_tev[i + 1]));
-            h->prof_syrk_ms += (double)ms;
-        }
-    }
+    GPK_TRY(step_read_prof(h));
     if (info == nz + 1) info = 0;          // the border pivot loss - y^T y is not part of H (may round below zero)
     if (host_info) *host_info = info;
     if (host_loss_in) *host_loss_in = loss;
+    if (host_pred) *host_pred = h->h_pinned[2];
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gpk_gn_step(gpk_handle h, const gpk_gn_problem* p, double* z, double step_size, double* S, int lds,
+                           double* Hb, int ldh, double* delta, double* host_loss_in, int* host_info) {
+    if (!h || !z || !S || !Hb || !delta) return GPK_ERR_ARG;
+    return step_core(h, p, z, StepWant{true, step_size, false, true}, S, lds, Hb, ldh, delta, host_loss_in, nullptr, host_info, nullptr);
+}
+
+extern "C" int gpk_gn_direction(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, int lds, double* Hb, int ldh,
+                                double* delta, double* host_loss_in, double* host_pred, int* host_info) {
+    if (!h) return GPK_ERR_ARG;
+    if (!z || !S || !Hb || !delta) return gpk_bad_arg(h, "gn_direction: null z / S / Hb / delta");
+    // (z is read only: want.update = false takes the update launch out of the tail and nothing else writes it)
+    return step_core(h, p, const_cast<double*>(z), StepWant{false, 0.0, true, true}, S, lds, Hb, ldh, delta, host_loss_in, host_pred, host_info,
+                     nullptr);
+}
+
+// ---- line search ("Line search") ---------------------------------------------------------------------------------
+namespace {
+
+// The caller's trial workspace W: [B: rows x ldw, the K right-hand sides | X: rows x ldw, the out-of-place result of the GEMM-only solve,
+// present when every factor comes with its inverted diagonal blocks | the partial sums of the column reduction].  A function of the
+// problem, K and ldw alone: gpk_gn_trial_worksize and the calls agree on it whatever the handle's switches say.
+struct TrialLayout { int ldw; size_t b_doubles, x_doubles, red_bytes; };
+
+int trial_layout(const Dims& d, int K, int ldw, TrialLayout& t) {
+    if (K < 1 || K > LS_MAX) return GPK_ERR_ARG;
+    if (ldw == 0) ldw = ((K + 15) / 16) * 16;
+    if (ldw < K) return GPK_ERR_ARG;
+    t.ldw = ldw;
+    t.b_doubles = (size_t)d.rows * ldw;
+    t.x_doubles = every_factor_has_dinv(d) ? t.b_doubles : 0;
+    t.red_bytes = gpk_i_col_sumsq_scratch_bytes(d.rows, K);
+    return 0;
+}
+
+int trial_steps(gpk_handle h, const double* host_t, int K, TrialT& ts) {
+    if (K < 1 || K > LS_MAX) return gpk_bad_arg(h, "line search: K must be 1 .. GPK_LS_MAX_TRIALS (16)");
+    if (!host_t) return gpk_bad_arg(h, "line search: null step sizes");
+    for (int k = 0; k < LS_MAX; ++k) ts.t[k] = k < K ? host_t[k] : 0.0;
+    for (int k = 0; k < K; ++k) if (!std::isfinite(ts.t[k])) return gpk_bad_arg(h, "line search: a step size is not finite");
+    return 0;
+}
+
+// F(z - t_k delta), k < K, into the columns of W (rows x ldw); nothing else of W is written
+int trial_build(gpk_handle h, const gpk_gn_problem* p, const double* z, const double* delta, const TrialT& ts, int K, double* W, int ldw) {
+    const BuildArgs a = build_args(p, z, W, ldw, 0, 0, 0, 0);
+    const long threads = (long)(p->Nd + p->Nb) * K;
+    gn_trial_build_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, h->stream>>>(a, delta, ts, K);
+    GPK_LAUNCH_CHECK(h);
+    return 0;
+}
+
+// dev_losses[k] = J(z - t_k delta): the build, one K-column forward solve per factor, the column sums of squares; all on h->stream
+int trial_losses_issue(gpk_handle h, const gpk_gn_problem* p, const Dims& d, const double* z, const double* delta, const TrialT& ts, int K,
+                       double* W, const TrialLayout& t, double* dev_losses) {
+    const bool dinv = h->tune.use_dinv && t.x_doubles > 0;
+    const int db = p->dinv_block > 0 ? p->dinv_block : 256;
+    if (dinv && !dinv_block_ok(db)) return gpk_bad_arg(h, "gn: dinv_block must be 256, 512, 1024 or 2048");
+    const int ldw = t.ldw;
+    double* B = W;
+    double* X = W + t.b_doubles;
+    double* red = W + t.b_doubles + t.x_doubles;
+    GPK_TRY(trial_build(h, p, z, delta, ts, K, B, ldw));
+    for (int k = 0; k < d.ngroups; ++k) {
+        const Group& g = d.g[k];
+        if (g.n <= 0) continue;
+        double* Bg = B + (long)g.off * ldw;
+        if (!g.L) {                                                  // rows without a factor: the build scaled them (1 / sqrt(lambda), 1 / gamma)
+            if (dinv) GPK_HIP(h, hipMemcpy2DAsync(X + (long)g.off * ldw, (size_t)ldw * 8, Bg, (size_t)ldw * 8, (size_t)K * 8, g.n,
+                                                  hipMemcpyDeviceToDevice, h->stream));
+        } else if (dinv) {
+            GPK_TRY(gpk_i_trsm_left_dinv(h, g.L, g.Dinv, db, g.n, g.ldl, Bg, ldw, X + (long)g.off * ldw, ldw, K, GpkLz()));
+        } else {
+            GPK_TRY(gpk_i_trsm_left_mt(h, false, g.L, g.n, g.ldl, Bg, K, ldw));
+        }
+    }
+    return gpk_i_col_sumsq(h, dinv ? X : B, d.rows, K, ldw, dev_losses, red);
+}
+
+// the accepted index (-> the int at d_scalars[11]) and step (-> d_scalars[10]) from the K losses, then the update of z
+int accept_issue(gpk_handle h, int nz, double* z, const double* delta, const double* dev_losses, const TrialT& ts, int K, const double* d_loss_in,
+                 const double* d_pred, double loss_in, double pred, double c1, const int* d_info) {
+    int* d_k = reinterpret_cast<int*>(h->d_scalars + 11);
+    ls_select_kernel<<<1, 64, 0, h->stream>>>(dev_losses, ts, K, d_loss_in, d_pred, loss_in, pred, c1, d_info, nz + 1, d_k, h->d_scalars + 10);
+    GPK_LAUNCH_CHECK(h);
+    ls_update_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, d_k, ts, delta, z);
+    GPK_LAUNCH_CHECK(h);
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 3, d_k, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 4, h->d_scalars + 10, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gpk_gn_trial_worksize(const gpk_gn_problem* p, int K, int ldw, int* host_ldw, size_t* bytes) {
+    Dims d;
+    TrialLayout t;
+    if (!p || gn_dims(p, d) != 0 || trial_layout(d, K, ldw, t) != 0) return GPK_ERR_ARG;
+    if (host_ldw) *host_ldw = t.ldw;
+    if (bytes) *bytes = (t.b_doubles + t.x_doubles) * sizeof(double) + t.red_bytes;
+    return 0;
+}
+
+extern "C" int gpk_gn_trial_losses(gpk_handle h, const gpk_gn_problem* p, const double* z, const double* delta, const double* host_t, int K,
+                                   double* W, int ldw, double* dev_losses, double* host_losses) {
+    if (!h) return GPK_ERR_ARG;
+    if (!z || !delta || !W || !dev_losses) return gpk_bad_arg(h, "gn_trial_losses: null z / delta / W / dev_losses");
+    Dims d;
+    GPK_TRY(check_prob(h, p, d));
+    TrialT ts;
+    GPK_TRY(trial_steps(h, host_t, K, ts));
+    TrialLayout t;
+    if (ldw <= 0 || trial_layout(d, K, ldw, t) != 0) return gpk_bad_arg(h, "gn_trial_losses: ldw < K");
+    GPK_TRY(trial_losses_issue(h, p, d, z, delta, ts, K, W, t, dev_losses));
+    if (!host_losses) return 0;                                      // nothing is downloaded, nothing synchronises
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 8, dev_losses, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < K; ++k) host_losses[k] = h->h_pinned[8 + k];
+    return 0;
+}
+
+extern "C" int gpk_gn_trial_accept(gpk_handle h, int nz, double* z, const double* delta, const double* dev_losses, const double* host_t, int K,
+                                   double loss_in, double pred, double c1, int* host_k, double* host_t_acc) {
+    if (!h) return GPK_ERR_ARG;
+    if (nz <= 0 || !z || !delta || !dev_losses) return gpk_bad_arg(h, "gn_trial_accept: nz <= 0 or null z / delta / dev_losses");
+    if (!(c1 > 0.0 && c1 < 1.0)) return gpk_bad_arg(h, "gn_trial_accept: c1 must lie in (0, 1)");
+    TrialT ts;
+    GPK_TRY(trial_steps(h, host_t, K, ts));
+    GPK_TRY(accept_issue(h, nz, z, delta, dev_losses, ts, K, nullptr, nullptr, loss_in, pred, c1, nullptr));
+    GPK_HIP(h, hipStreamSynchronize(h->stream));
+    if (host_k) *host_k = *reinterpret_cast<const int*>(h->h_pinned + 3);
+    if (host_t_acc) *host_t_acc = h->h_pinned[4];
+    return 0;
+}
+
+extern "C" int gpk_gn_step_ls(gpk_handle h, const gpk_gn_problem* p, double* z, const gpk_ls_options* opt, double* S, int lds, double* Hb, int ldh,
+                              double* delta, double* W, int ldw, double* host_loss_in, double* host_losses, int* host_k, double* host_t_acc,
+                              int* host_info) {
+    if (!h) return GPK_ERR_ARG;
+    if (!z || !S || !Hb || !delta || !W) return gpk_bad_arg(h, "gn_step_ls: null z / S / Hb / delta / W");
+    const int K = (opt && opt->K) ? opt->K : 8;
+    const double t0 = (opt && opt->t0 != 0.0) ? opt->t0 : 1.0, beta = (opt && opt->beta != 0.0) ? opt->beta : 0.5;
+    const double c1 = (opt && opt->c1 != 0.0) ? opt->c1 : 1e-4;
+    if (K < 1 || K > LS_MAX) return gpk_bad_arg(h, "line search: K must be 1 .. GPK_LS_MAX_TRIALS (16)");
+    if (!(t0 > 0.0 && std::isfinite(t0))) return gpk_bad_arg(h, "line search: t0 must be positive and finite");
+    if (!(beta > 0.0 && beta < 1.0)) return gpk_bad_arg(h, "line search: beta must lie in (0, 1)");
+    if (!(c1 > 0.0 && c1 < 1.0)) return gpk_bad_arg(h, "line search: c1 must lie in (0, 1)");
+    Dims d;
+    GPK_TRY(check_prob(h, p, d));
+    TrialLayout t;
+    if (ldw <= 0 || trial_layout(d, K, ldw, t) != 0) return gpk_bad_arg(h, "gn_step_ls: ldw < K");
+    TrialT ts;
+    for (int k = 0; k < LS_MAX; ++k) ts.t[k] = 0.0;
+    ts.t[0] = t0;
+    for (int k = 1; k < K; ++k) ts.t[k] = ts.t[k - 1] * beta;        // t_k = t0 beta^k by repeated multiplication: one rounding per trial
+    const double* d_loss = nullptr;
+    GPK_TRY(step_core(h, p, z, StepWant{false, 0.0, true, false}, S, lds, Hb, ldh, delta, nullptr, nullptr, nullptr, &d_loss));
+    double* dev_losses = h->d_scalars + 32;
+    GPK_TRY(trial_losses_issue(h, p, d, z, delta, ts, K, W, t, dev_losses));
+    // the Armijo test uses the exact substituted loss: step_core has joined its chain to the handle's stream already, in FRONT of the trial
+    // build and solve (the acceptance is its only consumer; joining there instead would let the chain run beside the K-column solve -- not
+    // measured, DESIGN.md section K "Line search")
+    GPK_TRY(accept_issue(h, d.nz, z, delta, dev_losses, ts, K, d_loss, h->d_scalars + 9, 0.0, 0.0, c1, h->d_info));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned, d_loss, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipMemcpyAsync(h->h_pinned + 8, dev_losses, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    GPK_HIP(h, hipStreamSynchronize(h->stream));                     // the one host synchronisation of the call
+    GPK_TRY(step_read_prof(h));
+    int info = *reinterpret_cast<const int*>(h->h_pinned + 1);
+    if (info == d.nz + 1) info = 0;
+    if (host_info) *host_info = info;
+    if (host_loss_in) *host_loss_in = h->h_pinned[0];
+    if (host_losses) for (int k = 0; k < K; ++k) host_losses[k] = h->h_pinned[8 + k];
+    if (host_k) *host_k = *reinterpret_cast<const int*>(h->h_pinned + 3);
+    if (host_t_acc) *host_t_acc = h->h_pinned[4];
     return 0;
 }
 
@@ -1114,14 +1392,14 @@ int gpk_i_gn_dims(gpk_handle h, const gpk_gn_problem* p, int* nz, int* rows) {
 // The tail of a step once the bordered matrix Hb is factored (its last row = (L_H^{-1} g/2)^T): backward solve, back to the natural
 // order of the unknowns (rev: the staircase order of gpk_gn_step), update of z.  scratch: nz doubles (rev only).
 int gpk_i_gn_finish(gpk_handle h, const gpk_gn_problem* p, int nz, int rev, const double* Hb, int ldh, double* scratch, double* delta,
-                    double* z, double step_size) {
+                    double* z, double step_size, bool update) {
     double* dl = rev ? scratch : delta;
     GPK_HIP(h, hipMemcpyAsync(dl, Hb + (long)nz * ldh, (size_t)nz * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     GPK_TRY(gpk_i_trsv(h, true, Hb, nz, ldh, dl));
     if (rev) {
         reverse_copy_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, dl, delta, rev, p->Nd);
-        axpy_rev_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, -step_size, dl, z, rev, p->Nd);
-    } else {
+        if (update) axpy_rev_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, -step_size, dl, z, rev, p->Nd);
+    } else if (update) {
         axpy_kernel<<<gpk_ceil_div(nz, 256), 256, 0, h->stream>>>(nz, -step_size, delta, z);
     }
     GPK_LAUNCH_CHECK(h);

@@ -163,6 +163,12 @@ __global__ __launch_bounds__(256) void bcast_rows_kernel(const double* __restric
 
 }  // namespace
 
+// the same reduction for the trial losses of the line search (gpk_gn.hip): the caller's scratch, the handle's workspace is not touched
+size_t gpk_i_col_sumsq_scratch_bytes(int rows, int cols) { return col_scratch_bytes(rows, cols); }
+int gpk_i_col_sumsq(gpk_handle h, const double* V, int rows, int cols, int ldv, double* out, double* scratch) {
+    return col_sumsq(h, V, rows, cols, ldv, 1.0, nullptr, 0.0, out, scratch);
+}
+
 extern "C" int gpk_col_sumsq(gpk_handle h, const double* V, int rows, int cols, int ldv, double alpha, const double* base, double* out) {
     if (!h) return GPK_ERR_ARG;
     if (!V || !out) return gpk_bad_arg(h, "col_sumsq: pointers");

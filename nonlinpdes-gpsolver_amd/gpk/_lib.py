@@ -25,6 +25,11 @@ class GNProblemStruct(C.Structure):
                 ('nonlin', C.c_int), ('p2', C.c_double)]
 
 
+class LSOptionsStruct(C.Structure):
+    """gpk_ls_options: zeros mean the defaults 8, 1.0, 0.5, 1e-4"""
+    _fields_ = [('K', C.c_int), ('t0', C.c_double), ('beta', C.c_double), ('c1', C.c_double)]
+
+
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
 _pi, _pd, _pvp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_void_p)
 _pp = C.POINTER(GNProblemStruct)
@@ -113,6 +118,11 @@ PROTOTYPES = {
     'gpk_gn_dims': (_i, [_pp, _pi, _pi]),
     'gpk_gn_worksize': (_i, [_pp, _i, _pi, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     'gpk_gn_step': (_i, [_vp, _pp, _vp, _d, _vp, _i, _vp, _i, _vp, _pd, _pi]),
+    'gpk_gn_direction': (_i, [_vp, _pp, _vp, _vp, _i, _vp, _i, _vp, _pd, _pd, _pi]),
+    'gpk_gn_trial_worksize': (_i, [_pp, _i, _i, _pi, C.POINTER(_sz)]),
+    'gpk_gn_trial_losses': (_i, [_vp, _pp, _vp, _vp, _pd, _i, _vp, _i, _vp, _pd]),
+    'gpk_gn_trial_accept': (_i, [_vp, _i, _vp, _vp, _vp, _pd, _i, _d, _d, _d, _pi, _pd]),
+    'gpk_gn_step_ls': (_i, [_vp, _pp, _vp, C.POINTER(LSOptionsStruct), _vp, _i, _vp, _i, _vp, _vp, _i, _pd, _pd, _pi, _pd, _pi]),
     'gpk_gn_structured_prepare': (_i, [_vp, _pp, _vp, _i, _vp, _vp, _vp, _i]),
     'gpk_gn_gram_prepare': (_i, [_vp, _pp, _vp, _i, _vp]),
     'gpk_gn_darcy_prepare': (_i, [_vp, _pp, _vp, _i, _vp, _i, _vp, _i]),
@@ -149,6 +159,7 @@ DEV_PROTOTYPES = {
     'gpk_debug_syrk_lz': (_i, [_vp, _i, _i, _d, _vp, _i, _d, _vp, _i, _i]),
     'gpk_debug_first_rows': (_i, [_vp, _pp, _pi, _pi]),
     'gpk_debug_step_mode': (_i, [_vp, _pp, _pi, _pi]),
+    'gpk_debug_gn_trial_build': (_i, [_vp, _pp, _vp, _vp, _pd, _i, _vp, _i]),
     'gpk_debug_workspace_bytes': (_i, [_vp, C.POINTER(_sz)]),
 }
 

@@ -249,7 +249,25 @@ class GNProblem:
             self._work = DeviceArray(self.ctx, self.rows)
         return self._S, self._H, self._delta, self._work
 
+    def trial_workspace(self, K=16):
+        """(W, ldw, dev_losses) for up to K trial steps of the line search (gpk_gn_trial_worksize); grown when a larger K is asked for"""
+        K = int(K)
+        if getattr(self, '_trial', None) is None or self._trial[3] < K:
+            self.release_trial_workspace()
+            ldw, nbytes = C.c_int(), C.c_size_t()
+            rc = self.ctx.lib.gpk_gn_trial_worksize(C.byref(self.struct), K, 0, C.byref(ldw), C.byref(nbytes))
+            if rc != 0:
+                raise GpkError(f'gpk_gn_trial_worksize: {rc} (1 <= K <= 16, got {K})')
+            self._trial = (DeviceArray(self.ctx, (nbytes.value + 7) // 8), ldw.value, DeviceArray(self.ctx, 16), K)
+        return self._trial[:3]
+
+    def release_trial_workspace(self):
+        t, self._trial = getattr(self, '_trial', None), None
+        if t is not None:
+            t[0].free(); t[2].free()
+
     def release_workspace(self):
+        self.release_trial_workspace()
         for a in (self._S, self._H, self._delta, self._work):
             if a is not None:
                 a.free()
@@ -642,6 +660,49 @@ class Context:
         self._chk(self.lib.gpk_gn_step(self.h, C.byref(prob.struct), z.ptr, float(step_size), S.ptr, S.ld, H.ptr, H.ld,
                                        delta.ptr, C.byref(loss), C.byref(info)))
         return loss.value, self._chk_info(info.value)
+
+    # ---- line search (gpk_gn_direction, gpk_gn_trial_losses, gpk_gn_trial_accept, gpk_gn_step_ls) ----
+    def gn_direction(self, prob, z):
+        """(loss(z), pred, info): gn_step without the update -- delta = H^{-1} g is left in prob.workspace()[2], z is not written;
+        pred = g . delta / 2, so loss - pred is the minimum of the linearised loss"""
+        S, H, delta, _ = prob.workspace()
+        loss, pred, info = C.c_double(), C.c_double(), C.c_int()
+        self._chk(self.lib.gpk_gn_direction(self.h, C.byref(prob.struct), z.ptr, S.ptr, S.ld, H.ptr, H.ld, delta.ptr,
+                                            C.byref(loss), C.byref(pred), C.byref(info)))
+        return loss.value, pred.value, self._chk_info(info.value)
+
+    def gn_trial_losses(self, prob, z, t, delta=None, download=True):
+        """J(z - t_k delta) for the step sizes t (1 .. 16 of them): numpy array, or (download=False: no synchronisation) the DeviceArray
+        that holds them in its first len(t) entries.  delta: a DeviceArray, default the direction of the last gn_direction / gn_step."""
+        t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        delta = prob.workspace()[2] if delta is None else delta
+        W, ldw, dl = prob.trial_workspace(max(t.size, 1))
+        out = np.empty(t.size) if download else None
+        self._chk(self.lib.gpk_gn_trial_losses(self.h, C.byref(prob.struct), z.ptr, delta.ptr, t.ctypes.data_as(C.POINTER(C.c_double)), t.size,
+                                               W.ptr, ldw, dl.ptr, out.ctypes.data_as(C.POINTER(C.c_double)) if download else None))
+        return out if download else dl
+
+    def gn_trial_accept(self, prob, z, losses, t, loss_in, pred, c1=1e-4, delta=None):
+        """(k, t_k): the acceptance rule on the device over `losses` (a DeviceArray, as gn_trial_losses(download=False) returns it) and
+        z <- z - t_k delta; k = -1 (t = 0.0) leaves z untouched"""
+        t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        delta = prob.workspace()[2] if delta is None else delta
+        k, ta = C.c_int(), C.c_double()
+        self._chk(self.lib.gpk_gn_trial_accept(self.h, prob.nz, z.ptr, delta.ptr, losses.ptr, t.ctypes.data_as(C.POINTER(C.c_double)), t.size,
+                                               float(loss_in), float(pred), float(c1), C.byref(k), C.byref(ta)))
+        return k.value, ta.value
+
+    def gn_step_ls(self, prob, z, trials=8, t0=1.0, shrink=0.5, c1=1e-4):
+        """One line-searched Gauss-Newton step, one host synchronisation: (loss(z_in), info, k, t_k, trial losses).  k = -1: no trial
+        reduced the loss (or the factorisation of H failed) and z is unchanged."""
+        S, H, delta, _ = prob.workspace()
+        W, ldw, _ = prob.trial_workspace(trials)
+        opt = _libmod.LSOptionsStruct(int(trials), float(t0), float(shrink), float(c1))
+        loss, info, k, ta = C.c_double(), C.c_int(), C.c_int(), C.c_double()
+        losses = np.empty(int(trials))
+        self._chk(self.lib.gpk_gn_step_ls(self.h, C.byref(prob.struct), z.ptr, C.byref(opt), S.ptr, S.ld, H.ptr, H.ld, delta.ptr, W.ptr, ldw,
+                                          C.byref(loss), losses.ctypes.data_as(C.POINTER(C.c_double)), C.byref(k), C.byref(ta), C.byref(info)))
+        return loss.value, self._chk_info(info.value), k.value, ta.value, losses
 
     def gn_loss(self, prob, z):
         _, _, _, work = prob.workspace()

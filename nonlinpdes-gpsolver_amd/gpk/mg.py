@@ -294,7 +294,9 @@ class MultiGpu:
         self.ctx._chk(self.lib.gpk_mg_potrf(self.h, A_ptr, int(n), int(lda), C.byref(info)))
         return self.ctx._chk_info(info.value)
 
-    def gn_step(self, prob_struct, z_ptr, step_size, S_ptr, lds, S2_ptr, Hb_ptr, ldh, delta_ptr):
+    def gn_step(self, prob_struct, z_ptr, step_size, S_ptr, lds, S2_ptr, Hb_ptr, ldh, delta_ptr, line_search=None):
+        if line_search is not None:
+            raise NotImplementedError('line search: the sharded multi-GPU step takes a fixed step size; run the single-GPU step (gn_step_ls)')
         loss, info = C.c_double(), C.c_int()
         self.ctx._chk(self.lib.gpk_mg_gn_step(self.h, C.byref(prob_struct), z_ptr, float(step_size), S_ptr, int(lds), S2_ptr, Hb_ptr, int(ldh),
                                               delta_ptr, C.byref(loss), C.byref(info)))

@@ -345,13 +345,18 @@ class ShardedFactorSolve:
         computed by the library (gpk_mg_column_bounds: the native step uses the same function)."""
         return _mg.column_bounds(ncols, lead, rows, self.P, self.col_align)
 
-    def gn_step(self, prob_struct, nz, rows, L, z, S, Hb, delta, step_size, rev=False, Dinv=None, S2=None):
+    def gn_step(self, prob_struct, nz, rows, L, z, S, Hb, delta, step_size, rev=False, Dinv=None, S2=None, line_search=None):
         """One Gauss-Newton step with S column-sharded and Hb row-block-sharded; z is updated identically on all ranks.
         L: replicated factor (rows x rows); S: (rows, >= nz+1); Hb: (nz+1, >= nz+1); returns (loss_in, info).
         rev (elliptic system): unknown j lives in column nz-1-j of S, which makes column c zero above row nz-1-c; the
         solves and products skip those zeros (28 % of the flops) and the column shards are cut by work, not by width.
         Dinv (ops.trtri_diag(L)) + S2 (zero-initialised, same shape as S, reused across steps): the column solves run through
-        the inverted diagonal blocks (GEMMs only) out of place into S2, which then takes S's role; S is scratch."""
+        the inverted diagonal blocks (GEMMs only) out of place into S2, which then takes S's role; S is scratch.
+        line_search (an equation's LineSearch, src/linesearch.py): not available here -- the trial losses and the acceptance live in the
+        single-GPU step (gpk_gn_step_ls).  This keyword is the ONLY route to the refusal: no equation class calls the sharded step, so a
+        caller that drives it for an equation with eq.line_search set has to hand the attribute over here (as MultiGpu.gn_step)."""
+        if line_search is not None:
+            raise NotImplementedError('line search: the sharded multi-GPU step takes a fixed step size; run the single-GPU step (gn_step_ls)')
         ops, comm, P, rank, nb = self.ops, self.comm, self.P, self.rank, self.nb
         nc = nz + 1
         if rev:

@@ -274,7 +274,25 @@ class _GPEquation(object):
         # J(z_0) .. J(z_{max_iter-1}) and one gpk_gn_loss closes the history.  Rounds 2-4 took that number from the F column of the
         # GEMM-only solve (~1e-8 relative error at nugget <= 1e-12 near convergence: gpk_tune(52, 0)) and round 4 therefore called
         # gpk_gn_loss after every step; GPK_SEPARATE_LOSS=1 keeps that sequence (same numbers to rounding, one more solve per step).
-        if os.environ.get('GPK_SEPARATE_LOSS', '0') != '1':
+        ls = getattr(self, 'line_search', None)                  # a run-time instance attribute (src/linesearch.py); None: the loop below
+        if ls is not None:
+            # gpk_gn_step_ls: direction, the K trial losses (one K-column solve) and the acceptance on the device, one synchronisation per
+            # step; like gpk_gn_step it returns the loss of the iterate it starts from, so the history keeps the reference's shape
+            t0 = ls.first_step(step_size)
+            self.step_hist, self.trial_loss_hist, self.ls_failed, self.ls_accepted = [], [], [], []
+            for it in range(max_iter):
+                loss_in, info, k, t_acc, trial = ctx.gn_step_ls(prob, z, ls.trials, t0, ls.shrink, ls.c1)
+                record(it, loss_in)
+                self._check_step_info(it + 1, info)
+                self.step_hist.append(t_acc if k >= 0 else 0.0)
+                self.ls_accepted.append(k)
+                self.trial_loss_hist.append(trial)
+                if k < 0:
+                    self.ls_failed.append(it + 1)
+                    print('[Error] line search failed at step', it + 1, ': none of the', ls.trials, 'trial steps from', t0,
+                          'down reduces the loss; the iterate is kept')
+            record(max_iter, ctx.gn_loss(prob, z))
+        elif os.environ.get('GPK_SEPARATE_LOSS', '0') != '1':
             for it in range(max_iter):
                 loss_in, info = ctx.gn_step(prob, z, step_size)   # loss of the iterate the step starts from
                 record(it, loss_in)

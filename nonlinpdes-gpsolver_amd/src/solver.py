@@ -235,10 +235,17 @@ class solver_GP(object):
         eqn.Gram_Cholesky()
         _say(print_option, 'chol', 'gn_start', 'gn_method', method=method)
         gn = dict(max_iter=c.GNsteps, step_size=c.step_size, initial_sol=c.initial_sol, print_hist=c.print_hist)
+        # cfg.line_search (bool or LineSearch; cfg.ls_trials / ls_shrink / ls_c1): the equation object takes it as an instance attribute
+        from .linesearch import from_config
+        ls = from_config(c)
+        if ls is not None:
+            eqn.line_search = ls
         if method == 'elimination':
             eqn.GN_method(**gn)
         elif method == 'relaxation':
             eqn.GN_relaxed_method(pen_lambda=pen_lambda, **gn)
+        if ls is not None and print_option:
+            print('line search: step_hist =', [float(t) for t in eqn.step_hist])
         _say(print_option, 'gn_done')
 
     # ---- model evidence of the kernel parameter (eqn.log_evidence; no counterpart in the reference) ------------------------------------

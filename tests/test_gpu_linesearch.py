@@ -1,0 +1,515 @@
+"""The line search of the Gauss-Newton iteration on the device (gpk_gn_direction, gpk_gn_trial_losses, gpk_gn_trial_accept,
+gpk_gn_step_ls; DESIGN.md section K, "Line search") against tests/_linesearch_reference.py and the long-double references of
+_gn_reference / _nl_reference / _semilinear_reference.
+
+Synthetic, well-conditioned factors with poisoned upper triangles and padding, as in test_gpu_gn_rounding.py; N_d = 65 (straddles
+nothing) and 129 (one past two 64-blocks); every test with and without the inverted diagonal blocks.  The trial-loss gate also runs at N_d = 333.
+
+  1. direction: z bitwise unchanged; delta, info, loss bit-identical to gpk_gn_step(step 0.5) on a second handle; loss through gate_loss;
+     pred against the long-double g . delta / 2 with the rule of every gate of _gn_reference: allowed(r64) = 32 r64 + 1, r64 the same
+     ratio of the float64 pipeline.
+  2. trial losses: every system of SYSTEMS, the semilinear system (gq of _semilinear_reference, eps 0.1) and the elliptic system with
+     GPK_NL_EXP; K in {1, 5, 16}, t from {0, 1, 2, 2^-k} (z - t delta is then one rounding on host and device alike); each column through
+     gate_loss against the long-double loss at z - t_k delta; the t = 0 column against gpk_gn_loss(z) within the same gate; canaries
+     (1e30) in the padding of W and behind dev_losses[K - 1] intact; K = 0 and K = 17 refused with -9001, canaries intact.
+  3. accept: the crafted loss vectors of test_linesearch_host.py uploaded: k as the reference rule, z_out bitwise z - t_k delta, z
+     bitwise untouched for k = -1.
+  4. gpk_gn_step_ls: (a) elliptic 65, defaults: k = 0 and z_out bit-identical to gpk_gn_step(step 1); (b) t0 = 8: k >= 2 and k = the
+     reference rule on the device's own losses, loss_in, pred, after asserting that no loss lies within 16 eps loss_in of its threshold;
+     (c) GPK_NL_EXP with a first trial that overflows exp: non-finite leading losses skipped, z_out finite; (d) gn_measurement(z_out)
+     bitwise the column the build kernel wrote for the accepted k (gpk_debug_gn_trial_build of the development library).
+  5. end to end through Semilinear2d on a Gram factor (N_d 200, N_b 60, nugget 1e-6, eps 0.05, N = u (p + q / 2), five steps): loss
+     history non-increasing, step_hist complete, accepted k of every step = the CPU reference's, final iterate within the 1e-6 parity
+     bound; without the attribute the same object repeats its earlier plain run bit for bit.
+     That equation does not separate the two iterations (eps = 0.02: both stall, 3.84e5 plain, 2.83e5 line-searched), nor does Eikonal
+     at small eps from the zero start (both converge, the line search two steps sooner).  Bratu does: -Delta u + 1e4 exp(u) = f from a
+     standard normal start, 7 steps -- plain Gauss-Newton never gets below its starting loss (9.14e12 -> 2.05e22), the line-searched
+     iteration reaches 3.19: reference ratio 6.4e21, a tenth of it asserted of the device, together with the checks above
+     (test_class_end_to_end_bratu_separates).  DESIGN.md section K, "Line search", has the numbers of all three candidates.
+  6. interfaces: solver_GP with cfg.line_search = True and a driver with --line_search True finish and print step_hist.
+
+RESULTS: each test prints its ratios under [direction], [trial], [step_ls]; worst ratios of a run on an MI355X, as "device of allowed":
+  direction loss 1.06 of 47.2;  direction pred 1.58 of 21.4;  trial 4.41 of 33 at N_d = 65 / 129 and 4.10 of 33 at 333 (numpy figure =
+  (allowed - 1) / 32).  step_ls: no loss closer than 1.8e12 eps loss_in to its threshold, on the device and on the CPU, same k.
+  End to end: Semilinear2d k = 1, 1, 0, 0, 0 on both sides, parity 4.5e-13;  Bratu k = 2, 0, 0, 0, 0, 0, 0 on both sides, parity 9.0e-15,
+  final-loss ratio plain / line-searched 6.43e21 on the device and on the reference (asserted: >= a tenth of the reference's).
+"""
+import ctypes as C
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _gn_reference as R
+import _linesearch_reference as LS
+import _nl_reference as NL
+import _semilinear_reference as SL
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LD, EPS = R.LD, R.EPS
+SIZES = (65, 129)
+ALL_SYSTEMS = R.SYSTEMS + ('semilinear', 'exp')
+DINV = [256, False]
+CANARY = 1e30
+T16 = np.array([0.0, 1.0, 2.0, 0.5, 0.25] + [2.0 ** -k for k in range(3, 14)])
+TRIALS = {1: T16[1:2], 5: T16[:5], 16: T16}
+
+
+@pytest.fixture(scope='module')
+def second_ctx():
+    import gpk
+    c = gpk.Context(0, dev=True)
+    yield c
+    c.close()
+
+
+def _case(system, Nd):
+    if system == 'semilinear':
+        return SL.case(Nd)
+    if system == 'exp':
+        return NL.case('exp', 'elliptic', Nd, R.NB[Nd])
+    return R.case(system, Nd)
+
+
+def _linearise(system, cs, z):
+    return SL.linearise(cs, z) if system == 'semilinear' else NL.linearise(cs, z) if system == 'exp' else R.linearise(cs, z)
+
+
+class _P64:
+    def __init__(self, loss):
+        self.loss = loss
+
+
+class LossRef:
+    """loss and p64.loss as gate_loss reads them: the long-double and the float64 (scipy) substitution loss at z"""
+
+    def __init__(self, system, cs, z):
+        from scipy.linalg import solve_triangular
+        lin = _linearise(system, cs, z)
+        w = R._group_solve(cs, lin.F)
+        self.loss = w @ w
+        w64 = lin.F.astype(np.float64)
+        for off, n, L in cs.groups:
+            if L is not None and n:
+                w64[off:off + n] = solve_triangular(L, w64[off:off + n], lower=True, check_finite=False)
+        self.p64 = _P64(float(w64 @ w64))
+
+    @staticmethod
+    def p64_only(system, cs, z):
+        from scipy.linalg import solve_triangular
+        w64 = _linearise(system, cs, z).F.astype(np.float64)
+        for off, n, L in cs.groups:
+            if L is not None and n:
+                w64[off:off + n] = solve_triangular(L, w64[off:off + n], lower=True, check_finite=False)
+        return float(w64 @ w64)
+
+
+def _loss_ref(system, cs, z):
+    if system == 'semilinear':
+        return LossRef(system, cs, z)
+    if system == 'exp':
+        return NL.VectorReference(cs, z, want_delta=False)
+    return R.VectorReference(cs, z, want_delta=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _direction(system, Nd):
+    """a fixed float64 direction per case: delta of the float64 pipeline at z0 (uploaded; the trial entry takes any delta)"""
+    cs = _case(system, Nd)
+    return R.Pipeline64(cs, cs.z0, _linearise(system, cs, cs.z0)).delta
+
+
+class _Ref:
+    def __init__(self, loss, loss64):
+        self.loss, self.p64 = loss, _P64(loss64)
+
+
+def _batched_refs(system, cs, zs):
+    """what gate_loss reads of a VectorReference -- the long-double loss and the float64 pipeline's -- for several points at once: the
+    measurement vectors as the columns of one long-double substitution (VectorReference also builds H, g and |H| per point, O(N^2 n_z)
+    each, which no loss gate reads; at N_d = 333 that is the whole cost)"""
+    from scipy.linalg import solve_triangular
+    F = np.stack([_linearise(system, cs, z).F for z in zs], axis=1)
+    W = R._group_solve(cs, F)
+    W64 = F.astype(np.float64)
+    for off, n, L in cs.groups:
+        if L is not None and n:
+            W64[off:off + n] = solve_triangular(L, W64[off:off + n], lower=True, check_finite=False)
+    return [_Ref(W[:, k] @ W[:, k], float(W64[:, k] @ W64[:, k])) for k in range(len(zs))]
+
+
+@functools.lru_cache(maxsize=None)
+def _trial_refs(system, Nd):
+    cs, d = _case(system, Nd), _direction(system, Nd)
+    if Nd > 129:
+        return _batched_refs(system, cs, [cs.z0 - t * d for t in T16])
+    return [_loss_ref(system, cs, cs.z0 - t * d) for t in T16]
+
+
+def _loss64(system, cs, z):
+    """the float64 (scipy) substitution loss at z"""
+    with np.errstate(all='ignore'):
+        return LossRef.p64_only(system, cs, z)
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_overshoot(system, Nd, t0, beta, K, c1):
+    """the step of test 4(b) on the CPU in float64: (loss_in, pred, trial losses, k, distance of the nearest loss to its threshold in
+    units of eps loss_in)"""
+    cs = _case(system, Nd)
+    p = R.Pipeline64(cs, cs.z0, _linearise(system, cs, cs.z0))
+    pred = 0.5 * float(p.g @ p.delta)
+    t = LS.steps(t0, beta, K)
+    trial = np.array([_loss64(system, cs, cs.z0 - tk * p.delta) for tk in t])
+    thr = LS.thresholds(t, p.loss, pred, c1)
+    fin = np.isfinite(trial)
+    return p.loss, pred, trial, LS.accept(trial, t, p.loss, pred, c1), float(np.min(np.abs(trial[fin] - thr[fin])) / (EPS * p.loss))
+
+
+def _upload_factor(ctx, L):
+    n = L.shape[0]
+    d = ctx.empty(n, n + R.LD_PAD, ld=n + R.LD_PAD)
+    d.upload(R.poisoned(L))
+    d.cols = n
+    return d
+
+
+def _problem(ctx, system, cs, dinv):
+    import gpk
+    L = _upload_factor(ctx, cs.L)
+    keep = [L]
+    if system == 'semilinear':
+        prob = gpk.GNProblem(ctx, 'Semilinear2d', cs.Nd, cs.Nb, cs.f, cs.g, L, p0=cs.eps, dinv=dinv, gq=cs.gq)
+    elif system == 'exp':
+        prob = gpk.GNProblem(ctx, 'Nonlinear_elliptic', cs.Nd, cs.Nb, cs.f, cs.g, L, p0=cs.p0, p1=cs.p1, p2=cs.p2, nonlin=cs.nonlin, dinv=dinv)
+    else:
+        L2 = _upload_factor(ctx, cs.L2) if cs.L2 is not None else None
+        keep += [L2] if L2 is not None else []
+        prob = gpk.GNProblem(ctx, R.SYSTEM_NAME[system], cs.Nd, cs.Nb, cs.f, cs.g, L, p0=cs.p0, p1=cs.p1, pen_lambda=cs.lam, data_u=cs.data,
+                             L2=L2, dinv=dinv, cache_a=False)
+    prob.keep += keep
+    return prob
+
+
+def _pd(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# ------------------------------------------------------------------------------------------------ 1. direction
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+@pytest.mark.parametrize('Nd', SIZES)
+@pytest.mark.parametrize('system', R.SYSTEMS)
+def test_direction(dev_ctx, second_ctx, system, Nd, dinv):
+    """[direction] worst ratios of a run on an MI355X: loss 1.06 of 47.2, pred 1.58 of 21.4 (module docstring)"""
+    ctx, cs = dev_ctx, R.case(system, Nd)
+    ref = R.vector_reference(system, Nd)
+    prob = _problem(ctx, system, cs, dinv)
+    z = ctx.array(cs.z0)
+    loss, pred, info = ctx.gn_direction(prob, z)
+    delta = prob.workspace()[2].download().copy()
+    assert np.array_equal(z.download(), cs.z0), 'gpk_gn_direction wrote z'
+    prob2 = _problem(second_ctx, system, cs, dinv)
+    z2 = second_ctx.array(cs.z0)
+    loss2, info2 = second_ctx.gn_step(prob2, z2, 0.5)
+    delta2 = prob2.workspace()[2].download().copy()
+    prob.free(); prob2.free()
+    assert info == info2 == 0 and np.array_equal(delta, delta2) and loss == loss2
+    rl, al = R.gate_loss(ref, loss)
+    want = (ref.g @ ref.delta) / LD(2)
+    ratio = lambda v: float(abs(LD(v) - want) / (LD(EPS) * want))
+    rp, ap = ratio(pred), R.allowed(ratio(0.5 * float(ref.p64.g @ ref.p64.delta)))
+    print(f'\n[direction] {system} {Nd} dinv={dinv}: loss {rl:.3g} of {al:.3g}; pred {rp:.3g} of {ap:.3g} (numpy {(ap - 1) / R.MARGIN:.3g})')
+    assert rl <= al and rp <= ap
+
+
+# ------------------------------------------------------------------------------------------------ 2. trial losses
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+@pytest.mark.parametrize('Nd', SIZES + (333,))
+@pytest.mark.parametrize('system', ALL_SYSTEMS)
+def test_trial_losses(dev_ctx, system, Nd, dinv):
+    ctx, cs = dev_ctx, _case(system, Nd)
+    refs = _trial_refs(system, Nd)
+    prob = _problem(ctx, system, cs, dinv)
+    z, delta = ctx.array(cs.z0), ctx.array(_direction(system, Nd))
+    loss_z = ctx.gn_loss(prob, z)
+    ldw, nbytes = C.c_int(), C.c_size_t()
+    bad = []
+    print()
+    for K, t in TRIALS.items():
+        assert ctx.lib.gpk_gn_trial_worksize(C.byref(prob.struct), K, 0, C.byref(ldw), C.byref(nbytes)) == 0
+        assert ldw.value == 16 and nbytes.value >= prob.rows * 16 * 8
+        n = nbytes.value // 8
+        W, dl = ctx.empty(n), ctx.empty(24)
+        W.upload(np.full(n, CANARY)); dl.upload(np.full(24, CANARY))
+        for badK in (0, 17):
+            tt = np.ones(17)
+            rc = ctx.lib.gpk_gn_trial_losses(ctx.h, C.byref(prob.struct), z.ptr, delta.ptr, _pd(tt), badK, W.ptr, ldw.value, dl.ptr, None)
+            assert rc == -9001 and b'K' in ctx.lib.gpk_last_error(ctx.h)
+        ctx.synchronize()
+        assert np.all(W.download() == CANARY) and np.all(dl.download() == CANARY), 'a refused call wrote something'
+        t = np.ascontiguousarray(t)
+        host = np.empty(K)
+        ctx._chk(ctx.lib.gpk_gn_trial_losses(ctx.h, C.byref(prob.struct), z.ptr, delta.ptr, _pd(t), K, W.ptr, ldw.value, dl.ptr, _pd(host)))
+        got = dl.download()
+        assert np.array_equal(got[:K], host) and np.all(got[K:] == CANARY), 'dev_losses: K doubles and nothing behind them'
+        Wh = W.download()
+        nbuf = 2 if dinv else 1                                      # B, and the out-of-place X of the GEMM-only solve
+        for b in range(nbuf):
+            blk = Wh[b * prob.rows * 16:(b + 1) * prob.rows * 16].reshape(prob.rows, 16)
+            assert np.all(blk[:, K:] == CANARY), 'the padding of W beyond K columns was written'
+            assert np.all(np.isfinite(blk[:, :K]))
+        assert np.array_equal(z.download(), cs.z0)
+        for k in range(K):
+            ref = refs[int(np.nonzero(T16 == t[k])[0][0])]
+            r, a = R.gate_loss(ref, host[k])
+            print(f'[trial] {system} {Nd} dinv={dinv} K={K} t={t[k]:g}: {r:.3g} of {a:.3g}')
+            if not r <= a:
+                bad.append((K, t[k], r, a))
+            if t[k] == 0.0:
+                r0, a0 = R.gate_loss(ref, loss_z)
+                assert r0 <= a0 and r <= a, 't = 0 column and gpk_gn_loss(z) within the same gate'
+        W.free(); dl.free()
+    prob.free()
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ 3. accept
+def test_accept(dev_ctx):
+    from test_linesearch_host import ACCEPT_CASES
+    ctx = dev_ctx
+    rng = np.random.RandomState(5)
+    for nz in (65, 300):
+        z0, d = rng.normal(size=nz), rng.normal(size=nz)
+        delta = ctx.array(d)
+        for name, (losses, t, loss_in, pred, c1, want) in ACCEPT_CASES.items():
+            losses, t = np.array(losses, dtype=float), np.array(t, dtype=float)
+            assert LS.accept(losses, t, loss_in, pred, c1) == want
+            z, dl = ctx.array(z0), ctx.array(np.concatenate([losses, np.full(3, -CANARY)]))
+            k, ta = C.c_int(7), C.c_double(7.0)
+            ctx._chk(ctx.lib.gpk_gn_trial_accept(ctx.h, nz, z.ptr, delta.ptr, dl.ptr, _pd(t), t.size, loss_in, pred, c1, C.byref(k), C.byref(ta)))
+            assert k.value == want, (name, k.value, want)
+            if want < 0:
+                assert ta.value == 0.0 and np.array_equal(z.download(), z0), name
+            else:
+                assert ta.value == t[want] and np.array_equal(z.download(), z0 - t[want] * d), name
+            z.free(); dl.free()
+        for badK in (0, 17):
+            z = ctx.array(z0)
+            rc = ctx.lib.gpk_gn_trial_accept(ctx.h, nz, z.ptr, delta.ptr, delta.ptr, _pd(np.ones(17)), badK, 1.0, 1.0, 1e-4, None, None)
+            assert rc == -9001 and np.array_equal(z.download(), z0)
+        delta.free()
+
+
+# ------------------------------------------------------------------------------------------------ 4. gpk_gn_step_ls
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+def test_step_ls_full_step_is_gn_step(dev_ctx, dinv):
+    ctx, cs = dev_ctx, R.case('elliptic', 65)
+    prob = _problem(ctx, 'elliptic', cs, dinv)
+    z, z1 = ctx.array(cs.z0), ctx.array(cs.z0)
+    loss, info, k, t, trial = ctx.gn_step_ls(prob, z)
+    d_ls = prob.workspace()[2].download().copy()
+    loss1, info1 = ctx.gn_step(prob, z1, 1.0)
+    assert (k, t, info, info1) == (0, 1.0, 0, 0) and loss == loss1 and trial.shape == (8,)
+    assert np.array_equal(d_ls, prob.workspace()[2].download())
+    assert np.array_equal(z.download(), z1.download()), 'the accepted full step is not the step of gpk_gn_step(step_size = 1)'
+    after = ctx.gn_loss(prob, z)
+    r, a = R.gate_loss(R.VectorReference(cs, z.download(), want_delta=False), trial[0])
+    print(f'\n[step_ls] elliptic 65 dinv={dinv}: accepted loss {trial[0]:.17g}, gpk_gn_loss(z_out) {after:.17g}; gate {r:.3g} of {a:.3g}')
+    prob.free()
+    assert r <= a
+
+
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+@pytest.mark.parametrize('Nd', SIZES)
+@pytest.mark.parametrize('system', ALL_SYSTEMS)
+def test_step_ls_overshoot_and_measured_point(dev_ctx, system, Nd, dinv):
+    """t0 = 8: the model rules out t > 2, so k >= 2; k = the reference rule on the device's own numbers; gn_measurement(z_out) is
+    bitwise the column the build kernel wrote for the accepted k"""
+    ctx, cs = dev_ctx, _case(system, Nd)
+    prob = _problem(ctx, system, cs, dinv)
+    z = ctx.array(cs.z0)
+    loss_d, pred, info_d = ctx.gn_direction(prob, z)
+    loss, info, k, t_acc, trial = ctx.gn_step_ls(prob, z, trials=8, t0=8.0, shrink=0.5, c1=1e-4)
+    t = LS.steps(8.0, 0.5, 8)
+    thr = LS.thresholds(t, loss, pred, 1e-4)
+    fin = np.isfinite(trial)
+    margin = np.min(np.abs(trial[fin] - thr[fin])) / (EPS * loss)
+    print(f'\n[step_ls] {system} {Nd} dinv={dinv}: k = {k}, t = {t_acc}, loss_in {loss:.6g}, pred {pred:.6g}, losses {trial}, '
+          f'nearest threshold at {margin:.3g} eps loss_in')
+    assert margin > 16, 'a loss lies within 16 eps loss_in of its threshold: choose another case (a condition, not a tolerance)'
+    # the same step on the CPU (float64 pipeline): the case was chosen there -- no loss near its threshold -- and gives the same index
+    _, _, trial_cpu, k_cpu, margin_cpu = _cpu_overshoot(system, Nd, 8.0, 0.5, 8, 1e-4)
+    print(f'[step_ls] CPU: k = {k_cpu}, losses {trial_cpu}, nearest threshold at {margin_cpu:.3g} eps loss_in')
+    assert margin_cpu > 16 and k == k_cpu
+    assert loss == loss_d and info == info_d == 0
+    assert k == LS.accept(trial, t, loss, pred, 1e-4) and t_acc == t[k]
+    # J + (t^2 - 2 t) pred > J for t > 2 is a statement about the LINEARISED loss; it carries over to the true loss of the elliptic case
+    # (the issue's case), where it is asserted.  For the other systems the true loss at t = 8, 4 is not bound by the model, so their index
+    # is held against the CPU's (above) instead of against 2.
+    if system == 'elliptic':
+        assert k >= 2 and k_cpu >= 2
+    z_out = z.download()
+    delta = prob.workspace()[2]
+    assert np.array_equal(z_out, cs.z0 - t[k] * delta.download())
+    W = ctx.empty(prob.rows, 8, ld=8)
+    zin = ctx.array(cs.z0)
+    ctx._chk(ctx.lib.gpk_debug_gn_trial_build(ctx.h, C.byref(prob.struct), zin.ptr, delta.ptr, _pd(t), 8, W.ptr, 8))
+    built = W.download()
+    assert np.array_equal(built[:, k], ctx.gn_measurement(prob, z)), 'the accepted iterate is not the point whose loss was measured'
+    prob.free()
+
+
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+@pytest.mark.parametrize('system', ALL_SYSTEMS)
+def test_accepted_point_is_measured_point_for_general_steps(dev_ctx, system, dinv):
+    """t_k = 7 x 0.3^k: t_k delta is not exact, so z + (-t_k) delta depends on whether the product and the sum are fused.  The trial
+    reader, the accepting update and gpk_axpy must agree on that: device output against device output, bit for bit."""
+    ctx, cs = dev_ctx, _case(system, 65)
+    prob = _problem(ctx, system, cs, dinv)
+    z, zin, zax = ctx.array(cs.z0), ctx.array(cs.z0), ctx.array(cs.z0)
+    loss, info, k, t_acc, trial = ctx.gn_step_ls(prob, z, trials=8, t0=7.0, shrink=0.3, c1=1e-4)
+    t = LS.steps(7.0, 0.3, 8)
+    print(f'\n[step_ls] {system} 65 dinv={dinv} general steps: k = {k}, t = {t_acc}, losses {trial}')
+    assert info == 0 and k >= 0 and t_acc == t[k] and k == LS.accept(trial, t, loss, ctx.gn_direction(prob, zin)[1], 1e-4)
+    delta = prob.workspace()[2]
+    W = ctx.empty(prob.rows, 8, ld=8)
+    ctx._chk(ctx.lib.gpk_debug_gn_trial_build(ctx.h, C.byref(prob.struct), zin.ptr, delta.ptr, _pd(t), 8, W.ptr, 8))
+    assert np.array_equal(W.download()[:, k], ctx.gn_measurement(prob, z)), 'the accepted iterate is not the point whose loss was measured'
+    ctx._chk(ctx.lib.gpk_axpy(ctx.h, prob.nz, -t[k], delta.ptr, zax.ptr))
+    assert np.array_equal(zax.download(), z.download()), 'the accepting update and gpk_axpy round differently'
+    prob.free()
+
+
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+def test_step_ls_skips_overflowing_trials(dev_ctx, dinv):
+    """GPK_NL_EXP, tau = p0 exp(p1 u): t0 = 2^14 sends some u_i beyond exp's range, the leading losses are not finite and are skipped"""
+    ctx, cs = dev_ctx, _case('exp', 65)
+    prob = _problem(ctx, 'exp', cs, dinv)
+    z = ctx.array(cs.z0)
+    _, pred, _ = ctx.gn_direction(prob, z)
+    d = prob.workspace()[2].download()
+    assert np.max(cs.p1 * (cs.z0 - 2.0 ** 14 * d)) > 710.0, 'the first trial does not overflow exp: choose a larger t0'
+    loss, info, k, t_acc, trial = ctx.gn_step_ls(prob, z, trials=16, t0=2.0 ** 14, shrink=0.5, c1=1e-4)
+    t = LS.steps(2.0 ** 14, 0.5, 16)
+    print(f'\n[step_ls] exp 65 dinv={dinv}: k = {k}, losses {trial}')
+    assert info == 0 and not np.isfinite(trial[0]) and k >= 1 and np.isfinite(trial[k])
+    assert k == LS.accept(trial, t, loss, pred, 1e-4)
+    assert np.all(np.isfinite(z.download())) and np.array_equal(z.download(), cs.z0 - t[k] * d)
+    prob.free()
+
+
+# ------------------------------------------------------------------------------------------------ 5. end to end through the class
+GQ_E2E, EPS_E2E, STEPS_E2E = (1.0, 0.5, 0.0, 0.0, 0.0), 0.05, 5
+
+
+def test_class_end_to_end():
+    from oracle import gp_oracle as O
+    from src.PDEs import Semilinear2d
+    from src.linesearch import LineSearch
+    Nd, Nb, nugget = 200, 60, 1e-6
+    Xd, Xb = SL.points(Nd, Nb)
+    e = Semilinear2d(eps=EPS_E2E, nonlinearity=GQ_E2E, bdy=SL.truth, rhs=lambda x1, x2: SL.manufactured_rhs(EPS_E2E, GQ_E2E, x1, x2))
+    e.get_sampled_points(Xd, Xb)
+    e.Gram_matrix(kernel='Gaussian', kernel_parameter=0.2, nugget=nugget, nugget_type='adaptive')
+    e.Gram_Cholesky()
+    e.GN_method(max_iter=STEPS_E2E, step_size=1, initial_sol='zero', print_hist=False)
+    plain_z, plain_hist = e._z_star[1].copy(), list(e.loss_hist)
+    assert not hasattr(e, 'step_hist')
+    T, _ = O.add_nugget(O.gram_matrix_assembly(Xd, Xb, 'Eikonal', 'Gaussian', 0.2), 'Eikonal', Nd, Nb, nugget)
+    L = O.cholesky(T)
+    sysm = SL.System(EPS_E2E, GQ_E2E, e.rhs_f, e.bdy_g)
+    ref = LS.ls_iterate(sysm, [L], np.zeros(3 * Nd), STEPS_E2E)
+    e.line_search = LineSearch()
+    e.GN_method(max_iter=STEPS_E2E, step_size=1, initial_sol='zero', print_hist=False)
+    z = e._z_star[1]
+    rel = float(np.linalg.norm(z - ref['z']) / np.linalg.norm(ref['z']))
+    print(f'\n[e2e] k device {e.ls_accepted} reference {ref["k"]}; loss device {e.loss_hist} reference {ref["loss_hist"]}; plain {plain_hist}; '
+          f'parity {rel:.3g}')
+    assert len(e.step_hist) == STEPS_E2E and len(e.trial_loss_hist) == STEPS_E2E and len(e.loss_hist) == STEPS_E2E + 1
+    failed = set(e.ls_failed)
+    assert all(b <= a for i, (a, b) in enumerate(zip(e.loss_hist, e.loss_hist[1:])) if i + 1 not in failed)
+    assert e.ls_accepted == ref['k'] and e.step_hist == ref['step_hist']
+    assert rel <= 1e-6
+    e.line_search = None
+    e.GN_method(max_iter=STEPS_E2E, step_size=1, initial_sol='zero', print_hist=False)
+    assert np.array_equal(e._z_star[1], plain_z) and e.loss_hist == plain_hist, 'the plain loop changed after the attribute had been set'
+
+
+BRATU_P0, BRATU_STEPS = 1e4, 7
+
+
+def test_class_end_to_end_bratu_separates():
+    """-Delta u + 1e4 exp(u) = f (u* = sin pi x1 sin pi x2) from a standard normal start -- the 'rdm' start, drawn once with
+    RandomState(0) and handed to both sides -- 200 + 60 points, Gaussian sigma 0.2, nugget 1e-6, 7 steps.  On the CPU reference plain
+    Gauss-Newton does not reduce the loss (9.14e12 -> 3.34e27 -> ... -> 2.05e22 after 7 steps, still 5.08e19 after 10) and the
+    line-searched iteration does (k = 2, 0, 0, 0, 0, 0, 0: 9.14e12 -> 9.02e12 -> 7.70e11 -> 5.02e10 -> 1.62e9 -> 7.01e6 -> 225 -> 3.19):
+    REFERENCE RATIO plain / line-searched final loss = 6.4e21; the device has to show a tenth of it."""
+    from oracle import gp_oracle as O
+    from src.PDEs import Nonlinear_elliptic2d
+    from src.linesearch import LineSearch
+    Nd, Nb, nugget, p0 = 200, 60, 1e-6, BRATU_P0
+    Xd, Xb = SL.points(Nd, Nb)
+    rhs = lambda x1, x2: 2 * np.pi ** 2 * SL.truth(x1, x2) + p0 * np.exp(SL.truth(x1, x2))
+    z0 = np.random.RandomState(0).normal(size=Nd)
+    e = Nonlinear_elliptic2d(bdy=SL.truth, rhs=rhs, nonlinearity=('exp', p0, 1.0))
+    e.get_sampled_points(Xd, Xb)
+    e.Gram_matrix(kernel='Gaussian', kernel_parameter=0.2, nugget=nugget, nugget_type='adaptive')
+    e.Gram_Cholesky()
+    e.GN_method(max_iter=BRATU_STEPS, step_size=1, initial_sol=z0.copy(), print_hist=False)
+    plain_z, plain_hist = e._z_star[1].copy(), list(e.loss_hist)
+    T, _ = O.add_nugget(O.gram_matrix_assembly(Xd, Xb, 'Nonlinear_elliptic', 'Gaussian', 0.2), 'Nonlinear_elliptic', Nd, Nb, nugget)
+    L = O.cholesky(T)
+    sysm = LS.ReactionSystem(lambda u: p0 * np.exp(u), lambda u: p0 * np.exp(u), e.rhs_f, e.bdy_g)
+    _, ref_plain = LS.plain_iterate(sysm, [L], z0, BRATU_STEPS)
+    ref = LS.ls_iterate(sysm, [L], z0, BRATU_STEPS)
+    ratio_ref = ref_plain[-1] / ref['loss_hist'][-1]
+    e.line_search = LineSearch()
+    e.GN_method(max_iter=BRATU_STEPS, step_size=1, initial_sol=z0.copy(), print_hist=False)
+    z = e._z_star[1]
+    rel = float(np.linalg.norm(z - ref['z']) / np.linalg.norm(ref['z']))
+    ratio = plain_hist[-1] / e.loss_hist[-1]
+    print(f'\n[e2e bratu] k device {e.ls_accepted} reference {ref["k"]}\n  loss device {e.loss_hist}\n  reference {ref["loss_hist"]}\n'
+          f'  plain device {plain_hist}\n  plain reference {list(ref_plain)}\n  parity {rel:.3g}; final-loss ratio device {ratio:.3g}, '
+          f'reference {ratio_ref:.3g}')
+    assert not ref_plain[-1] < ref_plain[0] and ref['loss_hist'][-1] < 1e-6 * ref['loss_hist'][0], 'the case no longer separates on the CPU'
+    failed = set(e.ls_failed)
+    assert all(b <= a for i, (a, b) in enumerate(zip(e.loss_hist, e.loss_hist[1:])) if i + 1 not in failed)
+    assert len(e.step_hist) == BRATU_STEPS
+    assert e.ls_accepted == ref['k'] and e.step_hist == ref['step_hist']
+    assert rel <= 1e-6
+    assert ratio >= ratio_ref / 10
+    del e.line_search
+    e.GN_method(max_iter=BRATU_STEPS, step_size=1, initial_sol=z0.copy(), print_hist=False)
+    assert np.array_equal(e._z_star[1], plain_z) and e.loss_hist == plain_hist
+
+
+# ------------------------------------------------------------------------------------------------ 6. interfaces
+def test_solver_gp_takes_cfg_line_search(capsys):
+    import types
+    from src.solver import solver_GP
+    eps, gq = 0.2, (1.0, 1.0, 0.0, 0.0, 0.0)
+    cfg = types.SimpleNamespace(eps=eps, nonlinearity=gq, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-6, nugget_type='adaptive',
+                                GNsteps=3, step_size=1, initial_sol='zero', print_hist=False, line_search=True, ls_trials=4, ls_shrink=0.5,
+                                ls_c1=1e-4)
+    from src.PDEs import Semilinear2d
+    from src.linesearch import from_config
+    s = solver_GP(cfg, PDE_type='Semilinear2d')
+    s.eqn = Semilinear2d(eps=eps, nonlinearity=gq, bdy=SL.truth, rhs=lambda x1, x2: SL.manufactured_rhs(eps, gq, x1, x2))
+    s.eqn.get_sampled_points(*SL.points(150, 40))
+    s.solve()
+    out = capsys.readouterr().out
+    assert 'step_hist' in out and len(s.eqn.step_hist) == 3 and s.eqn.line_search.trials == 4 and from_config(cfg).trials == 4
+
+
+def test_driver_takes_line_search_flag():
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, 'nonlinpdes-gpsolver_amd')]))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'nonlinpdes-gpsolver_amd', 'main_Semilinear2d.py'), '--N_domain', '150',
+                        '--N_boundary', '40', '--GNsteps', '3', '--show_figure', '', '--line_search', 'True', '--ls_trials', '4'],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=os.path.join(ROOT, 'nonlinpdes-gpsolver_amd'))
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert 'step_hist' in p.stdout
