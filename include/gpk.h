@@ -43,7 +43,16 @@ enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 
 /* nugget_type of src/PDEs.py:56,250,391 / src/InverseProblems.py:66 */
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
-enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5 };
+enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5, GPK_GN_MONGE_AMPERE = 6 };
+/* GPK_GN_MONGE_AMPERE (no counterpart in the reference; DESIGN.md section K, "Fully nonlinear: Monge-Ampere"):
+ *   det D^2 u = f, f > 0, convex branch, in the form  Delta u = sqrt((D u)^2 + (M u)^2 + 4 f),  D = d_11 - d_22,  M = 2 d_12
+ * ((Delta u)^2 = (D u)^2 + (M u)^2 + 4 det D^2 u), on the rows of gpk_assemble_hess ([D u; M u; Delta u; u] per domain point, then the
+ * boundary values), unknowns z = [v0 = u | v1 = D u | v2 = M u]:
+ *   F(z) = [v1; v2; s; v0; g],  s = sqrt(v1^2 + v2^2 + 4 f),   A(z): 1 at (t, v1_t), (N_d + t, v2_t), (3 N_d + t, v0_t) and
+ *   v1 / s, v2 / s at (2 N_d + t, v1_t / v2_t) -- the sparsity pattern of GPK_GN_EIKONAL, N = 4 N_d + N_b, n_z = 3 N_d.
+ * gpk_gn_problem: rhs_f = f; p0, p1 are not read; nonlin must be 0 (-9001).  Where the radicand is negative s is NaN, and it
+ * propagates through the step like every other NaN (loss and delta NaN): nothing on the device tests for it.
+ * gpk_gn_structured_prepare and gpk_gn_gram_prepare refuse the system (-9001); gpk_posterior_prepare and gpk_log_evidence serve it. */
 /* GPK_GN_SEMILINEAR (no counterpart in the reference; DESIGN.md section K, "Gradient-dependent nonlinearity"):
  *   -eps Delta u + N(u, grad u) = f,   N(u, p, q) = u (a1 p + a2 q) + b (p^2 + q^2) + c1 u + c3 u^3,   p = d_1 u, q = d_2 u,
  * on the rows of GPK_LAYOUT_EIKONAL ([d_1 u; d_2 u; Delta u; u] per domain point, then the boundary values), unknowns z = [v0 = u | v1 = p | v2 = q]:
@@ -92,7 +101,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -145,6 +154,10 @@ int gpk_pde_residual_nl(gpk_handle h, int nonlin, const double* host_params3, in
  * One fixed order of operations: a repeated call gives bit-identical output.  eps 0 or not finite, NULL pointers, Nt <= 0, ldf < Nt: -9001. */
 int gpk_pde_residual_sl(gpk_handle h, double eps, const double* host_gq5, int Nt,
                         const double* fields, int ldf, const double* rhs, double* out);
+/* The same for the Monge-Ampere equation: out[t] = d11 d22 - d12^2 - f, rows 0..2 of fields (ld ldf >= Nt) = d11, d12, d22 of the
+ * extension (gpk_extend_functionals_hess).  One fixed order of operations ((d11 * d22 - d12 * d12) - f, no contraction): a repeated call
+ * gives bit-identical output.  NULL pointers, Nt <= 0, ldf < Nt: -9001. */
+int gpk_pde_residual_ma(gpk_handle h, int Nt, const double* fields, int ldf, const double* rhs, double* out);
 /* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
  *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
  *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
@@ -217,6 +230,26 @@ int gpk_assemble_op(gpk_handle h, int kernel, const double* host_kparams, const 
 int gpk_extend_functionals_op(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                               const double* Xd, int Nd, const double* Xb, int Nb, const double* op, const double* bc,
                               const double* coeff, int fmask, double* out, int ldo);
+/* ---- Hessian layout: the second derivatives of u at the domain points as separate row blocks ("Fully nonlinear:
+ *      Monge-Ampere").  No reference call site.  With D = d_11 - d_22, M = 2 d_12: block 0 = D, block 1 = M, block 2 = Laplacian, each
+ *      on the Nd domain points; block 3 = delta on the Nd+Nb domain and boundary points.  N = 4Nd+Nb, Theta N x N, ld >= N: gpk_potrf,
+ *      gpk_potrs and the GPK_GN_MONGE_AMPERE system apply to it.  Kernels: Gaussian and anisotropic Gaussian (Matern ids: -9001).
+ *      host_kparams, Xd, Xb as gpk_assemble.  Nugget as gpk_assemble's for GPK_LAYOUT_EIKONAL: adaptive = nugget * trace ratio on each
+ *      derivative block, nugget on block 3.  host_ratios3 (three doubles, may be NULL) = trace(block k) / trace(block 3), k = 0, 1, 2,
+ *      with the values at d = 0
+ *        <D,D> = 3 p1^2 - 2 p1 p2 + 3 p2^2,   <M,M> = 4 p1 p2,   <Lap,Lap> = 3 p1^2 + 2 p1 p2 + 3 p2^2,   <delta,delta> = 1,
+ *      written for every nugget type.  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte
+ *      stores otherwise, with the same values; nothing outside the N x N view is written); the launch is timed like gpk_assemble's
+ *      when the per-phase timing is on (gpk_prof_read_assembly).  Bad arguments: -9001, named in gpk_last_error. */
+int gpk_assemble_hess(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                      double nugget, int nugget_type, double* Theta, int ld, double* host_ratios3);
+/* The six monomial derivatives of the extension on the Hessian layout at test points Xt (Nt,2), matrix-free: coeff (4Nd+Nb) =
+ * Theta^{-1} sol_vec with the Theta of gpk_assemble_hess.  fmask: a non-empty subset of the GPK_OPFN_* bits (anything else: -9001); out
+ * is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.  Fixed
+ * reduction order: a repeated call gives bit-identical output, and a row has the same bits whichever other rows are requested. */
+int gpk_extend_functionals_hess(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                                const double* Xd, int Nd, const double* Xb, int Nb,
+                                const double* coeff, int fmask, double* out, int ldo);
 /* ---- Operator and boundary functionals in three dimensions ("Operator and boundary functionals in three dimensions"):
  *      -psi[u] + alpha u^m = f on a box in R^3 with psi_i = c0 delta + sum_k b_k d_k + sum_{k<=l} a_kl d_k d_l at domain point i -- 3-D
  *      advection-diffusion-reaction, and with axis 3 as time psi = nu (d_1 d_1 + d_2 d_2) - d_3: u_t - nu Laplace_x u + alpha u^m = f in two
@@ -319,7 +352,7 @@ int gpk_syrk(gpk_handle h, int n, int k, double alpha, const double* A, int lda,
 typedef struct {
     int system;              /* GPK_GN_* */
     int Nd, Nb, Ndata;
-    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, - */
+    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, -   MONGE_AMPERE: -, - */
     double pen_lambda;       /* ELLIPTIC_RELAXED only */
     const double* rhs_f;     /* (Nd,)  */
     const double* bdy_g;     /* (Nb,)  */

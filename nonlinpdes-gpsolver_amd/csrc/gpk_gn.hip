@@ -28,6 +28,7 @@ int gn_dims(const gpk_gn_problem* p, Dims& d) {
         case GPK_GN_BURGERS:
         case GPK_GN_EIKONAL:
         case GPK_GN_SEMILINEAR:
+        case GPK_GN_MONGE_AMPERE:
             d.nz = 3 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 4 * Nd + Nb, 0, p->Dinv}; d.rows = 4 * Nd + Nb; break;
         case GPK_GN_DARCY:
             if (p->Ndata < 0 || p->Ndata > Nd) return GPK_ERR_ARG;
@@ -207,6 +208,17 @@ __device__ __forceinline__ void gn_build_rows(const BuildArgs& a, const int t, c
             putF(a, 2 * Nd + t, (sl_N(a.gq, v0, v1, v2) - a.f[t]) / eps);
             putF(a, 3 * Nd + t, v0);
         } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
+    } else if (a.system == GPK_GN_MONGE_AMPERE) {           // gpk.h, GPK_GN_MONGE_AMPERE: rows [D u; M u; Delta u; u], PDE row s = sqrt(v1^2 + v2^2 + 4 f)
+        if (t < Nd) {
+            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t];
+            const double s = sqrt(v1 * v1 + v2 * v2 + 4.0 * a.f[t]);   // (a negative radicand gives NaN, which the step carries like any other)
+            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0);
+            putA(a, 2 * Nd + t, Nd + t, v1 / s); putA(a, 2 * Nd + t, 2 * Nd + t, v2 / s);
+            putA(a, 3 * Nd + t, t, 1.0);
+            putF(a, t, v1); putF(a, Nd + t, v2);
+            putF(a, 2 * Nd + t, s);
+            putF(a, 3 * Nd + t, v0);
+        } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
     } else if (a.system == GPK_GN_DARCY) {                  // src/InverseProblems.py:106-117 (F), :127-143 (A)
         const double gam = a.p0;                            // noise_level
         const int U = 3 * Nd, D = 7 * Nd + Nb;
@@ -352,6 +364,7 @@ int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
         if (p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR takes nonlin = 0 only (its nonlinearity is gq_a1 .. gq_c3)");
         if (!(std::isfinite(p->p0) && p->p0 != 0.0)) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR needs a finite eps (p0) other than 0");
     }
+    if (p->system == GPK_GN_MONGE_AMPERE && p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_MONGE_AMPERE takes nonlin = 0 only");
     if (p->nonlin != GPK_NL_POWER && p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_ELLIPTIC_RELAXED)
         return gpk_bad_arg(h, "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED");
     return 0;
@@ -443,7 +456,7 @@ int exact_loss_chain(gpk_handle h, const Dims& d, bool after_main, bool* on_side
 int step_layout(gpk_handle h, const gpk_gn_problem* p) {
     const bool darcy_lz = p->system == GPK_GN_DARCY && h->tune.eikonal_lz && h->tune.use_dinv && p->Dinv && p->Dinv2 && p->dinv_block > 0;
     return (p->system == GPK_GN_ELLIPTIC || p->system == GPK_GN_ELLIPTIC_RELAXED) ? 1
-         : ((p->system == GPK_GN_EIKONAL || p->system == GPK_GN_SEMILINEAR) && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
+         : ((p->system == GPK_GN_EIKONAL || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE) && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
 }
 
 // The leading-zero profile of [A(z) | F] under that layout, a pure function of the problem and the handle's switches: the closed form
@@ -453,8 +466,9 @@ int step_layout(gpk_handle h, const gpk_gn_problem* p) {
 // The semilinear system shares Eikonal's layout 2 but NEVER its two-segment profile: its v0 columns carry N_u / eps in row 2 N_d + t, N_d
 // rows above Eikonal's first entry, which the second segment would skip -- dropping dN/du from H with no other symptom.  Its exact
 // profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row 2 N_d + t = n_z - 1 - c).
+// The Monge-Ampere system has exactly Eikonal's pattern (v0 does not enter its PDE row) and takes the two-segment profile.
 GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
-    if (rev == 2 && p->system == GPK_GN_EIKONAL && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
+    if (rev == 2 && (p->system == GPK_GN_EIKONAL || p->system == GPK_GN_MONGE_AMPERE) && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
     return (rev >= 1 && rev <= 3) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
@@ -726,7 +740,7 @@ enum class StepProduct { None, SyrkPotrf, Darcy };
 // No side effects.  A mode is chosen only when everything it reads has been prepared; an incomplete preparation falls through to the
 // next line and in the end to Plain.  (The elliptic system has layout 1, and its relaxed form is a system of its own: always Plain.)
 StepMode select_mode(gpk_handle h, const gpk_gn_problem* p, const Dims& d, int rev) {
-    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR) return StepMode::Plain;   // (the semilinear system has no structured form yet)
+    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE) return StepMode::Plain;   // (no structured form yet)
     const bool ops = p->W1 && p->W2 && p->ldw >= d.nz + 1;           // gpk_gn_structured_prepare
     const bool gram = p->G && p->ldg >= d.nz;                        // gpk_gn_gram_prepare
     if (p->system == GPK_GN_ELLIPTIC && ops && p->v0) return gram && p->pvec ? StepMode::GramElliptic : StepMode::StructuredElliptic;
@@ -890,6 +904,7 @@ extern "C" int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* p, 
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
     if (p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "structured solve: not for the relaxed system");
     if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR is not served (its PDE row has three z-dependent entries per point)");
+    if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "structured solve: GPK_GN_MONGE_AMPERE is not served yet (its structured form exists: A(z) = A_1 diag(d(z)) + A_2 as for Eikonal)");
     if (elliptic && !v0) return GPK_ERR_ARG;
     const int nc = d.nz + 1;
     if (lds < nc || ldw < nc) return gpk_bad_arg(h, "structured solve: lds/ldw < nz+1");
@@ -926,6 +941,7 @@ extern "C" int gpk_gn_gram_prepare(gpk_handle h, const gpk_gn_problem* p, double
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
     if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR is not served (it has no structured form)");
+    if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "gram_prepare: GPK_GN_MONGE_AMPERE is not served yet (no structured prepare)");
     if (p->system == GPK_GN_ELLIPTIC_RELAXED || !p->W1 || !p->W2 || (elliptic && !p->v0))
         return gpk_bad_arg(h, "gram_prepare: needs W1/W2 (and v0 for the elliptic system) of gpk_gn_structured_prepare; not for the relaxed system");
     const int nz = d.nz;

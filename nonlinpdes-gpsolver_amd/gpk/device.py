@@ -34,7 +34,8 @@ def dinv_block_for(n):
     while db > 256 and db > n // 4:
         db //= 2
     return db
-SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4, 'Semilinear2d': 5}
+SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4, 'Semilinear2d': 5,
+          'MongeAmpere2d': 6}
 NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
 EVIDENCE_TERMS = ('log_Z', 'J', 'logdet_theta', 'logdet_H', 'gamma_term', 'two_pi_term')   # host_terms[6] of gpk_log_evidence
 
@@ -516,6 +517,40 @@ class Context:
         return self._extend_functionals('extend_functionals_op', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_op, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb,
                                         lambda Nd, Nb: (self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)), coeff, which)
+
+    # ---- Hessian layout: D = d11 - d22, M = 2 d12, Laplacian, delta (gpk_assemble_hess, gpk_extend_functionals_hess, gpk_pde_residual_ma) ----
+    def assemble_hess(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the Hessian layout (blocks D, M, Laplacian on Xd, delta on [Xd; Xb]): (DeviceArray N x N with N = 4 Nd + Nb,
+        [trace(block k) / trace(block 3) for k = 0, 1, 2]).  out: a DeviceArray to write into (any leading dimension >= N)."""
+        require_gaussian_family(kernel, 'gpk_assemble_hess')
+        Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 2) for X in (Xd, Xb))
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 4 * Nd + Nb
+        dXd, dXb = self.points(Xd), self.points(Xb)
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratios = (C.c_double * 3)()
+        self._chk(self.lib.gpk_assemble_hess(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
+                                             float(nugget), NUGGET[nugget_type], T.ptr, T.ld, ratios))
+        self.synchronize()
+        return T, list(ratios)
+
+    def extend_functionals_hess(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
+        """Value / derivatives up to order two of the extension on the Hessian layout at Xt (gpk_extend_functionals_hess): a
+        (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP).  coeff = Theta^{-1} sol_vec (4 Nd + Nb values)
+        with the Theta of assemble_hess."""
+        return self._extend_functionals('extend_functionals_hess', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_hess, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
+
+    def pde_residual_ma(self, fields, rhs):
+        """Pointwise residual d11 d22 - d12^2 - f of the Monge-Ampere equation (gpk_pde_residual_ma), as an (Nt,) DeviceArray.
+        fields: (3, Nt) d11, d12, d22 of the extension; rhs as for pde_residual."""
+        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
+        Nt = du.cols
+        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        out = DeviceArray(self, Nt)
+        self._chk(self.lib.gpk_pde_residual_ma(self.h, Nt, du.ptr, du.ld, dr.ptr, out.ptr))
+        self.synchronize()
+        return out
 
     # ---- operator and boundary functionals in three dimensions (gpk_assemble_op3d, gpk_extend_functionals_op3d) ----
     def _coeff_rows(self, c, n, width, what):

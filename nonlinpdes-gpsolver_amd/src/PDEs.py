@@ -1078,3 +1078,103 @@ class Semilinear2d(_GPEquation):
     def _residual(self, fields_u, fields_a, rhs):
         """-eps Laplace(u) + N(u, grad u) - f on rows of the extension (gpk_pde_residual_sl)"""
         return get_context().pde_residual_sl(self.eps, self.nonlinearity.params, fields_u, rhs).download().reshape(-1)
+
+
+class MongeAmpere2d(_GPEquation):
+    """det D^2 u = f (f > 0) on a rectangle, u = g on its boundary: the Monge-Ampere equation, convex solution.  Fully nonlinear (the
+    equation is nonlinear in the second derivatives), no counterpart in the reference.  Solved in the convex-branch form
+        Laplace(u) = sqrt((D u)^2 + (M u)^2 + 4 f),   D = d_11 - d_22,  M = 2 d_12      ((Laplace u)^2 = (D u)^2 + (M u)^2 + 4 det D^2 u)
+    -- no division, smooth for f > 0, and the positive root selects the convex branch, so the zero start is admissible.  The Gram matrix
+    is the Hessian layout's (rows D u, M u, Laplace(u), u per domain point, then u on the boundary: gpk_assemble_hess, Gaussian kernels
+    only), the Gauss-Newton system is GPK_GN_MONGE_AMPERE with unknowns [u | D u | M u].  Where an iterate makes the radicand negative the
+    loss is NaN, reported like every other NaN.  log_evidence is the base class's; posterior_variance / posterior_covariance /
+    posterior_sample raise NotImplementedError (the layout has no rectangular cross evaluator yet).  GPK_STRUCTURED is ignored: the
+    structured form is not served yet.  eq.line_search (src/linesearch.py) is honoured; DESIGN.md section K names a configuration that needs it."""
+    _layout = 'Hessian'
+    _system = 'MongeAmpere2d'
+    _blocks_per_point = 3
+    _structured_optin = False
+    _deriv_names = ('value', 'd1', 'd2', 'd11', 'd12', 'd22')
+
+    def __init__(self, bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]])):
+        self.bdy = bdy
+        self.rhs = rhs
+        self.domain = domain
+
+    def _gn_params(self):
+        return 0.0, 0.0, 0.0
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
+        """kernel: Gaussian or anisotropic_Gaussian (the Matern family is refused: the Hessian layout has no evaluator for it)"""
+        require_gaussian_family(kernel, 'MongeAmpere2d.Gram_matrix')
+        ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
+        if nugget_type == 'adaptive':
+            self.ratio = list(ratios[:3])
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        return ctx.assemble_hess(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+
+    def _split(self, z):
+        Nd = self.N_domain
+        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:]
+
+    def _root(self, v1, v2):
+        with onp.errstate(invalid='ignore'):
+            return onp.sqrt(v1 * v1 + v2 * v2 + 4.0 * self.rhs_f)
+
+    def GN_loss(self, z, z_old):
+        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
+        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
+        v0, v1, v2 = self._split(z)
+        _, p, q = self._split(z_old)
+        s = self._root(p, q)
+        v3 = s + (p * (v1 - p) + q * (v2 - q)) / s
+        return self._tri_loss(onp.concatenate([v1, v2, v3, v0, self.bdy_g]))
+
+    def Hessian_GN(self, z, z_old):
+        return self._hessian(z_old)
+
+    def _initial(self, initial_sol, n):
+        if isinstance(initial_sol, str) and initial_sol == 'zero':
+            return onp.zeros(n)
+        return super()._initial(initial_sol, n)
+
+    def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
+        """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
+        sol = self._initial(initial_sol, 3 * self.N_domain)
+        self.init_sol = sol
+        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
+        v0, v1, v2 = self._split(sol)
+        self.sol_vec = onp.concatenate([v1, v2, self._root(v1, v2), v0, self.bdy_g])
+        self.sol_sampled_pts = v0
+
+    def extend_sol(self, X_test):
+        ctx = get_context()
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        coeff = self._coeff(self._dL, self.sol_vec)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = ctx.extend_functionals_hess(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                        coeff, which=('value',)).download().reshape(-1)
+
+    def _derivative_fields(self, X_test):
+        coeff = self._coeff(self._dL, self.sol_vec)
+        return {'u': get_context().extend_functionals_hess(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                           coeff, which=self._deriv_names)}
+
+    def extend_derivatives(self, X_test):
+        """value, d1, d2, d11, d12 and d22 of the GP solution at X_test (numpy arrays)"""
+        return super().extend_derivatives(X_test)
+
+    def PDE_residual(self, X_test):
+        """det D^2 u - f at X_test from the second derivatives of the GP solution (gpk_pde_residual_ma; f evaluated at X_test)"""
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        coeff = self._coeff(self._dL, self.sol_vec)
+        hess = get_context().extend_functionals_hess(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                     coeff, which=('d11', 'd12', 'd22'))
+        rhs = eval_callback(self.get_rhs, X_test[:, 0], X_test[:, 1])
+        self.test_residual = get_context().pde_residual_ma(hess, rhs).download().reshape(-1)
+        return self.test_residual
+
+    def _posterior_unserved(self):
+        return 'MongeAmpere2d: gpk_assemble_cross has no rectangular evaluator for the Hessian layout yet'

@@ -4,7 +4,7 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d
+from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d
 from .nonlinearity import GradientNonlinearity, Nonlinearity
 
 
@@ -121,6 +121,11 @@ _EQUATIONS = {
         lambda c: ['[Equation type] Semilinear equation with a gradient-dependent nonlinearity',
                    f'[Equation form] - eps*Delta u + N(u, grad u) = f, N = {_gradient_nl_of(c).describe()}'],
         lambda c: f'[Equation parameter] eps = {c.eps}, (a1, a2, b, c1, c3) = {_gradient_nl_of(c).params}'),
+    'MongeAmpere2d': (
+        lambda c, **k: MongeAmpere2d(**k),
+        lambda c: ['[Equation type] Monge-Ampere equation (fully nonlinear)',
+                   '[Equation form] det D^2 u = f, convex solution: Delta u = sqrt((u_11 - u_22)^2 + (2 u_12)^2 + 4 f)'],
+        None),
     'Darcy_flow2d': (
         lambda c, **k: Darcy_flow2d(**k),
         lambda c: ['[Inverse problem type] Darcy flow 2d', '[Inverse problem form] -div(a grad u) = f, infer a from f and some observed u'],
