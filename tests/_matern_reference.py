@@ -17,7 +17,9 @@ Error of the reference itself: long double (eps 1.1e-19); the closed form is use
 terms are below J^6 T^(J-4) / J! = 3e-22: a few 1e-18 relative to (a / rho)^n, the size of an entry of order n.
 
 Also here: the layouts (functional of each block, which point set it lives on), and Theta, Theta_test, extension rows and the adaptive
-trace ratios assembled from these entries.
+trace ratios assembled from these entries; and the cases of tests/test_gpu_matern_shapes.py that its host preconditions
+(tests/test_matern_host.py) share: the (nu, rho) of the large sizes, the row subset compared there, the planted near-coincident and far
+points, and the per-test-point gate of the extension.
 """
 import functools
 
@@ -189,6 +191,129 @@ def block_nuggets(kernel, rho, layout, Nd, Nb, nugget, nugget_type):
     if nugget_type == 'adaptive':
         return [LD(nugget) * r for r in trace_ratios(kernel, rho, layout, Nd, Nb)] + [LD(nugget)]
     return [LD(nugget if nugget_type == 'identity' else 0.0)] * nb
+
+
+# ------------------------------------------------------------------- cases of tests/test_gpu_matern_shapes.py and of its host preconditions
+KERNELS = ('Matern52', 'Matern72', 'Matern92')
+RHOS = (0.3, (0.3, 0.07))
+LARGE = ((530, 46), (265, 41))                     # M = 576, blocks even (two-point kernel, grid2.x = 2; Darcy_a: 530); M = 306, blocks odd (one-point kernel, grid.x = 2)
+EPS = float(np.finfo(np.float64).eps)
+TILE = 32                                          # rows of Theta per workgroup (TP of csrc/gpk_assemble_ref.h)
+SUBSET_ROWS = 30                                   # rows of every block that the large cases compare: 4 edge + 2 tile boundary + 24 random
+
+
+def large_case(layout, size):
+    """(kernel, rho) of the size-th large size for this layout: index (layout + size) mod 3 into KERNELS and mod 2 into RHOS, so
+    layout + size = 0 .. 5 meets the six (nu, rho) once each, every nu meets both sizes (both kernel shapes), every layout both sizes"""
+    k = list(LAYOUTS).index(layout) + size
+    return KERNELS[k % 3], RHOS[k % 2]
+
+
+def row_subset(layout, Nd, Nb):
+    """per block the SUBSET_ROWS rows (indices into Theta, ascending) whose reference the large cases build: the first and the last two
+    rows of the block, both sides of the 32-row tile boundary (of the point index, which is what a workgroup's blockIdx.y counts)
+    nearest the block's middle, and 24 random others"""
+    out = []
+    for b, (o, n) in enumerate(offsets(layout, Nd, Nb)):
+        edge = TILE * max(1, int(round(n / 2 / TILE)))
+        fixed = [0, 1, n - 2, n - 1, edge - 1, edge]
+        assert len(set(fixed)) == 6 and 0 < edge < n - 2, (layout, Nd, Nb, b)
+        rest = np.setdiff1d(np.arange(n), fixed)
+        rng = np.random.RandomState(1000 * Nd + 10 * Nb + b)
+        pick = rng.choice(rest, SUBSET_ROWS - len(fixed), replace=False)
+        out.append(o + np.sort(np.concatenate([fixed, pick])))
+    return out
+
+
+def subset_coverage(layout, Nd, Nb, subset):
+    """the smallest number of rows of a row block in which a column of Theta is compared, over all columns and row blocks: a row of the
+    subset compares all its columns; the exact symmetry of Theta carries the result to the transposed entries, which adds nothing to
+    this count (it is the count of direct comparisons)"""
+    worst = None
+    for (o, n), rows in zip(offsets(layout, Nd, Nb), subset):
+        rows = np.unique(rows)
+        assert np.all((rows >= o) & (rows < o + n))
+        worst = rows.size if worst is None else min(worst, rows.size)
+    return worst
+
+
+def subset_rows_reference(kernel, rho, layout, Xd, Xb, subset, evaluate=None):
+    """the rows `subset` of Theta stacked block after block, (sum of the subset sizes, N): long double through rows(), or through
+    evaluate(fx, Xt) -> (Nt, N) (the float64 numpy class)"""
+    evaluate = evaluate or (lambda fx, P: rows(kernel, rho, layout, fx, P, Xd, Xb))
+    return np.concatenate([evaluate(f, P[idx - o]) for (f, P), (o, _), idx in zip(_points(layout, Xd, Xb), offsets(layout, len(Xd), len(Xb)), subset)],
+                          axis=0)
+
+
+# offsets of the planted near-coincident points: (target, source, offset) in the domain set, the boundary set (source in the domain set)
+# and the test set (source named)
+PLANT_D = ((1, 0, (1e-12, 0.0)), (3, 2, (6e-9, -8e-9)), (5, 4, (0.0, 1e-5)), (7, 6, (1e-3, 1e-3)), (9, 8, (0.0, 0.0)))
+PLANT_B = ((0, 10, (0.0, 0.0)), (1, 11, (3e-7, 0.0)))
+PLANT_T = ((1, 'd', 12, (1e-12, 0.0)), (2, 'd', 13, (0.0, -1e-6)), (3, 'b', 2, (1e-9, 1e-9)))
+
+
+def planted_points(Xd, Xb, Xt):
+    """copies of the points with coincident and nearly coincident ones planted (separations 0, 1e-12, 1e-8, 1e-5, 1.4e-3 in the domain
+    set; a boundary point on a domain point and one 3e-7 from one; test points 1e-12, 1e-6 and 1.4e-9 from collocation points)"""
+    Xd, Xb, Xt = (np.array(X, dtype=np.float64, copy=True) for X in (Xd, Xb, Xt))
+    for k, s, d in PLANT_D:
+        Xd[k] = Xd[s] + np.asarray(d)
+    for k, s, d in PLANT_B:
+        Xb[k] = Xd[s] + np.asarray(d)
+    for k, which, s, d in PLANT_T:
+        Xt[k] = (Xd if which == 'd' else Xb)[s] + np.asarray(d)
+    Xt[0] = Xd[3]                                                       # (the verbatim test point of the cases follows its domain point)
+    return Xd, Xb, Xt
+
+
+FAR_RHO2 = 0.002                                   # a / rho_2 > 745: pairs a unit apart in the second coordinate are beyond the underflow of exp
+FAR_BAND = (708.0, 745.0)                          # exp(-t) is subnormal in float64 for t in the band, 0 beyond
+
+
+def far_points(kernel, Xd, Xb, Xt):
+    """copies of the points with second coordinates set so that t = a |u| of rho = (0.3, FAR_RHO2) is 720 and 735 (in the band: the
+    first coordinate adds less than 0.05 to either) for the domain pairs (0, 1), (0, 2) and a test point against Xd[0], and beyond
+    the band (t > 1100) for the domain pair (0, 4) and a test point against Xd[0]"""
+    a = float(np.sqrt(2.0 * ORDER[kernel] + 1.0))
+    Xd, Xb, Xt = (np.array(X, dtype=np.float64, copy=True) for X in (Xd, Xb, Xt))
+    Xd[0, 1], Xd[1, 1], Xd[2, 1], Xd[4, 1] = 0.01, 0.01 + 720.0 * FAR_RHO2 / a, 0.01 + 735.0 * FAR_RHO2 / a, 0.999
+    Xt[1], Xt[2] = (Xd[0, 0], Xd[1, 1]), (Xd[0, 0], 0.999)
+    return Xd, Xb, Xt
+
+
+def scaled_distance(kernel, rho, X, Y):
+    """t = a |u| for every pair of the two point sets, long double"""
+    rho = np.atleast_1d(np.asarray(rho, dtype=LD))
+    a = np.sqrt(LD(2 * ORDER[kernel] + 1))
+    X, Y = np.asarray(X, dtype=LD), np.asarray(Y, dtype=LD)
+    return a * np.sqrt(((X[:, None, 0] - Y[None, :, 0]) / rho[0]) ** 2 + ((X[:, None, 1] - Y[None, :, 1]) / rho[-1]) ** 2)
+
+
+def extension_ratios(got, rows_ld, coeff):
+    """per test point |got - rows @ coeff| / (eps |rows| @ |coeff|), with the product accumulated in long double"""
+    c = np.asarray(coeff, dtype=np.float64).astype(LD)
+    err = np.abs(np.asarray(got).astype(LD) - rows_ld @ c)
+    terms = np.abs(rows_ld) @ np.abs(c)
+    assert np.all(terms > 0)
+    return (err / (LD(EPS) * terms)).astype(np.float64), terms
+
+
+class ExtensionGate:
+    """Per test point: |got - ref| <= C eps (|rows| @ |coeff|)_t with C = 32 r_np + 1, r_np the worst such ratio of np_value (the float64
+    numpy class's rows @ coeff) over the test points -- the rule `allowed` of tests/_gn_reference.py.  The bound may at no test point
+    exceed 1e-12 max_t (|rows| @ |coeff|), the bound of tests/test_gpu_matern.py.  The figures (device: the worst device ratio) are there
+    to be printed before check() asserts both."""
+
+    def __init__(self, got, np_value, rows_ld, coeff):
+        self.ratios, self.terms = extension_ratios(got, rows_ld, coeff)
+        self.device = float(np.max(self.ratios))
+        self.r_np = float(np.max(extension_ratios(np_value, rows_ld, coeff)[0]))
+        self.allowed = 32.0 * self.r_np + 1.0
+
+    def check(self, what=''):
+        assert np.all(LD(self.allowed) * LD(EPS) * self.terms <= LD(1e-12) * np.max(self.terms)), \
+            (what, 'the per-point bound is looser than the norm bound', self.r_np)
+        assert np.all(self.ratios <= self.allowed), (what, int(np.argmax(self.ratios)), self.device, self.r_np, self.allowed)
 
 
 def theta_nugget(kernel, rho, layout, Xd, Xb, nugget, nugget_type='adaptive', base=None):

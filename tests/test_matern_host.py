@@ -1,5 +1,6 @@
 """Matern kernels on the host (no GPU): the long-double reference of tests/_matern_reference.py against mpmath.diff, the closed-form
-classes of src/kernels.py against that reference, the trace ratios, and the rejections of what is out of scope."""
+classes of src/kernels.py against that reference, the trace ratios, the rejections of what is out of scope, and the preconditions of
+tests/test_gpu_matern_shapes.py: its planted points, its row subset, and its two gates on a planted error."""
 import numpy as np
 import pytest
 
@@ -164,3 +165,159 @@ def test_out_of_scope_paths_name_the_kernel(kernel, monkeypatch):
     eq3.sampled_pts(20, 12, sampled_type='random')
     with pytest.raises(ValueError, match=kernel):
         eq3.Gram_matrix(kernel=kernel, kernel_parameter=0.3)
+
+
+# ------------------------------------------------------------------- preconditions of tests/test_gpu_matern_shapes.py (no GPU)
+SHAPE_SIZES = ((64, 36), (65, 41))
+KERNELS = MR.KERNELS
+
+
+def _device_test():
+    """tests/test_gpu_matern.py, whose points, numpy rows and block gate the shape tests reuse (imported on use: it is a GPU file)"""
+    import test_gpu_matern as TM
+    return TM
+
+
+def _block_errors(got, ref, blocks):
+    """max |got - ref| / max|block| over the blocks"""
+    return max(float(np.max(np.abs(got[ro:ro + rn, co:co + cn].astype(MR.LD) - ref[ro:ro + rn, co:co + cn])) /
+                     np.max(np.abs(ref[ro:ro + rn, co:co + cn]))) for ro, rn in blocks for co, cn in blocks)
+
+
+@pytest.mark.parametrize('size', SHAPE_SIZES)
+def test_planted_points_hold_the_separations_they_claim(size):
+    TM = _device_test()
+    Xd0, Xb0, Xt0 = TM._points(*size)
+    Xd, Xb, Xt = MR.planted_points(Xd0, Xb0, Xt0)
+    assert all(np.array_equal(a, b) for a, b in zip(TM._points(*size), (Xd0, Xb0, Xt0)))      # (the inputs are left as they were)
+    sep = lambda p, q: float(np.hypot(*(np.asarray(p, dtype=MR.LD) - np.asarray(q, dtype=MR.LD))))
+    for k, s, d in MR.PLANT_D:
+        assert abs(sep(Xd[k], Xd[s]) - np.hypot(*d)) <= 1e-3 * np.hypot(*d), (k, s)       # (an offset of 1e-12 next to 0.5: 1.1e-16 off)
+    for k, s, d in MR.PLANT_B:
+        assert abs(sep(Xb[k], Xd[s]) - np.hypot(*d)) <= 1e-3 * np.hypot(*d), (k, s)
+    for k, which, s, d in MR.PLANT_T:
+        assert abs(sep(Xt[k], (Xd if which == 'd' else Xb)[s]) - np.hypot(*d)) <= 1e-3 * np.hypot(*d), (k, s)
+    assert np.array_equal(Xd[9], Xd[8]) and np.array_equal(Xb[0], Xd[10])
+    assert np.array_equal(Xt[0], Xd[3]) and np.array_equal(Xt[5], Xb[2]) and np.array_equal(Xt[66], Xd[-1])   # the three verbatim ones
+    # nothing else moved, and the planted pairs are the only close ones: every other pair keeps the spacing of uniform points
+    moved_d, moved_b = {k for k, _, _ in MR.PLANT_D}, {k for k, _, _ in MR.PLANT_B}
+    assert all(np.array_equal(Xd[k], Xd0[k]) for k in range(size[0]) if k not in moved_d)
+    assert all(np.array_equal(Xb[k], Xb0[k]) for k in range(size[1]) if k not in moved_b)
+    seps = sorted({round(float(np.hypot(*d)), 15) for _, _, d in MR.PLANT_D})
+    assert seps[0] == 0.0 and 0 < seps[1] <= 1e-12 and 1e-9 < seps[2] < 1e-7 and seps[3] == 1e-5 and 1e-3 < seps[4] < 2e-3
+
+
+@pytest.mark.parametrize('kernel', KERNELS)
+@pytest.mark.parametrize('size', SHAPE_SIZES)
+def test_far_points_hold_pairs_in_the_band_and_beyond(kernel, size):
+    TM = _device_test()
+    rho = (0.3, MR.FAR_RHO2)
+    Xd, Xb, Xt = MR.far_points(kernel, *TM._points(*size))
+    # (exp(-708) is the last normal value, 3.3e-308: the planted pairs sit at 720 and 735, inside the subnormal range)
+    assert 0.0 < float(np.exp(-735.0)) < float(np.exp(-720.0)) < np.finfo(np.float64).tiny and float(np.exp(-746.0)) == 0.0
+    t = MR.scaled_distance(kernel, rho, Xd, Xd)
+    for i, j in ((0, 1), (0, 2)):
+        assert MR.FAR_BAND[0] <= t[i, j] <= MR.FAR_BAND[1] and t[i, j] == t[j, i], (i, j, float(t[i, j]))
+    assert t[0, 4] > MR.FAR_BAND[1] and t[4, 0] > MR.FAR_BAND[1]
+    tt = MR.scaled_distance(kernel, rho, Xt[:67], Xd)
+    assert MR.FAR_BAND[0] <= tt[1, 0] <= MR.FAR_BAND[1] and tt[2, 0] > MR.FAR_BAND[1]
+    band, beyond = int(np.sum((t >= MR.FAR_BAND[0]) & (t <= MR.FAR_BAND[1]))), int(np.sum(t > MR.FAR_BAND[1]))
+    print(f'[matern-shapes] far points {kernel} {size}: {band} domain pairs in the band, {beyond} beyond')
+    assert band >= 4 and beyond >= 2
+    # the reference and the numpy class are finite there
+    T = MR.theta(kernel, rho, 'Burgers', Xd, Xb)
+    Tn = np.concatenate([TM._np_rows(kernel, rho, 'Burgers', f, P, Xd, Xb) for f, P in MR._points('Burgers', Xd, Xb)], axis=0)
+    assert np.all(np.isfinite(T)) and np.all(np.isfinite(Tn))
+
+
+@pytest.mark.parametrize('kernel', KERNELS)
+@pytest.mark.parametrize('layout', ['Nonlinear_elliptic', 'Burgers', 'Eikonal', 'Darcy_a'])
+def test_numpy_class_on_the_planted_points_keeps_the_gate_meaningful(layout, kernel):
+    """The gate of the shape tests is (4e-15 + 4 e_np) max|block|, e_np measured on the same points.  It means something only while the
+    numpy class itself is accurate there: asked here is e_np <= 1e-15 (4.5 eps).  That keeps the class itself more than a factor 2 inside the gate,
+    the measured part 4 e_np no larger than the fixed part 4e-15, and so the whole gate below 8e-15, twice the project's Gram-block
+    bound.  A larger e_np on the planted points would make the device gate hollow, and this test says so."""
+    TM = _device_test()
+    for size in SHAPE_SIZES:
+        Xd, Xb, Xt = MR.planted_points(*TM._points(*size))
+        blocks = MR.offsets(layout, *size)
+        for rho in RHOS:
+            T = MR.theta(kernel, rho, layout, Xd, Xb)
+            Tn = np.concatenate([TM._np_rows(kernel, rho, layout, f, P, Xd, Xb) for f, P in MR._points(layout, Xd, Xb)], axis=0)
+            Tt = MR.theta_test(kernel, rho, layout, Xt[:67], Xd, Xb)
+            Ttn = TM._np_rows(kernel, rho, layout, MR.ID, Xt[:67], Xd, Xb)
+            assert np.all(np.isfinite(T)) and np.all(np.isfinite(Tt)) and np.all(np.isfinite(Tn)) and np.all(np.isfinite(Ttn))
+            e_np = max(_block_errors(Tn, T, blocks),
+                       max(float(np.max(np.abs(Ttn[:, o:o + n] - Tt[:, o:o + n])) / np.max(np.abs(Tt[:, o:o + n]))) for o, n in blocks))
+            print(f'[matern-shapes] numpy class on the planted points {layout} {kernel} rho {rho} {size}: e_np {e_np:.3g}')
+            assert e_np <= 1e-15, 'the gate (4e-15 + 4 e_np) would be hollow on these points'
+
+
+def test_block_gate_rejects_a_relative_1e_11_in_a_near_coincident_entry():
+    TM = _device_test()
+    Nd, Nb = SHAPE_SIZES[1]
+    kernel, rho, layout = 'Matern52', RHOS[1], 'Burgers'
+    Xd, Xb, _ = MR.planted_points(*TM._points(Nd, Nb))
+    T = MR.theta(kernel, rho, layout, Xd, Xb)
+    Tn = np.concatenate([TM._np_rows(kernel, rho, layout, f, P, Xd, Xb) for f, P in MR._points(layout, Xd, Xb)], axis=0)
+    blocks = MR.offsets(layout, Nd, Nb)
+    good = T.astype(np.float64)
+    TM._gate_blocks('rounded reference', good, T, Tn, blocks, blocks)
+    for o, _ in blocks:                                               # the pair Xd[1], Xd[0] (1e-12 apart), in every diagonal block
+        assert abs(T[o + 1, o]) >= 0.5 * np.max(np.abs(T[o:o + Nd, o:o + Nd])), 'the planted entry is not of the size of the block diagonal'
+        bad = good.copy()
+        bad[o + 1, o] *= 1.0 + 1e-11
+        with pytest.raises(AssertionError):
+            TM._gate_blocks('planted error', bad, T, Tn, blocks, blocks)
+
+
+def test_extension_gate_rejects_1e_11_in_one_row():
+    TM = _device_test()
+    Nd, Nb = SHAPE_SIZES[1]
+    kernel, rho, layout = 'Matern72', RHOS[1], 'Eikonal'
+    Xd, Xb, Xt = MR.planted_points(*TM._points(Nd, Nb))
+    Xt = Xt[:9]
+    for nm in ('value', 'laplacian'):
+        rows = MR.rows(kernel, rho, layout, MR.FUNCTIONALS[nm], Xt, Xd, Xb)
+        rows_np = TM._np_rows(kernel, rho, layout, MR.FUNCTIONALS[nm], Xt, Xd, Xb)
+        coeff = np.random.RandomState(rows.shape[1]).normal(size=rows.shape[1])
+        value = rows_np @ coeff
+        g = MR.ExtensionGate(value, value, rows, coeff)
+        print(f'[matern-shapes] extension gate {nm}: numpy class r_np {g.r_np:.3g}, allowed {g.allowed:.3g}')
+        g.check()
+        assert g.allowed * MR.EPS <= 1e-12
+        t = int(np.argmax(np.abs(value) / g.terms.astype(np.float64)))
+        assert abs(value[t]) * 1e-11 > g.allowed * MR.EPS * float(g.terms[t]), 'the planted error is inside the gate: choose another point'
+        bad = value.copy()
+        bad[t] *= 1.0 + 1e-11
+        with pytest.raises(AssertionError):
+            MR.ExtensionGate(bad, value, rows, coeff).check()
+        with pytest.raises(AssertionError, match='looser'):              # a numpy ratio that would lift the gate above the norm bound
+            worse = value + 1e-11 * g.terms.astype(np.float64)
+            MR.ExtensionGate(value, worse, rows, coeff).check()
+
+
+@pytest.mark.parametrize('layout', sorted(MR.LAYOUTS))
+def test_row_subset_of_the_large_cases_covers_every_column(layout):
+    seen = set()
+    for size, (Nd, Nb) in enumerate(MR.LARGE):
+        sub = MR.row_subset(layout, Nd, Nb)
+        blocks = MR.offsets(layout, Nd, Nb)
+        assert len(sub) == len(blocks)
+        for (o, n), idx in zip(blocks, sub):
+            loc = idx - o
+            assert idx.size == MR.SUBSET_ROWS == np.unique(idx).size and loc.min() == 0 and loc.max() == n - 1
+            assert {0, 1, n - 2, n - 1} <= set(loc.tolist())
+            edges = [int(p) for p in loc if p % MR.TILE == 0 and p - 1 in loc and p > 1]
+            assert edges and min(abs(p - n / 2) for p in edges) <= MR.TILE / 2, 'no tile boundary next to the middle of the block'
+        assert MR.subset_coverage(layout, Nd, Nb, sub) >= 30
+        assert [a.tolist() for a in MR.row_subset(layout, Nd, Nb)] == [a.tolist() for a in sub]      # deterministic
+        seen.add(MR.large_case(layout, size))
+    assert len(seen) == 2
+
+
+def test_large_cases_meet_every_nu_at_both_kernel_shapes():
+    table = {(layout, size): MR.large_case(layout, size) for layout in MR.LAYOUTS for size in range(len(MR.LARGE))}
+    for size in range(len(MR.LARGE)):
+        assert {table[l, size][0] for l in MR.LAYOUTS} == set(KERNELS)
+    assert {v for v in table.values()} == {(k, r) for k in KERNELS for r in MR.RHOS}
