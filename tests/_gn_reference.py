@@ -338,11 +338,12 @@ def full_reference(system, Nd):
 class VectorReference:
     """The step at z without L^-1 A: w = L^-1 F(z) and loss = w^T w; apply_H(d) = 2 A^T L^-T L^-1 A d; g = 2 A^T L^-T w;
     residual(d) = apply_H(d) - g = 2 A^T L^-T L^-1 (A d - F); delta by float64 Cholesky (Pipeline64) + refinement with these long-double
-    residuals.  Two single-vector long-double solves per factor and product: O(N^2)."""
+    residuals.  Two single-vector long-double solves per factor and product: O(N^2).
+    lin_fn: the linearisation (default: linearise of this module; _semilinear_reference and _monge_ampere_reference pass their own)."""
 
-    def __init__(self, cs, z, want_delta=True):
+    def __init__(self, cs, z, want_delta=True, lin_fn=None):
         self.case, self.z = cs, np.array(z, dtype=np.float64)
-        lin = self.lin = linearise(cs, z)
+        lin = self.lin = (lin_fn or linearise)(cs, z)
         self.w = _group_solve(cs, lin.F)
         self.loss = self.w @ self.w
         self.g = LD(2) * lin.tmul(_group_solve(cs, self.w, trans=True))

@@ -279,6 +279,20 @@ def full_reference(Nd, Nb):
 gates = SL.gates
 
 
+class VectorReference(R.VectorReference):
+    """_gn_reference.VectorReference (the step without L^-1 A, O(N^2)) on this module's linearise; gated by gate_loss,
+    gate_backward_vec and gate_forward of _gn_reference"""
+
+    def __init__(self, cs, z, want_delta=True):
+        super().__init__(cs, z, want_delta, lin_fn=linearise)
+
+
+@functools.lru_cache(maxsize=None)
+def vector_reference(Nd, Nb):
+    cs = case(Nd, Nb)
+    return VectorReference(cs, cs.z0)
+
+
 # ------------------------------------------------------------------------------------------------ the Gram gate
 GRAM_BOUND = 4e-15            # the project's Gram-block bound (tests/_gauss_reference.py BOUND), here per entry, in units of its magnitude sum
 

@@ -8,6 +8,7 @@ poisoned upload and sizes it shares:
   linearise           F(z), the magnitude sums of its entries and the entries of A(z) with their magnitude sums, long double
   check_build         [A | F] as a kernel wrote it against those entries: copies and constants exact, the rest within 4 ulp
   FullReference       S, H, g, loss, delta of one step in long double, with the float64 pipeline (_gn_reference.Pipeline64) next to it
+  VectorReference     the same step without L^-1 A (_gn_reference.VectorReference on this linearise): loss, g, delta, H as an operator
   gn_float64          the float64 Gauss-Newton iteration on a Gram factor (the oracle's gn_method with this system)
   posterior_*, log_evidence   the numpy formulas of include/gpk.h with the reference's P and R, in the dtype asked for
 """
@@ -162,6 +163,21 @@ class FullReference:
 def full_reference(Nd):
     cs = case(Nd)
     return FullReference(cs, cs.z0)
+
+
+class VectorReference(R.VectorReference):
+    """_gn_reference.VectorReference (w, loss, g, p64, normH, delta, apply_H, residual: the step without L^-1 A, O(N^2)) on this
+    module's linearise, for the sizes the full form is too slow for; the gates gate_loss, gate_backward_vec, gate_forward of
+    _gn_reference apply to it unchanged"""
+
+    def __init__(self, cs, z, want_delta=True):
+        super().__init__(cs, z, want_delta, lin_fn=linearise)
+
+
+@functools.lru_cache(maxsize=None)
+def vector_reference(Nd, Nb):
+    cs = case(Nd) if NB.get(Nd) == Nb else Case(Nd, Nb)
+    return VectorReference(cs, cs.z0)
 
 
 def err(got, ref):

@@ -19,11 +19,12 @@ FLAT = 1 << 30                        # slope divisor of a flat segment
 
 
 def systems():
-    return ('elliptic', 'relaxed', 'burgers', 'eikonal', 'darcy')
+    return ('elliptic', 'relaxed', 'burgers', 'eikonal', 'darcy', 'semilinear', 'monge_ampere')
 
 
 def n_unknowns(system, Nd):
-    return {'elliptic': Nd, 'relaxed': 2 * Nd, 'burgers': 3 * Nd, 'eikonal': 3 * Nd, 'darcy': 6 * Nd}[system]
+    return {'elliptic': Nd, 'relaxed': 2 * Nd, 'burgers': 3 * Nd, 'eikonal': 3 * Nd, 'darcy': 6 * Nd, 'semilinear': 3 * Nd,
+            'monge_ampere': 3 * Nd}[system]
 
 
 def _entries(system, Nd, Nb, group='u'):
@@ -38,6 +39,13 @@ def _entries(system, Nd, Nb, group='u'):
     elif system == 'burgers':                      # unknowns [v0 | v2 | v3]; rows [PDE; v2; v3; v0; g]
         out += [(t, t), (Nd + t, t), (2 * Nd + t, t), (Nd + t, Nd + t), (2 * Nd + t, 2 * Nd + t), (t, 3 * Nd + t)]
     elif system == 'eikonal':                      # unknowns [v0 | v1 | v2]; rows [v1; v2; PDE; v0; g]
+        out += [(Nd + t, t), (2 * Nd + t, Nd + t), (Nd + t, 2 * Nd + t), (2 * Nd + t, 2 * Nd + t), (t, 3 * Nd + t)]
+    elif system == 'semilinear':                   # unknowns [v0 | v1 | v2]; rows [v1; v2; PDE; v0; g] (include/gpk.h, GPK_GN_SEMILINEAR):
+        # the PDE row (N(v0, v1, v2) - f) / eps of point t depends on all three unknowns of t -- N_u, N_p, N_q -- so v0_t enters in
+        # row 2 N_d + t already, N_d rows above its unit entry
+        out += [(Nd + t, t), (2 * Nd + t, Nd + t), (t, 2 * Nd + t), (Nd + t, 2 * Nd + t), (2 * Nd + t, 2 * Nd + t), (t, 3 * Nd + t)]
+    elif system == 'monge_ampere':                 # unknowns [u | D u | M u]; rows [D u; M u; Delta u; u; g] (GPK_GN_MONGE_AMPERE):
+        # the PDE row s = sqrt(v1^2 + v2^2 + 4 f) has the entries v1 / s, v2 / s and none for v0: Eikonal's pattern
         out += [(Nd + t, t), (2 * Nd + t, Nd + t), (Nd + t, 2 * Nd + t), (2 * Nd + t, 2 * Nd + t), (t, 3 * Nd + t)]
     elif system == 'darcy':                        # unknowns [w0 | w1 | w2 | v0 | v1 | v2]
         if group == 'a':                           # rows [w1; w2; w0]
@@ -61,7 +69,7 @@ def staircase_position(system, Nd):
         return j
     if system == 'burgers':                        # the three unknowns of point t interleaved
         return 3 * t + g
-    if system == 'eikonal':                        # groups taken in the order v1, v2, v0
+    if system in ('eikonal', 'semilinear', 'monge_ampere'):    # groups taken in the order v1, v2, v0
         return np.choose(g, [2, 0, 1]) * Nd + t
     if system == 'darcy':                          # groups taken in the order v1, v2, w1, w2, w0, v0
         return np.choose(g, [4, 2, 3, 5, 0, 1]) * Nd + t
@@ -95,8 +103,9 @@ def closed_form(n, lead, lead_div=1):
 
 def promised_profile(system, Nd, Nb, variant='exact'):
     """first_row(c), c < n_z, that the layout of gpk_gn_step must promise.  variant: 'exact' (GEMM-only solve path), 'conservative'
-    (Eikonal on the substitution path: the slope-1 closed form over all columns); Darcy: 'u' or 'a' (the a-part: slope 1 on its
-    columns [N_d, 4 N_d) only, 3 N_d = no entry)."""
+    (Eikonal and Monge-Ampere on the substitution path: the slope-1 closed form over all columns); Darcy: 'u' or 'a' (the a-part:
+    slope 1 on its columns [N_d, 4 N_d) only, 3 N_d = no entry).  The semilinear system has ONE profile on every path, the closed form
+    (exact for it); Monge-Ampere's exact profile is Eikonal's two-segment one, written as such."""
     nz = n_unknowns(system, Nd)
     if system == 'darcy':
         if variant == 'a':
@@ -107,8 +116,10 @@ def promised_profile(system, Nd, Nb, variant='exact'):
             out[sub] = closed_form(3 * Nd, 3 * Nd)    # (equal to the exact rows there: tests/test_staircase_model.py)
             return out
         return envelope(exact_first_rows(system, Nd, Nb, 'u'))
-    if system == 'eikonal' and variant == 'conservative':
+    if system == 'semilinear' or (system in ('eikonal', 'monge_ampere') and variant == 'conservative'):
         return closed_form(nz, nz)
+    if system == 'monge_ampere':
+        return stair_eval(stair_encoding('eikonal', Nd), nz)
     return envelope(exact_first_rows(system, Nd, Nb))
 
 

@@ -32,8 +32,10 @@ on the same W + 1, computed at run time.
      z.(p2 + q2); Eikonal: d_c (W1^T w)_c + (W2^T w)_c).  The host rendition is gated with the same scale.
   e. structured level 1, elliptic n_z = 513, 1025 (second trip of structured_form_kernel) and the dinv forms of the systems and sizes of
      a. and c.: their W lives in the handle's workspace, which the development library does not expose, so these are gated by the loss and
-     delta against _gn_reference.VectorReference, as section d of test_gpu_gn_rounding.py (Semilinear and Monge-Ampere have no vector-only
-     reference and are left to a.).
+     delta against _gn_reference.VectorReference, as section d of test_gpu_gn_rounding.py.  Semilinear and Monge-Ampere N_d = 342
+     (nc = 1027) with inverted blocks of 256 and 512, against the VectorReference of _semilinear_reference / _monge_ampere_reference:
+     the two-partition pipeline plus the GEMM-only solve, where Monge-Ampere runs Eikonal's two-segment profile and Semilinear must not
+     (the gates reject the dropped N_u / eps entries: tests/test_semilinear_host.py); three steps on one handle give the same bits.
 
 RESULTS: every test prints `device, allowed (numpy); worst so far` under its tag.  Worst lines of a run on an MI355X, as "tag: device
 of allowed (numpy)":
@@ -42,6 +44,9 @@ of allowed (numpy)":
   [fused darcy] 6.22 of 115 (3.56);             [fused darcy pred] 0.172 of 33 (1);
   [fused gram] 7.98 of 106 (3.28), Eikonal;     [fused gram pred] 0.458 of 33 (1);
   [fused vector loss] 0.716 of 33 (1);  [fused vector backward] 2.11 of 26.1 (0.784);  [fused vector forward] 9.43 of 126 (3.91).
+  Semilinear N_d 342, dinv 256 / 512: [fused vector loss] 0.306 of 39.4 (1.2), backward 0.381 of 12.8 (0.368), forward 277 of 8.43e3 (263:
+  its H has the larger condition; the device is at 1.05 x the float64 rendition);  Monge-Ampere N_d 342: loss 0.106 of 33 (1), backward
+  1.5 of 43 (1.31), forward 4.47 of 128 (3.96).  Both repeat their bits over three steps and ran pipelined.
 The device stays within a factor 4 of the float64 host rendition everywhere; Darcy's loss - |y|^2 is 5e-7 of the loss at this start.
 No variant of test_gpu_variants.VARIANTS is documented as not bit-repeatable; the repeat-bits assertions run on the default schedule only.
 """
@@ -349,6 +354,12 @@ _VREF = {}
 
 
 def _vector_reference(kind, Nd):
+    if kind == 'semilinear':
+        import _semilinear_reference as SL
+        return SL.vector_reference(Nd, FP.NB_FUSED)
+    if kind == 'monge_ampere':
+        import _monge_ampere_reference as MA
+        return MA.vector_reference(Nd, FP.NB_FUSED)
     cs = _case(kind, Nd)
     if Nd in R.NB:                                                   # (the case of test_gpu_gn_rounding.py: its cached reference)
         return R.vector_reference(kind, Nd)
@@ -358,13 +369,17 @@ def _vector_reference(kind, Nd):
 
 
 VECTOR = ([(k, n, dict(dinv=256)) for k, n in SUBSTITUTION if k in R.SYSTEMS] + [('darcy', 171, dict(dinv=256))]
-          + [('elliptic', 513, dict(dinv=256, structured=1)), ('elliptic', 1025, dict(dinv=256, structured=1))])
+          + [('elliptic', 513, dict(dinv=256, structured=1)), ('elliptic', 1025, dict(dinv=256, structured=1))]
+          # the two systems that reach Eikonal's kernels through step_layout / step_profile (csrc/gpk_gn.hip), at the smallest pipelined
+          # size, n_c = 1027: Semilinear must keep the closed form there, Monge-Ampere runs the two-segment profile
+          + [(k, 342, dict(dinv=b)) for k in ('semilinear', 'monge_ampere') for b in (256, 512)])
 
 
 @pytest.mark.parametrize('kind,Nd,form', VECTOR, ids=lambda v: '-'.join(f'{k}={x}' for k, x in v.items()) if isinstance(v, dict) else str(v))
 def test_forms_with_the_solved_block_in_the_workspace(dev_ctx, kind, Nd, form):
-    ctx, cs = dev_ctx, _case(kind, Nd)
+    ctx = dev_ctx
     ref = _vector_reference(kind, Nd)
+    cs = ref.case
     prob = _problem(ctx, kind, cs, **form)
     z = ctx.array(cs.z0)
     print()
@@ -375,6 +390,12 @@ def test_forms_with_the_solved_block_in_the_workspace(dev_ctx, kind, Nd, form):
             assert mode.value == 1, 'not the structured level 1 of the elliptic system'
         loss, info = ctx.gn_step(prob, z, 0.5)
         delta, z_out = prob.workspace()[2].download().copy(), z.download().copy()
+        if kind in ('semilinear', 'monge_ampere'):                   # repeat bits on one handle
+            for _ in range(2):
+                z.upload(cs.z0)
+                again = ctx.gn_step(prob, z, 0.5)
+                assert again == (loss, info) and np.array_equal(prob.workspace()[2].download(), delta) \
+                    and np.array_equal(z.download(), z_out), 'not repeatable'
         if kind != 'darcy' and cs.nz + 1 >= 1025:
             assert _pipelined_step(ctx, prob, cs.z0), NO_STREAMS
     finally:

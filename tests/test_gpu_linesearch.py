@@ -1,6 +1,6 @@
 """The line search of the Gauss-Newton iteration on the device (gpk_gn_direction, gpk_gn_trial_losses, gpk_gn_trial_accept,
 gpk_gn_step_ls; DESIGN.md section K, "Line search") against tests/_linesearch_reference.py and the long-double references of
-_gn_reference / _nl_reference / _semilinear_reference.
+_gn_reference / _nl_reference / _semilinear_reference / _monge_ampere_reference.
 
 Synthetic, well-conditioned factors with poisoned upper triangles and padding, as in test_gpu_gn_rounding.py; N_d = 65 (straddles
 nothing) and 129 (one past two 64-blocks); every test with and without the inverted diagonal blocks.  The trial-loss gate also runs at N_d = 333.
@@ -8,15 +8,18 @@ nothing) and 129 (one past two 64-blocks); every test with and without the inver
   1. direction: z bitwise unchanged; delta, info, loss bit-identical to gpk_gn_step(step 0.5) on a second handle; loss through gate_loss;
      pred against the long-double g . delta / 2 with the rule of every gate of _gn_reference: allowed(r64) = 32 r64 + 1, r64 the same
      ratio of the float64 pipeline.
-  2. trial losses: every system of SYSTEMS, the semilinear system (gq of _semilinear_reference, eps 0.1) and the elliptic system with
-     GPK_NL_EXP; K in {1, 5, 16}, t from {0, 1, 2, 2^-k} (z - t delta is then one rounding on host and device alike); each column through
-     gate_loss against the long-double loss at z - t_k delta; the t = 0 column against gpk_gn_loss(z) within the same gate; canaries
+  2. trial losses: every system of SYSTEMS, the semilinear system (gq of _semilinear_reference, eps 0.1), the elliptic system with
+     GPK_NL_EXP and the Monge-Ampere system (f > 0: the radicand v1^2 + v2^2 + 4 f is positive at every trial point, asserted in long
+     double before anything is compared); K in {1, 5, 16}, t from {0, 1, 2, 2^-k} (z - t delta is then one rounding on host and device
+     alike); each column through gate_loss against the long-double loss at z - t_k delta; the t = 0 column against gpk_gn_loss(z) within the same gate; canaries
      (1e30) in the padding of W and behind dev_losses[K - 1] intact; K = 0 and K = 17 refused with -9001, canaries intact.
   3. accept: the crafted loss vectors of test_linesearch_host.py uploaded: k as the reference rule, z_out bitwise z - t_k delta, z
      bitwise untouched for k = -1.
   4. gpk_gn_step_ls: (a) elliptic 65, defaults: k = 0 and z_out bit-identical to gpk_gn_step(step 1); (b) t0 = 8: k >= 2 and k = the
      reference rule on the device's own losses, loss_in, pred, after asserting that no loss lies within 16 eps loss_in of its threshold;
-     (c) GPK_NL_EXP with a first trial that overflows exp: non-finite leading losses skipped, z_out finite; (d) gn_measurement(z_out)
+     (c) GPK_NL_EXP with a first trial that overflows exp: non-finite leading losses skipped, z_out finite;
+     (c') Monge-Ampere with f_i < 0 at one point, chosen so that the radicand is positive at z and negative at z - delta (verified in long double with the device's delta): the
+     NaN leading losses are skipped, k = the reference rule on the device's own losses, z_out finite; (d) gn_measurement(z_out)
      bitwise the column the build kernel wrote for the accepted k (gpk_debug_gn_trial_build of the development library).
   5. end to end through Semilinear2d on a Gram factor (N_d 200, N_b 60, nugget 1e-6, eps 0.05, N = u (p + q / 2), five steps): loss
      history non-increasing, step_hist complete, accepted k of every step = the CPU reference's, final iterate within the 1e-6 parity
@@ -30,7 +33,9 @@ nothing) and 129 (one past two 64-blocks); every test with and without the inver
 
 RESULTS: each test prints its ratios under [direction], [trial], [step_ls]; worst ratios of a run on an MI355X, as "device of allowed":
   direction loss 1.06 of 47.2;  direction pred 1.58 of 21.4;  trial 4.41 of 33 at N_d = 65 / 129 and 4.10 of 33 at 333 (numpy figure =
-  (allowed - 1) / 32).  step_ls: no loss closer than 1.8e12 eps loss_in to its threshold, on the device and on the CPU, same k.
+  (allowed - 1) / 32); Monge-Ampere: 2.61 of 33 at N_d = 65 / 129 and 3.63 of 117 at 333.  Negative radicand (N_d 65, point 4: 0.944 at z,
+  -0.944 at z - delta): losses NaN, NaN, 0.1216, ... on both paths, k = 2.
+  step_ls: no loss closer than 1.8e12 eps loss_in to its threshold, on the device and on the CPU, same k.
   End to end: Semilinear2d k = 1, 1, 0, 0, 0 on both sides, parity 4.5e-13;  Bratu k = 2, 0, 0, 0, 0, 0, 0 on both sides, parity 9.0e-15,
   final-loss ratio plain / line-searched 6.43e21 on the device and on the reference (asserted: >= a tenth of the reference's).
 """
@@ -45,6 +50,7 @@ import pytest
 
 import _gn_reference as R
 import _linesearch_reference as LS
+import _monge_ampere_reference as MA
 import _nl_reference as NL
 import _semilinear_reference as SL
 
@@ -53,7 +59,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LD, EPS = R.LD, R.EPS
 SIZES = (65, 129)
-ALL_SYSTEMS = R.SYSTEMS + ('semilinear', 'exp')
+ALL_SYSTEMS = R.SYSTEMS + ('semilinear', 'exp', 'monge_ampere')
 DINV = [256, False]
 CANARY = 1e30
 T16 = np.array([0.0, 1.0, 2.0, 0.5, 0.25] + [2.0 ** -k for k in range(3, 14)])
@@ -73,11 +79,23 @@ def _case(system, Nd):
         return SL.case(Nd)
     if system == 'exp':
         return NL.case('exp', 'elliptic', Nd, R.NB[Nd])
+    if system == 'monge_ampere':
+        return MA.case(Nd, R.NB[Nd])
     return R.case(system, Nd)
 
 
 def _linearise(system, cs, z):
+    if system == 'monge_ampere':
+        with np.errstate(invalid='ignore'):                          # (a negative radicand is NaN here as on the device)
+            return MA.linearise(cs, z)
     return SL.linearise(cs, z) if system == 'semilinear' else NL.linearise(cs, z) if system == 'exp' else R.linearise(cs, z)
+
+
+def radicand(cs, z):
+    """v1^2 + v2^2 + 4 f of the Monge-Ampere row at the float64 point z, in long double"""
+    Nd = cs.Nd
+    z = np.asarray(z, dtype=np.float64).astype(LD)
+    return z[Nd:2 * Nd] ** 2 + z[2 * Nd:] ** 2 + 4 * cs.f.astype(LD)
 
 
 class _P64:
@@ -110,7 +128,7 @@ class LossRef:
 
 
 def _loss_ref(system, cs, z):
-    if system == 'semilinear':
+    if system in ('semilinear', 'monge_ampere'):
         return LossRef(system, cs, z)
     if system == 'exp':
         return NL.VectorReference(cs, z, want_delta=False)
@@ -183,7 +201,9 @@ def _problem(ctx, system, cs, dinv):
     import gpk
     L = _upload_factor(ctx, cs.L)
     keep = [L]
-    if system == 'semilinear':
+    if system == 'monge_ampere':
+        prob = gpk.GNProblem(ctx, 'MongeAmpere2d', cs.Nd, cs.Nb, cs.f, cs.g, L, dinv=dinv)
+    elif system == 'semilinear':
         prob = gpk.GNProblem(ctx, 'Semilinear2d', cs.Nd, cs.Nb, cs.f, cs.g, L, p0=cs.eps, dinv=dinv, gq=cs.gq)
     elif system == 'exp':
         prob = gpk.GNProblem(ctx, 'Nonlinear_elliptic', cs.Nd, cs.Nb, cs.f, cs.g, L, p0=cs.p0, p1=cs.p1, p2=cs.p2, nonlin=cs.nonlin, dinv=dinv)
@@ -233,6 +253,10 @@ def test_direction(dev_ctx, second_ctx, system, Nd, dinv):
 @pytest.mark.parametrize('system', ALL_SYSTEMS)
 def test_trial_losses(dev_ctx, system, Nd, dinv):
     ctx, cs = dev_ctx, _case(system, Nd)
+    if system == 'monge_ampere':                                     # a condition on the case, checked before anything is compared
+        d = _direction(system, Nd).astype(LD)
+        lowest = min(float(np.min(radicand(cs, (cs.z0.astype(LD) - LD(t) * d).astype(np.float64)))) for t in T16)
+        assert lowest > 0, f'a trial point of T16 has a radicand {lowest} <= 0: scale the direction'
     refs = _trial_refs(system, Nd)
     prob = _problem(ctx, system, cs, dinv)
     z, delta = ctx.array(cs.z0), ctx.array(_direction(system, Nd))
@@ -400,6 +424,51 @@ def test_step_ls_skips_overflowing_trials(dev_ctx, dinv):
     assert info == 0 and not np.isfinite(trial[0]) and k >= 1 and np.isfinite(trial[k])
     assert k == LS.accept(trial, t, loss, pred, 1e-4)
     assert np.all(np.isfinite(z.download())) and np.array_equal(z.download(), cs.z0 - t[k] * d)
+    prob.free()
+
+
+@functools.lru_cache(maxsize=None)
+def _negative_radicand_case(Nd):
+    """MA.case(Nd) with f_i < 0 at the one point i whose |(v1, v2)| the full step shrinks most: 4 f_i = -(a + b) / 2 with a, b =
+    v1^2 + v2^2 at z0 and at z0 - delta (float64 pipeline; delta depends on f_i, so the choice is iterated), which puts the radicand of
+    point i at (a - b) / 2 > 0 at z0 and at (b - a) / 2 < 0 at the first trial point.  The test verifies both with the device's delta."""
+    import copy
+    base = MA.case(Nd, R.NB[Nd])
+    cs = copy.copy(base)
+    cs.f = base.f.copy()
+    r2 = lambda z: z[Nd:2 * Nd] ** 2 + z[2 * Nd:] ** 2
+    i = None
+    for _ in range(6):
+        d = R.Pipeline64(cs, cs.z0, MA.linearise(cs, cs.z0)).delta
+        a, b = r2(cs.z0), r2(cs.z0 - d)
+        i = int(np.argmax(a - b)) if i is None else i
+        cs.f[i] = -(a[i] + b[i]) / 8
+    return cs, i
+
+
+@pytest.mark.parametrize('dinv', DINV, ids=['dinv', 'substitution'])
+def test_step_ls_skips_trials_with_a_negative_radicand(dev_ctx, dinv):
+    """Monge-Ampere, the twin of test_step_ls_skips_overflowing_trials: the radicand v1^2 + v2^2 + 4 f is positive at every point of z
+    and negative at one point of the first trial point z - delta (both verified here in long double, with the device's own delta): the
+    build returns NaN there, the leading loss is not finite and is skipped; k is the reference rule's on the device's own losses"""
+    ctx = dev_ctx
+    cs, i = _negative_radicand_case(65)
+    prob = _problem(ctx, 'monge_ampere', cs, dinv)
+    z = ctx.array(cs.z0)
+    _, pred, info_d = ctx.gn_direction(prob, z)
+    d = prob.workspace()[2].download().copy()
+    assert info_d == 0 and np.all(np.isfinite(d))
+    assert float(np.min(radicand(cs, cs.z0))) > 0, 'the radicand is not positive at z: the step itself is undefined'
+    first = radicand(cs, cs.z0 - 1.0 * d)
+    assert float(first[i]) < 0 and np.count_nonzero(first < 0) >= 1, 'the first trial point has no negative radicand: rebuild the case'
+    loss, info, k, t_acc, trial = ctx.gn_step_ls(prob, z, trials=8, t0=1.0, shrink=0.5, c1=1e-4)
+    t = LS.steps(1.0, 0.5, 8)
+    print(f'\n[step_ls] monge_ampere 65 dinv={dinv}: radicand at point {i}: {float(radicand(cs, cs.z0)[i]):.3g} at z, {float(first[i]):.3g} at '
+          f'z - delta; k = {k}, losses {trial}')
+    assert info == 0 and not np.isfinite(trial[0]) and k >= 1 and np.isfinite(trial[k])
+    assert k == LS.accept(trial, t, loss, pred, 1e-4) and t_acc == t[k]
+    assert np.all(np.isfinite(z.download())) and np.array_equal(z.download(), cs.z0 - t[k] * d)
+    assert float(np.min(radicand(cs, z.download()))) > 0
     prob.free()
 
 

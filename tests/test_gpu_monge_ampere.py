@@ -9,11 +9,14 @@ class MongeAmpere2d on the device, against tests/_monge_ampere_reference.py.
   b. extension rows against long-double rows @ coeff for every single bit and the full mask, N_t = 5 and 130; repeatable to the bit, a
      row's bits independent of the mask; refusals leave `out` untouched.
   c. one Gauss-Newton step at N_d = 150, N_b = 40 by the method and bound of tests/test_gpu_semilinear.py (SL.gates), substitution path
-     and inverted blocks of 256 and 512; gpk_gn_direction / gpk_gn_step_ls from the iterate after two steps; the prepares refuse.
+     and inverted blocks of 256 and 512; the same step and gates at (N_d, N_b) = (64, 7) and (129, 3), substitution path and blocks of
+     256, where the ends of the second segment of the two-segment profile (columns N_d and 3 N_d) sit on / one past the 64 / 128 edges;
+     gpk_gn_direction / gpk_gn_step_ls from the iterate after two steps; the prepares refuse.
   d. the residual entry.   e. MongeAmpere2d end to end.
 Every test prints what it measures under a [monge-ampere] tag.
 
-RESULTS (MI355X): see DESIGN.md section K, "Fully nonlinear: Monge-Ampere"."""
+RESULTS (MI355X): see DESIGN.md section K, "Fully nonlinear: Monge-Ampere".  The step at the block edges, worst ratio to the bound over
+both sizes and both paths: H 0.177, g 0.221, loss 0.0351, delta 0.262, z 0.262 (cond(H) 3.6)."""
 import ctypes as C
 
 import numpy as np
@@ -269,6 +272,32 @@ def test_step_hessian_grad_loss(ctx, dinv):
     assert info == 0 and np.array_equal(H, H.T)
     bad = _report(f'step dinv {dinv}', MA.gates(ref, H=H, g=g, loss=loss, delta=delta, z_out=z_out))
     bad += _report(f'step dinv {dinv} in-step', MA.gates(ref, loss=step_loss))
+    assert not bad, bad
+
+
+# N_d on a 64-edge and one past a 128-edge: the second segment of the two-segment profile (dinv) starts at column N_d and ends at 3 N_d,
+# so its ends sit on / next to the 64 / 128 / 256 tile and block edges (columns 64, 192; 129, 387); N_b of _gn_reference.NB where defined
+STEP_EDGES = tuple((Nd, MA.R.NB.get(Nd, 7)) for Nd in (64, 129))
+
+
+@pytest.mark.parametrize('dinv', [False, 256])
+@pytest.mark.parametrize('Nd,Nb', STEP_EDGES)
+def test_step_at_the_block_edges_of_the_profile(ctx, Nd, Nb, dinv):
+    """the step of test_step_hessian_grad_loss, same gates, at (N_d, N_b) = (64, 7) and (129, 3): dinv = 256 runs the two-segment
+    profile, dinv = False the conservative closed form"""
+    cs, ref = MA.case(Nd, Nb), MA.full_reference(Nd, Nb)
+    prob = _problem(ctx, cs, dinv)
+    assert (prob.nz, prob.rows) == (3 * Nd, 4 * Nd + Nb)
+    z = ctx.array(cs.z0)
+    H, g = ctx.gn_hessian_grad(prob, z)
+    loss = ctx.gn_loss(prob, z)
+    step_loss, info = ctx.gn_step(prob, z, 1.0)
+    delta, z_out = prob.workspace()[2].download().copy(), z.download().copy()
+    prob.free()
+    print(f'\n[monge-ampere step] N_d {Nd} N_b {Nb} dinv {dinv}: cond(H) {ref.cond:.3g}')
+    assert info == 0 and np.array_equal(H, H.T)
+    bad = _report(f'step {Nd} dinv {dinv}', MA.gates(ref, H=H, g=g, loss=loss, delta=delta, z_out=z_out))
+    bad += _report(f'step {Nd} dinv {dinv} in-step', MA.gates(ref, loss=step_loss))
     assert not bad, bad
 
 

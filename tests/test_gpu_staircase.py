@@ -5,10 +5,17 @@ solved block (gpk_i_gemm with `lead`, its lower-triangular SYRK form), the subst
 inverted diagonal blocks skip work from that promise.  This file checks
 
   A. the promise: gpk_debug_first_rows against the numpy model of tests/_staircase_model.py (written from the equations), and the
-     non-zeros gpk_gn_build_rev actually writes against it;
+     non-zeros gpk_gn_build_rev actually writes against it.  The two systems that reach Eikonal's layout 2 through the dispatch of
+     step_layout / step_profile (csrc/gpk_gn.hip) have tests of their own, at all six N_d: Semilinear (with and without the inverted
+     blocks: the closed form, explicitly not Eikonal's two-segment profile; random z, z = 0 and the Eikonal special case
+     gq = (0, 0, 1, 0, 0)), Monge-Ampere with the inverted blocks (the two-segment profile; random z and z = 0) and its conservative
+     twin (substitution path, gpk_tune key 23 = 2: the closed form).  All comparisons are exact integer comparisons; on an MI355X the
+     device agrees with the model in every column at every size;
   B. every consumer of every profile against a dense reference, with operands that are non-zero exactly AT first_row(c): products on
      small integers (exact in fp64 whatever the summation order: compared bit for bit), solves against the same entry point with
-     lead = 0 and by their residual in long double; under each launch form (gpk_tune keys) that changes the schedule of these paths;
+     lead = 0 and by their residual in long double; under each launch form (gpk_tune keys) that changes the schedule of these paths.
+     Semilinear and Monge-Ampere add nothing here: their profiles are 'eikonal_conservative' and 'eikonal' of PROFILES, at the same
+     factor order 4 N_d + N_b;
   C. the column-shard frames of the sharded step (stair_base = c0 for a piecewise profile, lead = n_z - c0 for a closed form).
 """
 import contextlib
@@ -69,23 +76,29 @@ def reset_profile(ctx):
 
 # ------------------------------------------------------------------------------------------------ A. the promise
 SYSTEM_NAME = {'elliptic': 'Nonlinear_elliptic', 'relaxed': 'Nonlinear_elliptic_relaxed', 'burgers': 'Burgers', 'eikonal': 'Eikonal',
-               'darcy': 'Darcy_flow2d'}
-LAYOUT = {'elliptic': 1, 'relaxed': 1, 'burgers': 3, 'eikonal': 2, 'darcy': 4}
+               'darcy': 'Darcy_flow2d', 'semilinear': 'Semilinear2d', 'monge_ampere': 'MongeAmpere2d'}
+LAYOUT = {'elliptic': 1, 'relaxed': 1, 'burgers': 3, 'eikonal': 2, 'darcy': 4, 'semilinear': 2, 'monge_ampere': 2}
+GQ_EIKONAL = (0.0, 0.0, 1.0, 0.0, 0.0)           # N = p^2 + q^2: the Eikonal special case of the semilinear system, dN/du = 0 for every z
 
 
-def _problem(ctx, system, Nd, dinv=True):
-    """a GNProblem with identity factors (the build and the layout do not read them) and random, non-zero data"""
+def _problem(ctx, system, Nd, dinv=True, gq=None):
+    """a GNProblem with identity factors (the build and the layout do not read them) and random, non-zero data (f > 0: the radicand of
+    the Monge-Ampere row is positive at every z); gq: the coefficients of the semilinear system (default: _semilinear_reference.GQ)"""
     import gpk
     Nb = NB[Nd]
     rng = np.random.RandomState(Nd)
-    order = {'elliptic': 2 * Nd + Nb, 'relaxed': 2 * Nd + Nb, 'burgers': 4 * Nd + Nb, 'eikonal': 4 * Nd + Nb, 'darcy': 4 * Nd + Nb}[system]
+    order = 2 * Nd + Nb if system in ('elliptic', 'relaxed') else 4 * Nd + Nb
     L = ctx.array(np.eye(order))
     L2 = ctx.array(np.eye(3 * Nd)) if system == 'darcy' else None
-    p = dict(elliptic=(1.0, 3.0, 0.0), relaxed=(1.0, 3.0, 1e-3), burgers=(0.7, 0.02, 0.0), eikonal=(0.1, 0.0, 0.0), darcy=(0.05, 0.0, 0.0))[system]
+    p = dict(elliptic=(1.0, 3.0, 0.0), relaxed=(1.0, 3.0, 1e-3), burgers=(0.7, 0.02, 0.0), eikonal=(0.1, 0.0, 0.0), darcy=(0.05, 0.0, 0.0),
+             semilinear=(0.1, 0.0, 0.0), monge_ampere=(0.0, 0.0, 0.0))[system]
     f = rng.uniform(0.5, 1.5, Nd); g = rng.uniform(0.5, 1.5, Nb)
     data = rng.uniform(0.5, 1.5, NDATA[Nd]) if system == 'darcy' else None
+    if system == 'semilinear':
+        import _semilinear_reference as SL
+        gq = SL.GQ if gq is None else gq
     prob = gpk.GNProblem(ctx, SYSTEM_NAME[system], Nd, Nb, f, g, L, p0=p[0], p1=p[1], pen_lambda=p[2], data_u=data, L2=L2,
-                         dinv=256 if dinv else False, cache_a=False)
+                         dinv=256 if dinv else False, cache_a=False, gq=gq)
     prob.keep += [L] + ([L2] if L2 is not None else [])
     return prob
 
@@ -156,6 +169,80 @@ def test_eikonal_conservative_profile(dev_ctx, Nd):
     Nb = NB[Nd]
     want = M.promised_profile('eikonal', Nd, Nb, 'conservative')
     for prob, form in ((_problem(ctx, 'eikonal', Nd, dinv=False), None), (_problem(ctx, 'eikonal', Nd), (23, 2))):
+        ctx.tune(23, form[1] if form else 1)
+        try:
+            rev, fu, _ = first_rows(ctx, prob)
+            S = build(ctx, prob, ctx.array(_starts(Nd, prob.nz)[0][1]))[:, :prob.nz]
+        finally:
+            ctx.tune(23, 1)
+        assert rev == 2 and np.array_equal(fu, want)
+        assert np.all(M.first_nonzero_rows(S) >= fu)
+
+
+@pytest.mark.parametrize('dinv', [True, False], ids=['dinv', 'substitution'])
+@pytest.mark.parametrize('Nd', ND)
+def test_semilinear_keeps_the_closed_form(dev_ctx, Nd, dinv):
+    """The semilinear system runs Eikonal's layout 2 and, with and without the inverted blocks, the slope-1 closed form -- NOT Eikonal's
+    two-segment profile, which would promise zeros over the entries N_u / eps of the v0 columns.  Random z without zeros: the build's
+    first non-zeros ARE the profile.  z = 0, and the Eikonal special case gq = (0, 0, 1, 0, 0) (dN/du = 0 for every z: those entries
+    are stored zeros): nowhere above it, and the reported profile does not follow the data."""
+    ctx = dev_ctx
+    Nb = NB[Nd]
+    want = M.promised_profile('semilinear', Nd, Nb)
+    assert np.array_equal(want, M.closed_form(3 * Nd, 3 * Nd))
+    prob = _problem(ctx, 'semilinear', Nd, dinv=dinv)
+    nz = prob.nz
+    rev, fu, _ = first_rows(ctx, prob)
+    assert rev == LAYOUT['semilinear'] == 2
+    assert np.array_equal(fu, want), np.nonzero(fu != want)[0][:8]
+    assert not np.array_equal(fu, M.promised_profile('eikonal', Nd, Nb))
+    assert np.all(np.diff(fu) <= 0)
+    for name, z0 in _starts(Nd, nz):
+        got = M.first_nonzero_rows(build(ctx, prob, ctx.array(z0))[:, :nz])
+        assert np.all(got >= fu), (name, np.nonzero(got < fu)[0][:8])
+        if name == 'random':
+            assert np.array_equal(got, fu), np.nonzero(got != fu)[0][:8]
+            assert np.array_equal(got, M.exact_first_rows('semilinear', Nd, Nb))
+    special = _problem(ctx, 'semilinear', Nd, dinv=dinv, gq=GQ_EIKONAL)
+    rev, fs, _ = first_rows(ctx, special)
+    assert rev == 2 and np.array_equal(fs, want)
+    got = M.first_nonzero_rows(build(ctx, special, ctx.array(_starts(Nd, nz)[0][1]))[:, :nz])
+    assert np.all(got >= fs)
+    assert np.array_equal(got, M.exact_first_rows('eikonal', Nd, Nb))    # (what is left when N_u vanishes: Eikonal's pattern)
+
+
+@pytest.mark.parametrize('Nd', ND)
+def test_monge_ampere_two_segment_profile(dev_ctx, Nd):
+    """Monge-Ampere on the GEMM-only solve path: layout 2 with Eikonal's two-segment profile; random z: the build's first non-zeros are
+    the profile; z = 0 (v1 / s = v2 / s = 0 with s = 2 sqrt(f) > 0): nowhere above it."""
+    ctx = dev_ctx
+    Nb = NB[Nd]
+    want = M.stair_eval(M.stair_encoding('eikonal', Nd), 3 * Nd)
+    assert np.array_equal(want, M.promised_profile('monge_ampere', Nd, Nb))
+    prob = _problem(ctx, 'monge_ampere', Nd)
+    nz = prob.nz
+    rev, fu, _ = first_rows(ctx, prob)
+    assert rev == LAYOUT['monge_ampere'] == 2
+    assert np.array_equal(fu, want), np.nonzero(fu != want)[0][:8]
+    assert np.all(np.diff(fu) <= 0)
+    for name, z0 in _starts(Nd, nz):
+        S = build(ctx, prob, ctx.array(z0))
+        assert np.all(np.isfinite(S))
+        got = M.first_nonzero_rows(S[:, :nz])
+        assert np.all(got >= fu), (name, np.nonzero(got < fu)[0][:8])
+        if name == 'random':
+            assert np.array_equal(got, fu), np.nonzero(got != fu)[0][:8]
+
+
+@pytest.mark.parametrize('Nd', (64, 129, 333))
+def test_monge_ampere_conservative_profile(dev_ctx, Nd):
+    """The twin of test_eikonal_conservative_profile: Monge-Ampere on the substitution path and under gpk_tune key 23 = 2 reports the
+    conservative closed form; the build stays inside it."""
+    ctx = dev_ctx
+    Nb = NB[Nd]
+    want = M.promised_profile('monge_ampere', Nd, Nb, 'conservative')
+    assert np.array_equal(want, M.closed_form(3 * Nd, 3 * Nd))
+    for prob, form in ((_problem(ctx, 'monge_ampere', Nd, dinv=False), None), (_problem(ctx, 'monge_ampere', Nd), (23, 2))):
         ctx.tune(23, form[1] if form else 1)
         try:
             rev, fu, _ = first_rows(ctx, prob)

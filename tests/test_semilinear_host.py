@@ -96,6 +96,44 @@ def test_step_gates_reject_a_dropped_dN_du():
         assert r <= a, (name, r, a)
 
 
+def test_vector_gates_reject_a_dropped_dN_du_at_the_pipelined_size():
+    """N_d = 342, N_b = 40 (n_z + 1 = 1027, the smallest pipelined size; tests/test_gpu_fused_phase.py section e): the vector-only
+    reference agrees with itself (the refined delta leaves a residual at the long-double rounding level, the float64 pipeline passes
+    the gates); a float64 step whose v0 columns are cut off above row 3 N_d + t -- rows [2 N_d + t, 3 N_d + t), what Eikonal's
+    two-segment profile would skip -- fails the backward and the forward gate, and so does a delta moved by 1e-11."""
+    import _gn_reference as R
+    from scipy.linalg import cho_factor, cho_solve, solve_triangular
+    Nd, Nb = 342, 40
+    vec = SL.vector_reference(Nd, Nb)
+    cs = vec.case
+    assert cs.nz + 1 == 1027
+    d = vec.delta
+    scale = vec.normH * float(np.linalg.norm(d.astype(np.float64))) + float(np.linalg.norm(vec.g.astype(np.float64)))
+    assert np.linalg.norm(vec.residual(d).astype(np.float64)) <= 1e-3 * R.EPS * scale
+    p = vec.p64
+    for gate, v in ((R.gate_loss, p.loss), (R.gate_backward_vec, p.delta), (R.gate_forward, p.delta)):
+        r, a = gate(vec, v)
+        assert r <= a, (gate.__name__, r, a)
+    A = vec.lin.dense(np.float64)
+    t = np.arange(Nd)
+    for tt in (0, Nd - 1):                                            # the only entry of a v0 column in those rows is N_u / eps
+        assert np.count_nonzero(A[2 * Nd + tt:3 * Nd + tt, tt]) == 1 and A[2 * Nd + tt, tt] != 0
+    A[2 * Nd + t, t] = 0.0
+    Sb = solve_triangular(cs.L, np.concatenate([A, vec.lin.F.astype(np.float64)[:, None]], axis=1), lower=True, check_finite=False)
+    H, g = 2 * Sb[:, :-1].T @ Sb[:, :-1], 2 * Sb[:, :-1].T @ Sb[:, -1]
+    wrong = cho_solve(cho_factor(H, lower=True), g)
+    u = np.random.RandomState(Nd).normal(size=cs.nz); u /= np.linalg.norm(u)
+    moved = p.delta + 1e-11 * np.linalg.norm(p.delta) * u
+    print()
+    for what, dd, factor in (('dropped dN/du', wrong, 1e6), ('delta moved by 1e-11', moved, 1.0)):
+        for gate in (R.gate_backward_vec, R.gate_forward):
+            r, a = gate(vec, dd)
+            print(f'[semilinear host] {what}: {gate.__name__} {r:.3g}, allowed {a:.3g}: fails by a factor {r / a:.3g}')
+            assert r > factor * a, (what, gate.__name__, r, a)
+    r, a = R.gate_loss(vec, p.loss * (1 + 1e-11))
+    assert r > a
+
+
 # (gq, eps): the three problems of the issue's table at N_d 300, N_b 80, Gaussian sigma 0.2, nugget 1e-6.  L2 errors at the collocation
 # points reached by the float64 reference iteration after 10 steps, from zero and from a standard normal start alike (this test prints
 # them): 1.69e-5, 1.11e-5, 1.09e-5 on the points of SL.points (the issue's table, on other points: 1.4e-5, 1.3e-5, 1.3e-5).  The bound

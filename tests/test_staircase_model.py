@@ -11,7 +11,8 @@ ND = (64, 65, 127, 128, 129, 333)
 
 @pytest.mark.parametrize('Nd', ND)
 @pytest.mark.parametrize('system,variant', [('elliptic', 'exact'), ('relaxed', 'exact'), ('burgers', 'exact'), ('eikonal', 'exact'),
-                                            ('eikonal', 'conservative'), ('darcy', 'u'), ('darcy', 'a')])
+                                            ('eikonal', 'conservative'), ('darcy', 'u'), ('darcy', 'a'), ('semilinear', 'exact'),
+                                            ('monge_ampere', 'exact'), ('monge_ampere', 'conservative')])
 def test_promised_profile_is_non_increasing_and_below_the_exact_rows(system, variant, Nd):
     Nb = 11
     fr = M.promised_profile(system, Nd, Nb, variant)
@@ -47,6 +48,41 @@ def test_where_the_layouts_are_exact(Nd):
     fu = M.promised_profile('darcy', Nd, Nb, 'u')
     assert np.array_equal(fu[:2 * Nd], ex[:2 * Nd]) and np.array_equal(fu[4 * Nd:], ex[4 * Nd:])
     assert np.all(fu[2 * Nd:4 * Nd] == 2 * Nd) and np.all(ex[2 * Nd:4 * Nd] >= 2 * Nd) and ex[3 * Nd - 1] == 2 * Nd
+
+
+@pytest.mark.parametrize('Nd', ND)
+def test_semilinear_keeps_the_closed_form(Nd):
+    """The semilinear system shares Eikonal's column order, but v0_t enters its PDE row 2 N_d + t: its exact rows are the slope-1 closed
+    form over all n_z columns, on every solve path, and Eikonal's two-segment profile would promise zeros where N_u / eps sits -- on
+    every v0 column (c < N_d), by exactly N_d rows."""
+    Nb, nz = 7, 3 * Nd
+    ex = M.exact_first_rows('semilinear', Nd, Nb)
+    want = M.closed_form(nz, nz)
+    for variant in ('exact', 'conservative'):
+        assert np.array_equal(M.promised_profile('semilinear', Nd, Nb, variant), want)
+    assert np.array_equal(want, M.envelope(ex)) and np.array_equal(want, ex)
+    assert np.array_equal(M.column_of_unknown('semilinear', Nd), M.column_of_unknown('eikonal', Nd))
+    two = M.promised_profile('eikonal', Nd, Nb)
+    assert np.all(two[:Nd] > ex[:Nd]) and np.array_equal(two[:Nd] - ex[:Nd], np.full(Nd, Nd))     # it would be wrong there ...
+    assert np.array_equal(two[Nd:], ex[Nd:])                                                       # ... and only there
+    # the entries it would drop are those of the PDE row: (2 N_d + t, v0_t), t = N_d - 1 - c
+    c = np.arange(Nd)
+    assert np.array_equal(ex[:Nd], 2 * Nd + (Nd - 1 - c))
+
+
+@pytest.mark.parametrize('Nd', ND)
+def test_monge_ampere_has_the_eikonal_profiles(Nd):
+    """v0 does not enter the Monge-Ampere PDE row: the exact rows are Eikonal's, the exact profile is the two-segment encoding, and the
+    conservative closed form overstates the v0 columns by N_d rows"""
+    Nb, nz = 7, 3 * Nd
+    ex = M.exact_first_rows('monge_ampere', Nd, Nb)
+    assert np.array_equal(ex, M.exact_first_rows('eikonal', Nd, Nb))
+    two = M.promised_profile('monge_ampere', Nd, Nb)
+    assert np.array_equal(two, M.stair_eval(M.stair_encoding('eikonal', Nd), nz))
+    assert np.array_equal(two, M.envelope(ex)) and np.array_equal(two, ex)
+    cons = M.promised_profile('monge_ampere', Nd, Nb, 'conservative')
+    assert np.array_equal(cons, M.closed_form(nz, nz))
+    assert np.array_equal(ex[:Nd] - cons[:Nd], np.full(Nd, Nd)) and np.array_equal(ex[Nd:], cons[Nd:])
 
 
 @pytest.mark.parametrize('Nd', ND)
