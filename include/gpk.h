@@ -37,9 +37,17 @@ enum { GPK_LAYOUT_ELLIPTIC = 0, GPK_LAYOUT_BURGERS = 1, GPK_LAYOUT_EIKONAL = 2, 
  *   polynomial (nu = 5/2: (1 + t + t^2/3) exp(-t)).  host_kparams = {rho_1, rho_2}: BOTH are read, each finite and > 0, else -9001.
  * The Matern ids are served by the calls of the reference layouts -- gpk_assemble, gpk_assemble_test, gpk_extend, gpk_extend_functionals,
  * gpk_assemble_cross, for every layout -- and by nothing else: the 3-D, boundary-functional and operator calls return -9001 for them.
- * Ids 2..7 and every id above 10 are invalid everywhere (-9001).  nu = 3/2 is absent on purpose: that kernel is not C^4 at coincident
- * points, so the diagonal of a Laplacian block does not exist. */
-enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 = 8, GPK_KERNEL_MATERN72 = 9, GPK_KERNEL_MATERN92 = 10 };
+ * Ids 2..7 and every id above 10 but 16 are invalid everywhere (-9001).  nu = 3/2 is absent on purpose: that kernel is not C^4 at
+ * coincident points, so the diagonal of a Laplacian block does not exist.
+ * GPK_KERNEL_PERIODIC ("Periodic kernel"): the product over the two axes of
+ *   kappa_k(d) = exp(-(2 p_k / w_k^2) sin^2(w_k d / 2)),  p_k = 2 / sigma_k^2,  w_k = 2 pi / L_k   on an axis with period L_k > 0,
+ *   kappa_k(d) = exp(-p_k d^2 / 2)   (the anisotropic Gaussian factor)                                on an axis with L_k = 0,
+ * so that every sample path, the posterior mean and all their derivatives have period L_k along axis k and that axis needs no boundary
+ * points.  host_kparams = {sigma_1, sigma_2, L_1, L_2}: FOUR doubles are read; sigma_k finite and > 0, L_k finite and >= 0, not both
+ * periods 0 (that kernel is GPK_KERNEL_ANISOTROPIC), else -9001 and nothing is launched.  Served by the same six calls as the Matern ids
+ * (gpk_assemble, gpk_assemble_test, gpk_assemble_cross, gpk_assemble_prior, gpk_extend, gpk_extend_functionals) and by nothing else. */
+enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 = 8, GPK_KERNEL_MATERN72 = 9, GPK_KERNEL_MATERN92 = 10,
+       GPK_KERNEL_PERIODIC = 16 };
 /* nugget_type of src/PDEs.py:56,250,391 / src/InverseProblems.py:66 */
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */

@@ -1,12 +1,26 @@
 """Shared argparse helpers of the main_*.py drivers (same flag names, types and defaults as the reference's drivers)."""
 
 
+import argparse
+
+
+class _ScalarOrList(argparse.Action):
+    """--kernel_parameter of the drivers whose default kernel takes one value: one value is stored as a float, as before; several (the
+    two length scales of --kernel periodic_Gaussian) as a list"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values[0] if len(values) == 1 else list(values))
+
+
 def add_kernel_and_sampling(parser, kernel, kernel_parameter, nugget, N_domain, N_boundary, kp_nargs=None):
     parser.add_argument("--kernel", type=str, default=kernel)
     if kp_nargs:
         parser.add_argument("--kernel_parameter", type=float, nargs=kp_nargs, default=kernel_parameter)
     else:
-        parser.add_argument("--kernel_parameter", type=float, default=kernel_parameter)
+        parser.add_argument("--kernel_parameter", type=float, nargs='+', action=_ScalarOrList, default=kernel_parameter)
+    # --kernel periodic_Gaussian --period L1 L2: the period of each axis, 0 = not periodic (solver_GP: cfg.period); a periodic axis
+    # gets no boundary points and must be as wide as its period
+    parser.add_argument("--period", type=float, nargs=2, default=None)
     parser.add_argument("--nugget", type=float, default=nugget)
     parser.add_argument("--nugget_type", type=str, default="adaptive", choices=["adaptive", "identity", 'none'])
     parser.add_argument("--sampled_type", type=str, default='random', choices=['random', 'grid'])
@@ -71,6 +85,14 @@ def nonlinearity_from(cfg):
     except ValueError as e:
         raise SystemExit(f'--nl_params: {e}')
     return tau, tau
+
+
+def periodic_axes_of(cfg):
+    """(axis 1 periodic, axis 2 periodic) of --period; the flag needs --kernel periodic_Gaussian and the kernel needs the flag"""
+    period = getattr(cfg, 'period', None)
+    if (cfg.kernel == 'periodic_Gaussian') != bool(period and any(period)):
+        raise SystemExit('--kernel periodic_Gaussian and --period L1 L2 (one of them > 0) go together')
+    return (False, False) if not period else (period[0] > 0, period[1] > 0)
 
 
 def figures_enabled(cfg):

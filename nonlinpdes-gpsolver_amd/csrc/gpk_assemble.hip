@@ -17,7 +17,7 @@
 //
 // The functional tables, the Hermite evaluation (hermite_plain), the frame of the extension kernel, the 16-byte store and the host side
 // of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.  The layouts, the argument structs and
-// the layout dispatch are shared with the Matern family of these layouts (gpk_assemble_matern.hip, launched from the entry points below): gpk_assemble_ref.h.
+// the layout dispatch are shared with the Matern family and the periodic kernel of these layouts (gpk_assemble_matern.hip, gpk_assemble_periodic.hip, launched from the entry points below): gpk_assemble_ref.h.
 #include "gpk_assemble_ref.h"
 
 using namespace gpk_asm;
@@ -372,12 +372,15 @@ __global__ __launch_bounds__(256) void pde_residual_sl_kernel(double eps, SlCoef
 template <int L> constexpr int lay_size(int b, int Nd, int Nb) { return b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0; }
 template <int L> constexpr int lay_N(int Nd, int Nb) { return lay_size<L>(0, Nd, Nb) + lay_size<L>(1, Nd, Nb) + lay_size<L>(2, Nd, Nb) + lay_size<L>(3, Nd, Nb); }
 
-// precisions, block offsets / sizes and the packed points: the fields AsmArgs and FnArgs share (the others are the caller's)
+// precisions, block offsets / sizes and the packed points: the fields AsmArgs and FnArgs share (the others are the caller's); the axes
+// of the periodic kernel
 template <class Args>
-int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb) {
+int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb,
+                PerArgs& per) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd) return gpk_bad_arg(h, "assemble: sizes/pointers");
     double p[2];
     if (matern_order(kernel)) GPK_TRY(matern_scales(h, kp, p));      // (the Matern family: inverse length scales)
+    else if (kernel == GPK_KERNEL_PERIODIC) { GPK_TRY(periodic_axes(h, kp, per)); p[0] = per.ax[0].p; p[1] = per.ax[1].p; }   // (per: read by the periodic kernels only)
     else GPK_TRY(precisions(h, "assemble: kernel id", kernel, kp, 2, p));
     g.p1 = p[0]; g.p2 = p[1];
     const bool known = with_layout(layout, [&](auto l) {
@@ -415,16 +418,19 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
                             double* ratios) {
     if (!h || !Theta) return GPK_ERR_ARG;
     AsmArgs g{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    PerArgs per{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
     const int matern = matern_order(kernel);                         // the kernel family is chosen here, on the host: 0 = Gaussian
+    const bool periodic = kernel == GPK_KERNEL_PERIODIC;
     int nb = 0, N = 0;
     double c[4] = {0, 0, 0, 0};
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         nb = Lay<L>::nb; N = lay_N<L>(Nd, Nb);
-        if (!matern) diag_values<L>(g.p1, g.p2, c);
+        if (!matern && !periodic) diag_values<L>(g.p1, g.p2, c);
     });
     if (matern) gpk_i_matern_diag(matern, layout, g.p1, g.p2, c);
+    if (periodic) gpk_i_periodic_diag(layout, per, c);
     if (ld < N) return gpk_bad_arg(h, "assemble: ld < N");
     // ratio_k = trace(block k) / trace(last block)   (src/PDEs.py:62-66, 256-262, 397-402; IP.py:72-87)
     double r[4] = {0, 0, 0, 1.0};
@@ -438,6 +444,7 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
     TimedLaunch timed(h);
     GPK_TRY(timed.start());
     if (matern) gpk_i_matern_gram(matern, layout, pairs, h->tune.asm_nt, h->stream, g);
+    else if (periodic) gpk_i_periodic_gram(layout, pairs, h->tune.asm_nt, h->stream, g, per);
     else with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP)), grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
@@ -459,13 +466,15 @@ extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const dou
     if (!out || !Xt) return gpk_bad_arg(h, "assemble_test: pointers");
     if (Nt <= 0) return gpk_bad_arg(h, "assemble_test: Nt <= 0");
     AsmArgs g{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    PerArgs per{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
     int N = 0;
     with_layout(layout, [&](auto l) { N = lay_N<decltype(l)::value>(Nd, Nb); });
     if (ld < N) return gpk_bad_arg(h, "assemble_test: ld < N");      // (rows would overlap and the last one leave the Nt x ld region)
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
     if (const int matern = matern_order(kernel)) gpk_i_matern_test(matern, layout, h->stream, g);
+    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_test(layout, h->stream, g, per);
     else with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
@@ -480,11 +489,13 @@ extern "C" int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const do
     if (Nt <= 0) return gpk_bad_arg(h, "assemble_cross: Nt <= 0");
     if (ld < Nt) return gpk_bad_arg(h, "assemble_cross: ld < Nt");
     AsmArgs g{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    PerArgs per{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const bool wide = pairs_eligible(h, out, ld, Nt);
     const dim3 grid(gpk_ceil_div(gpk_ceil_div(Nt, 2), 256), gpk_ceil_div(g.M, CROSS_TP));
     if (const int matern = matern_order(kernel)) gpk_i_matern_cross(matern, layout, wide, h->stream, g);
+    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_cross(layout, wide, h->stream, g, per);
     else with_layout(layout, [&](auto l) {                           // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
         constexpr int L = decltype(l)::value;
         if (wide) assemble_cross_kernel<L, true><<<grid, 256, 0, h->stream>>>(g);
@@ -505,13 +516,16 @@ extern "C" int gpk_assemble_prior(gpk_handle h, int kernel, const double* kp, co
     PriorArgs g{};
     double p[2];
     const int matern = matern_order(kernel);
+    PerArgs per{};
     if (matern) GPK_TRY(matern_scales(h, kp, p));
+    else if (kernel == GPK_KERNEL_PERIODIC) { GPK_TRY(periodic_axes(h, kp, per)); p[0] = per.ax[0].p; p[1] = per.ax[1].p; }
     else GPK_TRY(precisions(h, "assemble_prior: kernel id", kernel, kp, 2, p));
     g.p1 = p[0]; g.p2 = p[1];
     g.xa = Xa; g.na = na; g.xb = Xb; g.nb = nb; g.out = out; g.ld = ld;
     const bool wide = pairs_eligible(h, out, ld, nb);
     const dim3 grid(gpk_ceil_div(gpk_ceil_div(nb, 2), 256), gpk_ceil_div(na, CROSS_TP));
     if (matern) gpk_i_matern_prior(matern, wide, h->stream, g);
+    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_prior(wide, h->stream, g, per);
     else if (wide) assemble_prior_kernel<true><<<grid, 256, 0, h->stream>>>(g);
     else assemble_prior_kernel<false><<<grid, 256, 0, h->stream>>>(g);
     GPK_LAUNCH_CHECK(h);
@@ -561,9 +575,11 @@ extern "C" int gpk_extend(gpk_handle h, int layout, int kernel, const double* kp
                           const double* Xd, int Nd, const double* Xb, int Nb, const double* coeff, double* out) {
     if (!h || !out || !Xt || !coeff || Nt <= 0) return GPK_ERR_ARG;
     AsmArgs g{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    PerArgs per{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
     g.out = out; g.ld = 0; g.tx = Xt; g.Nt = Nt; g.coeff = coeff;
     if (const int matern = matern_order(kernel)) gpk_i_matern_extend(matern, layout, h->stream, g);
+    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_extend(layout, h->stream, g, per);
     else with_layout(layout, [&](auto l) { extend_kernel<decltype(l)::value><<<Nt, 256, 0, h->stream>>>(g); });
     GPK_LAUNCH_CHECK(h);
     return 0;
@@ -578,9 +594,11 @@ extern "C" int gpk_extend_functionals(gpk_handle h, int layout, int kernel, cons
     if (Nt <= 0) return gpk_bad_arg(h, "extend_functionals: Nt <= 0");
     if (ldo < Nt) return gpk_bad_arg(h, "extend_functionals: ldo < Nt");
     FnArgs g;
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb));
+    PerArgs per{};
+    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
     if (const int matern = matern_order(kernel)) gpk_i_matern_extend_fn(matern, layout, fmask, h->stream, g);
+    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_extend_fn(layout, fmask, h->stream, g, per);
     else with_layout(layout, [&](auto l) { launch_extend_fn<decltype(l)::value>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g); });
     GPK_LAUNCH_CHECK(h);
     return 0;

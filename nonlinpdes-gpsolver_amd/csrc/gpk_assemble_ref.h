@@ -1,6 +1,7 @@
-// gpk_assemble_ref.h -- what the two translation units of the reference layouts share: gpk_assemble.hip (the Gaussian family, the host
-// side of every entry point) and gpk_assemble_matern.hip (the Matern family: kernels and their launches).  The layouts, the argument
-// structs of the kernels, the layout dispatch, and the launch interface of the Matern kernels.  The kernels themselves stay in their
+// gpk_assemble_ref.h -- what the three translation units of the reference layouts share: gpk_assemble.hip (the Gaussian family, the host
+// side of every entry point), gpk_assemble_matern.hip (the Matern family: kernels and their launches) and gpk_assemble_periodic.hip (the
+// periodic kernel, likewise).  The layouts, the argument
+// structs of the kernels, the layout dispatch, and the launch interfaces of the Matern and the periodic kernels.  The kernels themselves stay in their
 // files: each family is compiled on its own, so that nothing added for one changes the code generated for the other.
 #pragma once
 #include "gpk_assemble_common.h"
@@ -73,7 +74,48 @@ inline int matern_scales(gpk_handle h, const double* kp, double (&r)[2]) {
     return 0;
 }
 
+// ---- the periodic kernel (DESIGN.md §K "Periodic kernel"): kappa_k(d) = exp(-(2 p_k / w_k^2) sin^2(w_k d / 2)), w_k = 2 pi / L_k -------
+// One axis of the product kernel, as the periodic kernels read it.  L = 0: the Gaussian factor exp(-p d^2 / 2) and the Hermite table
+// (w2 = pw = 0, g = p / 2); L > 0: the periodic factor, exponent -g sin^2(w d / 2).  Passed to the kernels beside AsmArgs / FnArgs /
+// PriorArgs, which therefore stay as the Gaussian and the Matern kernels know them.
+struct PerAxis {
+    double p;                             // precision 2 / sigma^2
+    double L;                             // period, 0: not periodic
+    double w2;                            // w^2
+    double pw;                            // p / w
+    double g;                             // factor of the exponent: 2 p / w^2, or p / 2
+};
+struct PerArgs { PerAxis ax[2]; };
+
+// host_kparams = {sigma_1, sigma_2, L_1, L_2} -> the two axes; -9001 (and nothing launched) unless both sigma are finite and > 0, both
+// periods finite and >= 0 and one of them > 0 (none: that is GPK_KERNEL_ANISOTROPIC)
+inline int periodic_axes(gpk_handle h, const double* kp, PerArgs& k) {
+    constexpr double big = 1.79769313486231570e308, two_pi = 6.28318530717958647692;
+    for (int a = 0; a < 2; ++a) {
+        const double sigma = kp[a], L = kp[2 + a];
+        if (!(sigma > 0.0) || !(sigma <= big) || !(L >= 0.0) || !(L <= big))
+            return gpk_bad_arg(h, "assemble: the periodic kernel needs two finite length scales > 0 and two finite periods >= 0");
+        PerAxis& x = k.ax[a];
+        x.p = 2.0 / (sigma * sigma); x.L = L;
+        if (L > 0.0) { const double w = two_pi / L; x.w2 = w * w; x.pw = x.p / w; x.g = 2.0 * x.p / x.w2; }
+        else { x.w2 = 0.0; x.pw = 0.0; x.g = 0.5 * x.p; }
+    }
+    if (!(k.ax[0].L > 0.0) && !(k.ax[1].L > 0.0))
+        return gpk_bad_arg(h, "assemble: the periodic kernel with both periods 0 is the anisotropic Gaussian kernel: use its id");
+    return 0;
+}
+
 }  // namespace gpk_asm
+
+// Launches of gpk_assemble_periodic.hip on stream st: the interface of the Matern launches below, the axes in place of the order.
+void gpk_i_periodic_gram(int layout, bool pairs, int nt, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
+void gpk_i_periodic_test(int layout, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
+void gpk_i_periodic_cross(int layout, bool wide, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
+void gpk_i_periodic_prior(bool wide, hipStream_t st, const gpk_asm::PriorArgs& g, const gpk_asm::PerArgs& k);
+void gpk_i_periodic_extend(int layout, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
+void gpk_i_periodic_extend_fn(int layout, int mask, hipStream_t st, const gpk_asm::FnArgs& g, const gpk_asm::PerArgs& k);
+// value of <f_b, f_b> at d = 0 for the blocks of the layout: the table there is (1, 0, -p, 0, 3 p^2 + w^2 p) per axis
+void gpk_i_periodic_diag(int layout, const gpk_asm::PerArgs& k, double (&c)[4]);
 
 // Launches of gpk_assemble_matern.hip on stream st (m = matern_order(kernel), layout a valid id, the grids of the Gaussian kernels of
 // the same shape).  gram: pairs as pairs_eligible, nt = 1: non-temporal 16-byte stores (the write-through policies 2 / 3 of key 55: plain).

@@ -10,8 +10,9 @@ from . import _lib as _libmod
 from ._lib import GNProblemStruct, GpkError, load_library
 
 LAYOUT = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_u': 2, 'Darcy_a': 3}
-KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1, 'Matern52': 8, 'Matern72': 9, 'Matern92': 10}      # GPK_KERNEL_*
+KERNEL = {'Gaussian': 0, 'anisotropic_Gaussian': 1, 'Matern52': 8, 'Matern72': 9, 'Matern92': 10, 'periodic_Gaussian': 16}      # GPK_KERNEL_*
 MATERN = ('Matern52', 'Matern72', 'Matern92')     # nu = 5/2, 7/2, 9/2: the reference layouts only (assemble .. assemble_cross)
+PERIODIC = 'periodic_Gaussian'                    # (sigma_1, sigma_2, L_1, L_2), L_k = 0: axis k is not periodic; the reference layouts only
 NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
@@ -56,12 +57,17 @@ def kernel_params(kernel, kernel_parameter):
         if len(kp) not in (1, 2):
             raise ValueError(f'{kernel} needs one length scale or one per axis, got {len(kp)}')
         return (C.c_double * 2)(kp[0], kp[-1])
+    if kernel == PERIODIC:                                 # {sigma_1, sigma_2, L_1, L_2}
+        kp = [float(v) for v in np.atleast_1d(np.asarray(kernel_parameter, dtype=np.float64))]
+        if len(kp) != 4:
+            raise ValueError(f'{kernel} needs (sigma_1, sigma_2, L_1, L_2), got {len(kp)} value(s)')
+        return (C.c_double * 4)(*kp)
     raise ValueError(f'unknown kernel {kernel!r}')
 
 
 def require_gaussian_family(kernel, what):
     """The 3-D, boundary-functional and operator evaluators serve the Gaussian family only: say so before any device call."""
-    if kernel in MATERN:
+    if kernel in MATERN or kernel == PERIODIC:
         raise ValueError(f'{what}: the kernel {kernel!r} is available for the layouts Nonlinear_elliptic, Burgers, Eikonal and Darcy '
                          'only; the 3-D, boundary-functional and operator evaluators take Gaussian or anisotropic_Gaussian')
 

@@ -1,12 +1,15 @@
 #%%
 """Darcy-flow inverse problem -div(a grad u) = f: recover a from noisy observations of u, GP solver on an MI355X.
-Same command line as the reference's main_DarcyFlow2d.py (flags, defaults, --randomseed)."""
+Same command line as the reference's main_DarcyFlow2d.py (flags, defaults, --randomseed).
+--kernel periodic_Gaussian --kernel_parameter S1 S2 --period 1 0 (or 0 1): one periodic kernel for both fields and no boundary points on the
+faces of that axis.  The observations still come from the finite-difference solution with u = 0 on all four faces, which is not the
+periodic problem's solution: the errors printed under the flag measure the distance to that solution, not the method."""
 import argparse
 
 import numpy as onp
 from scipy.interpolate import griddata
 
-from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, report_test_residual, report_test_variance, report_posterior_samples, seed_from, solve_or_select, tensor_grid
+from _driver_common import add_gn_and_logs, add_kernel_and_sampling, figures_enabled, periodic_axes_of, report_test_residual, report_test_variance, report_posterior_samples, seed_from, solve_or_select, tensor_grid
 from reference_solver.FD_for_Darcy_flow import FD_Darcy_flow_2d
 from src.solver import solver_GP
 
@@ -40,6 +43,7 @@ def rms(a):
 def main(argv=None):
     cfg = parse(argv)
     seed_from(cfg)
+    periodic_axes_of(cfg)                                                # (checks that --kernel periodic_Gaussian and --period go together)
     show = figures_enabled(cfg)
     solver = solver_GP(cfg, PDE_type="Darcy_flow2d")
     solver.set_equation(bdy=lambda x1, x2: 0, rhs=source, domain=onp.array(UNIT_SQUARE))

@@ -12,12 +12,16 @@ default) is the equation above.  --bc works with either.
 tau(u): p0*exp(p1*u), p0*sinh(p1*u), p0*sin(p1*u) or p0*u + p1*u^2 + p2*u^3; the right-hand side is manufactured with the same tau, so
 every --operator / --bc combination works with every kind:
     python main_NonLinElliptic2d.py --nonlinearity exp --nl_params=-1,1 --nugget 1e-8          (Bratu)
-    python main_NonLinElliptic2d.py --nonlinearity sinh --nl_params=4,1 --bc robin --nugget 1e-8   (Poisson-Boltzmann)"""
+    python main_NonLinElliptic2d.py --nonlinearity sinh --nl_params=4,1 --bc robin --nugget 1e-8   (Poisson-Boltzmann)
+--kernel periodic_Gaussian --kernel_parameter S1 S2 --period L1 L2 (no counterpart in the reference) makes the solution periodic along the
+axes with L_k = 1 (0: not periodic) through a periodic kernel: no boundary points on the faces of that axis, and a manufactured solution
+that is periodic there (manufactured_periodic); with the Laplacian and Dirichlet data on the other faces only:
+    python main_NonLinElliptic2d.py --kernel periodic_Gaussian --kernel_parameter 0.2 0.2 --period 1 0 --nugget 1e-8 --GNsteps 6"""
 import argparse
 
 import numpy as onp
 
-from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, add_nonlinearity, nonlinearity_from, report_test_error,
+from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, add_nonlinearity, nonlinearity_from, periodic_axes_of, report_test_error,
                             report_test_residual, report_test_variance, report_posterior_samples, solve_forward, tensor_grid)
 
 UNIT_SQUARE = [[0, 1], [0, 1]]
@@ -53,6 +57,25 @@ def manufactured(alpha, m=None):
 
     def f(x1, x2):
         lap = -2 * pi ** 2 * onp.sin(pi * x1) * onp.sin(pi * x2) - 64 * pi ** 2 * onp.sin(4 * pi * x1) * onp.sin(4 * pi * x2)
+        return -lap + tau.tau(u(x1, x2))
+    return u, f
+
+
+def manufactured_periodic(periodic, alpha, m=None):
+    """u* and f = -Laplace(u*) + tau(u*) for a solution with period 1 along the axes of `periodic`: u* = a1 a2 + 2 b1 b2 with, per axis,
+    a = sin(2 pi x), b = cos(4 pi x) on a periodic axis (neither vanishes with all derivatives at the faces, so the periodicity is the
+    kernel's doing) and a = sin(pi x), b = sin(4 pi x) otherwise, as in manufactured()"""
+    pi = onp.pi
+    tau = reaction(alpha, m)
+    a = [(onp.sin, 2 * pi) if per else (onp.sin, pi) for per in periodic]
+    b = [(onp.cos, 4 * pi) if per else (onp.sin, 4 * pi) for per in periodic]
+
+    def u(x1, x2):
+        return a[0][0](a[0][1] * x1) * a[1][0](a[1][1] * x2) + 2 * b[0][0](b[0][1] * x1) * b[1][0](b[1][1] * x2)
+
+    def f(x1, x2):
+        lap = (-(a[0][1] ** 2 + a[1][1] ** 2) * a[0][0](a[0][1] * x1) * a[1][0](a[1][1] * x2)
+               - 2 * (b[0][1] ** 2 + b[1][1] ** 2) * b[0][0](b[0][1] * x1) * b[1][0](b[1][1] * x2))
         return -lap + tau.tau(u(x1, x2))
     return u, f
 
@@ -115,6 +138,11 @@ def main(argv=None):
     cfg = parse(argv)
     tau, cfg.nonlinearity = nonlinearity_from(cfg)                      # (None: alpha*u^m of --alpha / --m, the facade's default)
     u, f = manufactured(tau)
+    periodic = periodic_axes_of(cfg)
+    if any(periodic):
+        if cfg.operator != 'laplace' or cfg.bc != 'dirichlet':
+            raise SystemExit('--kernel periodic_Gaussian: with --operator laplace and --bc dirichlet only')
+        u, f = manufactured_periodic(periodic, tau)
     if cfg.operator != 'laplace':
         f = manufactured_operator_rhs(tau)
         cfg.operator = OPERATORS[cfg.operator]                           # the facade takes the callable (or 'laplace' / None: the Laplacian)

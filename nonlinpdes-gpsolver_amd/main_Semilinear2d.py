@@ -5,12 +5,14 @@
     python main_Semilinear2d.py --equation hamilton_jacobi --eps 0.5                 |grad u|^2 + u: viscous Hamilton-Jacobi
     python main_Semilinear2d.py --equation custom --nl_params=1,-1,0.5,1,1 --eps 0.2
 --nl_params=a1,a2,b,c1,c3 overrides the coefficients of any --equation.  The manufactured solution is u* = sin(pi x1) sin(pi x2) with f
-formed analytically.  Plain Gauss-Newton steps: keep --eps at 0.1 or above (convection-dominated settings do not converge)."""
+formed analytically.  Plain Gauss-Newton steps: keep --eps at 0.1 or above (convection-dominated settings do not converge).
+--kernel periodic_Gaussian --kernel_parameter S1 S2 --period L1 L2 (L_k = 1 or 0): periodic along the axes with L_k = 1, no boundary points
+on their faces; the manufactured solution has sin(2 pi x_k) + cos(2 pi x_k) / 2 in place of sin(pi x_k) there."""
 import argparse
 
 import numpy as onp
 
-from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, report_test_error, report_test_residual, report_test_variance,
+from _driver_common import (add_gn_and_logs, add_kernel_and_sampling, periodic_axes_of, report_test_error, report_test_residual, report_test_variance,
                             report_posterior_samples, solve_forward, tensor_grid)
 
 UNIT_SQUARE = [[0, 1], [0, 1]]
@@ -41,17 +43,25 @@ def coefficients_from(cfg):
     return params
 
 
-def manufactured(eps, nl):
-    """u* = sin(pi x1) sin(pi x2) and f = -eps Laplace(u*) + N(u*, grad u*) for the GradientNonlinearity nl"""
+def manufactured(eps, nl, periodic=(False, False)):
+    """u* = a(x1) a(x2) and f = -eps Laplace(u*) + N(u*, grad u*) for the GradientNonlinearity nl, with a(x) = sin(pi x), or on a periodic
+    axis a(x) = sin(2 pi x) + cos(2 pi x) / 2 (period 1, not zero at the faces)"""
     pi = onp.pi
 
+    def factor(per):
+        k = 2 * pi if per else pi
+        h = 0.5 if per else 0.0
+        return (lambda x: onp.sin(k * x) + h * onp.cos(k * x)), (lambda x: k * (onp.cos(k * x) - h * onp.sin(k * x))), k * k
+
+    (a1, da1, k1), (a2, da2, k2) = factor(periodic[0]), factor(periodic[1])
+
     def u(x1, x2):
-        return onp.sin(pi * x1) * onp.sin(pi * x2)
+        return a1(x1) * a2(x2)
 
     def f(x1, x2):
         us = u(x1, x2)
-        p, q = pi * onp.cos(pi * x1) * onp.sin(pi * x2), pi * onp.sin(pi * x1) * onp.cos(pi * x2)
-        return 2 * pi ** 2 * eps * us + nl.N(us, p, q)
+        p, q = da1(x1) * a2(x2), a1(x1) * da2(x2)
+        return (k1 + k2) * eps * us + nl.N(us, p, q)
     return u, f
 
 
@@ -60,7 +70,7 @@ def main(argv=None):
     cfg = parse(argv)
     nl = GradientNonlinearity.make(coefficients_from(cfg))
     cfg.nonlinearity = nl
-    u, f = manufactured(cfg.eps, nl)
+    u, f = manufactured(cfg.eps, nl, periodic_axes_of(cfg))
     solver, show = solve_forward(cfg, "Semilinear2d", u, f, UNIT_SQUARE, verbose=cfg.print_hist)
     Xd = solver.eqn.X_domain
     solver.collocation_pts_err(u(Xd[:, 0], Xd[:, 1]))                    # error on the collocation points

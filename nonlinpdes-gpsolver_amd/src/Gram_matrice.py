@@ -6,7 +6,7 @@ from ._runtime import get_context
 
 _LAYOUTS = {'Nonlinear_elliptic': ('Nonlinear_elliptic',), 'Burgers': ('Burgers',), 'Eikonal': ('Eikonal',),
             'Darcy_flow2d': ('Darcy_u', 'Darcy_a')}
-_KERNELS = ('Gaussian', 'anisotropic_Gaussian', 'Matern52', 'Matern72', 'Matern92')
+_KERNELS = ('Gaussian', 'anisotropic_Gaussian', 'Matern52', 'Matern72', 'Matern92', 'periodic_Gaussian')
 
 
 def Gram_matrix_assembly(X_domain, X_boundary, eqn='Nonlinear_elliptic', kernel='Gaussian', kernel_parameter=0.2):

@@ -23,11 +23,14 @@ class Darcy_flow2d(_GPEquation):
         self.domain = domain
 
     # ---- points: the first N_data collocation points carry the observations --------------------------------------
+    _periodic_axes = (False, False)   # set on an instance (solver_GP: cfg.period): sampled_pts() leaves the faces of a periodic axis out
+
     def sampled_pts(self, N_domain, N_boundary, N_data, sampled_type='random'):
+        kw = {'periodic': tuple(self._periodic_axes)} if any(self._periodic_axes) else {}
         if sampled_type == 'random':
-            X_domain, X_boundary = sampled_pts_rdm(N_domain, N_boundary, self.domain, time_dependent=False)
+            X_domain, X_boundary = sampled_pts_rdm(N_domain, N_boundary, self.domain, time_dependent=False, **kw)
         elif sampled_type == 'grid':
-            X_domain, X_boundary = sampled_pts_grid(N_domain, N_boundary, self.domain, time_dependent=False)
+            X_domain, X_boundary = sampled_pts_grid(N_domain, N_boundary, self.domain, time_dependent=False, **kw)
         else:
             raise UnboundLocalError("local variable 'X_domain' referenced before assignment")
         self._set_points(X_domain, X_boundary)

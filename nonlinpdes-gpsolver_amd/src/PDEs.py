@@ -63,6 +63,7 @@ class _GPEquation(object):
     _layout = None              # Gram layout name
     _system = None              # Gauss-Newton system name
     _time_dependent = False
+    _periodic_axes = (False, False)   # set on an instance (solver_GP: cfg.period): sampled_pts() leaves the faces of a periodic axis out
     _blocks_per_point = 1       # unknown groups per collocation point
     _dim = 2                    # columns of a point
     _structured_optin = True    # _problem() honours GPK_STRUCTURED
@@ -93,10 +94,11 @@ class _GPEquation(object):
         self._drop_device_state()
 
     def sampled_pts(self, N_domain, N_boundary, sampled_type='random'):
+        kw = {'periodic': tuple(self._periodic_axes)} if any(self._periodic_axes) else {}
         if sampled_type == 'random':
-            X_domain, X_boundary = sampled_pts_rdm(N_domain, N_boundary, self.domain, time_dependent=self._time_dependent)
+            X_domain, X_boundary = sampled_pts_rdm(N_domain, N_boundary, self.domain, time_dependent=self._time_dependent, **kw)
         elif sampled_type == 'grid':
-            X_domain, X_boundary = sampled_pts_grid(N_domain, N_boundary, self.domain, time_dependent=self._time_dependent)
+            X_domain, X_boundary = sampled_pts_grid(N_domain, N_boundary, self.domain, time_dependent=self._time_dependent, **kw)
         else:
             raise UnboundLocalError("local variable 'X_domain' referenced before assignment")
         self._set_points(X_domain, X_boundary)

@@ -191,3 +191,65 @@ class Matern72_kernel(Matern_kernel):
 class Matern92_kernel(Matern_kernel):
     def __init__(self):
         Matern_kernel.__init__(self, 4.5)
+
+
+# ---- periodic kernel ("Periodic kernel") ----------------------------------------------------------------------
+def _sincospi(x):
+    """(sin pi x, cos pi x) with exact argument reduction, as sincospi on the device: x is reduced to r in [-1, 1] modulo 2 and then to
+    t = r - q / 2 in [-1/4, 1/4], q the nearest half-integer count -- both steps exact in floating point -- so that the only rounding is
+    that of pi t and of the sine / cosine of a small argument."""
+    x = np.asarray(x, dtype=np.float64)
+    r = x - 2.0 * np.round(0.5 * x)
+    q = np.round(2.0 * r)
+    t = np.pi * (r - 0.5 * q)
+    s, c = np.sin(t), np.cos(t)
+    k = q.astype(np.int64) % 4
+    return np.choose(k, [s, c, -s, -c]), np.choose(k, [c, -s, -c, s])
+
+
+def _periodic_table(p, L, d):
+    """(h0..h4, z) of one axis with precision p and period L > 0 at d, h_m = (-1)^m kappa^(m) / kappa for
+    kappa(d) = exp(-(2 p / w^2) sin^2(w d / 2)), w = 2 pi / L, and z = sin(w d / 2): with s = (p / w) sin w d, c = p cos w d
+        h1 = s, h2 = s^2 - c, h3 = s (s^2 - 3 c - w^2), h4 = s^4 - 6 s^2 c + 3 c^2 - 4 w^2 s^2 + w^2 c.
+    At d = 0 the table is (1, 0, -p, 0, 3 p^2 + w^2 p), and it tends to the Hermite table as w -> 0."""
+    w = 2.0 * np.pi / L
+    sh, ch = _sincospi(d / L)
+    s = (p / w) * (2.0 * sh * ch)
+    c = p * (1.0 - 2.0 * sh * sh)
+    s2, w2 = s * s, w * w
+    return (1.0, s, s2 - c, s * (s2 - 3.0 * c - w2), s2 * (s2 - 6.0 * c - 4.0 * w2) + c * (3.0 * c + w2)), sh
+
+
+class Periodic_kernel(_ClosedFormKernel):
+    """Product over the two axes of kappa_k(d) = exp(-(2 p_k / w_k^2) sin^2(w_k d / 2)), p_k = 2 / sigma_k^2, w_k = 2 pi / L_k, on an axis
+    with period L_k > 0, and of the anisotropic Gaussian factor exp(-p_k d^2 / 2) on an axis with L_k = 0.  The last argument of every
+    method is (sigma_1, sigma_2, L_1, L_2).  Every method name of the Gaussian classes; the same closed form with the table of
+    _periodic_table in place of the Hermite table on a periodic axis -- what csrc/gpk_assemble_periodic.hip computes per point pair."""
+
+    @staticmethod
+    def _axes(param):
+        v = np.atleast_1d(np.asarray(param, dtype=np.float64))
+        if v.size != 4 or not np.all(np.isfinite(v)) or not np.all(v[:2] > 0) or not np.all(v[2:] >= 0) or not np.any(v[2:] > 0):
+            raise ValueError(f'Periodic_kernel: (sigma_1, sigma_2, L_1, L_2) = {param!r}: two finite length scales > 0 and two finite '
+                             'periods >= 0, not both 0 (that kernel is Anisotropic_Gaussian_kernel)')
+        return [(2.0 / float(v[k]) ** 2, float(v[2 + k])) for k in range(2)]
+
+    def _eval(self, fx, fy, x1, x2, y1, y2, param):
+        d = (np.asarray(x1, dtype=np.float64) - np.asarray(y1, dtype=np.float64),
+             np.asarray(x2, dtype=np.float64) - np.asarray(y2, dtype=np.float64))
+        tables, expo = [], 0.0
+        for (p, L), dk in zip(self._axes(param), d):
+            if L > 0.0:
+                h, z = _periodic_table(p, L, dk)
+                expo = expo + (2.0 * p / (2.0 * np.pi / L) ** 2) * z * z
+            else:
+                h = _hermite(p, dk)
+                expo = expo + 0.5 * p * dk * dk
+            tables.append(h)
+        a, b = tables
+        total = 0.0
+        for (a1, a2) in fx:
+            for (b1, b2) in fy:
+                term = a[a1 + b1] * b[a2 + b2]
+                total = total - term if (a1 + a2) & 1 else total + term
+        return total * np.exp(-expo)

@@ -178,6 +178,25 @@ def _say(enabled, *keys, **fmt):
             print(_LOG[k].format(**fmt))
 
 
+def _periods_of(c, domain):
+    """cfg.period = (L_1, L_2) as two floats, or None (absent, None, or both 0); L_k = 0: axis k is not periodic.  A period other than
+    the width of the domain on its axis is refused: the solution would be asked to repeat inside the domain, or not to close at its
+    faces."""
+    period = getattr(c, 'period', None)
+    if period is None:
+        return None
+    L = [float(v) for v in onp.atleast_1d(onp.asarray(period, dtype=onp.float64))]
+    if len(L) != 2 or len(domain) != 2:
+        raise ValueError(f'cfg.period {period!r}: one period per axis of a two-dimensional domain (0: the axis is not periodic)')
+    if not any(L):
+        return None
+    for k in range(2):
+        width = float(domain[k][1]) - float(domain[k][0])
+        if L[k] != 0.0 and L[k] != width:
+            raise ValueError(f'cfg.period: the period {L[k]} of axis {k + 1} differs from the width {width} of the domain on that axis')
+    return L
+
+
 def _as_vector(truth, n):
     """the user's truth as n float64 values (a scalar truth -- e.g. 0 -- is broadcast like under jnp)"""
     t = onp.asarray(truth, dtype=onp.float64)
@@ -197,6 +216,20 @@ class solver_GP(object):
             return
         make, header, params = _EQUATIONS[self.PDE_type]
         self.eqn = make(self.config, bdy=bdy, rhs=rhs, domain=domain)
+        # cfg.period = (L_1, L_2): the periodic kernel's periods -- auto_sample() leaves the faces of a periodic axis out, and the
+        # periods join the two length scales of cfg.kernel_parameter
+        periods = _periods_of(self.config, domain)
+        if periods is not None:
+            if self.config.kernel != 'periodic_Gaussian':
+                raise ValueError(f"cfg.period needs cfg.kernel = 'periodic_Gaussian', got {self.config.kernel!r}")
+            self.eqn._periodic_axes = (periods[0] > 0.0, periods[1] > 0.0)
+            kp = [float(v) for v in onp.atleast_1d(onp.asarray(self.config.kernel_parameter, dtype=onp.float64))]
+            if len(kp) == 1:
+                kp = kp * 2
+            if len(kp) == 2:
+                self.config.kernel_parameter = kp + periods
+            elif len(kp) != 4 or kp[2:] != periods:
+                raise ValueError(f'cfg.kernel_parameter {self.config.kernel_parameter!r}: (sigma_1, sigma_2), or with the periods of cfg.period appended')
         if print_option:
             print(_LOG['start'])
             for line in header(self.config):
