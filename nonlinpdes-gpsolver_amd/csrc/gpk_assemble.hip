@@ -15,10 +15,11 @@
 // point is wave-uniform (scalar loads, no LDS needed: 16 B per point).  No symmetry trick: the ALU cost per pair
 // (~1 exp + ~60 flops) is >10x below the HBM write time of its 32..128 output bytes.
 //
-// The functional tables, the Hermite evaluation (hermite_plain), the frame of the extension kernel, the 16-byte store and the host side
-// of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.  The layouts, the argument structs and
-// the layout dispatch are shared with the Matern family and the periodic kernel of these layouts (gpk_assemble_matern.hip, gpk_assemble_periodic.hip, launched from the entry points below): gpk_assemble_ref.h.
-#include "gpk_assemble_ref.h"
+// The kernels are the frames of gpk_assemble_frames.h, instantiated here for the Gaussian policy below; the Matern family and the periodic
+// kernel instantiate them in gpk_assemble_matern.hip and gpk_assemble_periodic.hip, and the entry points below launch whichever family
+// the kernel id names through its table (gpk_assemble_ref.h).  The functional tables, the Hermite evaluation (hermite_plain), the
+// 16-byte store and the host side of a call (precisions, nugget, timing) are shared with the other evaluators: gpk_assemble_common.h.
+#include "gpk_assemble_frames.h"
 
 using namespace gpk_asm;
 
@@ -41,291 +42,48 @@ __host__ __device__ __forceinline__ double pair_coeff(const double (&a)[5], cons
     return s;
 }
 
+// The Gaussian and the anisotropic Gaussian kernel: the Hermite tables of the two axes and kappa, an entry is pair_coeff(a, b) kappa.
+// No pragma anywhere: the compiler may contract across these functions and the frames, as it always has here.
+struct Gauss {
+    struct State { double a[5], b[5], e; };
+    static constexpr bool write_through = true;      // all four store policies of key 55 (measured here)
+
+    __host__ __device__ __forceinline__ static void eval(double p1, double p2, double d1, double d2, State& s) {
+        s.e = exp(-0.5 * (p1 * d1 * d1 + p2 * d2 * d2));
+        hermite_plain(p1, d1, s.a);
+        hermite_plain(p2, d2, s.b);
+    }
+    // both kappa first, then the tables: the order of the two-point kernels (register assignment follows it)
+    __device__ __forceinline__ static void eval2(double p1, double p2, double d1a, double d2a, State& s0, double d1b, double d2b, State& s1) {
+        s0.e = exp(-0.5 * (p1 * d1a * d1a + p2 * d2a * d2a));
+        s1.e = exp(-0.5 * (p1 * d1b * d1b + p2 * d2b * d2b));
+        hermite_plain(p1, d1a, s0.a); hermite_plain(p2, d2a, s0.b);
+        hermite_plain(p1, d1b, s1.a); hermite_plain(p2, d2b, s1.b);
+    }
+    template <int FX, int FY>
+    __host__ __device__ __forceinline__ static double entry(const State& s) { return pair_coeff<FX, FY>(s.a, s.b) * s.e; }
+    // the extension kernels sum coefficient * c over the blocks and multiply by kappa once
+    template <int FX, int FY>
+    __device__ __forceinline__ static double scaled(const State& s, double c) { return pair_coeff<FX, FY>(s.a, s.b) * c; }
+    __device__ __forceinline__ static double weigh(const State& s, double v) { return v * s.e; }
+    __device__ __forceinline__ static double weigh_fn(const State& s, double v) { return v * s.e; }
+    // kappa with the one fma written out (kappa2_fma): even in d to the bit, exp(-0) = 1 on the diagonal
+    __device__ __forceinline__ static double prior(double p1, double p2, double d1, double d2) {
+        double a[5], b[5];
+        hermite_plain(p1, d1, a);
+        hermite_plain(p2, d2, b);
+        return pair_coeff<F_DELTA, F_DELTA>(a, b) * kappa2_fma(p1, p2, d1, d2);
+    }
+    static void at_zero(double p1, double p2, State& s) { eval(p1, p2, 0.0, 0.0, s); }
+
+    template <class F> static void with(const KernelParams&, F&& f) { f(Gauss{}); }
+};
+
 __global__ void pack_points_kernel(const double* __restrict__ Xd, int Nd, const double* __restrict__ Xb, int Nb,
                                    double* __restrict__ px, double* __restrict__ py) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < Nd) { px[i] = Xd[2 * i]; py[i] = Xd[2 * i + 1]; }
     else if (i < Nd + Nb) { px[i] = Xb[2 * (i - Nd)]; py[i] = Xb[2 * (i - Nd) + 1]; }
-}
-
-template <int L, int BI, int BJ>
-__device__ __forceinline__ void store_block(const AsmArgs& g, int p, int q, const double (&a)[5], const double (&b)[5], double e) {
-    if (q < g.size[BJ]) {
-        double v = pair_coeff<Lay<L>::f[BI], Lay<L>::f[BJ]>(a, b) * e;
-        if (BI == BJ && p == q) v += g.nug[BI];
-        g.out[(long)(g.off[BI] + p) * g.ld + g.off[BJ] + q] = v;
-    }
-}
-
-template <int L, int BI>
-__device__ __forceinline__ void store_row(const AsmArgs& g, int p, int q, const double (&a)[5], const double (&b)[5], double e) {
-    if (p < g.size[BI]) {                               // wave-uniform
-        store_block<L, BI, 0>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 1) store_block<L, BI, 1>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 2) store_block<L, BI, 2>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 3) store_block<L, BI, 3>(g, p, q, a, b, e);
-    }
-}
-
-// Two column points per lane, one 16-byte store per (row functional, column functional, row point): a wave writes 1 KB contiguous
-// per store instruction and issues half as many of them.  Needs every block offset, the leading dimension and the base address to
-// be even multiples of 8 bytes (checked by the launcher; otherwise the one-point-per-lane kernel below runs).  NT: the store policy of
-// store2 (gpk_tune key 55; all four are instantiated here, see the table at gpk_assemble below).
-
-template <int L, int BI, int BJ, int NT>
-__device__ __forceinline__ void store_block2(const AsmArgs& g, int p, int q, const double (&a0)[5], const double (&b0)[5], double e0,
-                                             const double (&a1)[5], const double (&b1)[5], double e1) {
-    if (q < g.size[BJ]) {                                            // (sizes are even here: q and q + 1 are both inside or both outside)
-        double v0 = pair_coeff<Lay<L>::f[BI], Lay<L>::f[BJ]>(a0, b0) * e0;
-        double v1 = pair_coeff<Lay<L>::f[BI], Lay<L>::f[BJ]>(a1, b1) * e1;
-        if (BI == BJ) { if (p == q) v0 += g.nug[BI]; if (p == q + 1) v1 += g.nug[BI]; }
-        store2<NT>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q, v0, v1);
-    }
-}
-
-template <int L, int BI, int NT>
-__device__ __forceinline__ void store_row2(const AsmArgs& g, int p, int q, const double (&a0)[5], const double (&b0)[5], double e0,
-                                           const double (&a1)[5], const double (&b1)[5], double e1) {
-    if (p < g.size[BI]) {                               // wave-uniform
-        store_block2<L, BI, 0, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 1) store_block2<L, BI, 1, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 2) store_block2<L, BI, 2, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 3) store_block2<L, BI, 3, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-    }
-}
-
-template <int L, int NT>
-__global__ __launch_bounds__(256) void assemble2_kernel(AsmArgs g) {
-    const int q = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = q < g.M;                                       // (M even: q + 1 < M as well)
-    const double y1a = live ? g.px[q] : 0.0, y2a = live ? g.py[q] : 0.0;
-    const double y1b = live ? g.px[q + 1] : 0.0, y2b = live ? g.py[q + 1] : 0.0;
-    const int p0 = blockIdx.y * TP;
-    const int pend = min(p0 + TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double x1 = g.px[p], x2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        const double d1a = x1 - y1a, d2a = x2 - y2a, d1b = x1 - y1b, d2b = x2 - y2b;
-        const double e0 = exp(-0.5 * (g.p1 * d1a * d1a + g.p2 * d2a * d2a));
-        const double e1 = exp(-0.5 * (g.p1 * d1b * d1b + g.p2 * d2b * d2b));
-        double a0[5], b0[5], a1[5], b1[5];
-        hermite_plain(g.p1, d1a, a0); hermite_plain(g.p2, d2a, b0);
-        hermite_plain(g.p1, d1b, a1); hermite_plain(g.p2, d2b, b1);
-        store_row2<L, 0, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 1) store_row2<L, 1, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 2) store_row2<L, 2, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 3) store_row2<L, 3, NT>(g, p, q, a0, b0, e0, a1, b1, e1);
-    }
-}
-
-template <int L>
-__global__ __launch_bounds__(256) void assemble_kernel(AsmArgs g) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const bool live = q < g.M;
-    const double y1 = live ? g.px[q] : 0.0, y2 = live ? g.py[q] : 0.0;
-    const int p0 = blockIdx.y * TP;
-    const int pend = min(p0 + TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double x1 = g.px[p], x2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        const double d1 = x1 - y1, d2 = x2 - y2;
-        const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
-        double a[5], b[5];
-        hermite_plain(g.p1, d1, a);
-        hermite_plain(g.p2, d2, b);
-        store_row<L, 0>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 1) store_row<L, 1>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 2) store_row<L, 2>(g, p, q, a, b, e);
-        if (Lay<L>::nb > 3) store_row<L, 3>(g, p, q, a, b, e);
-    }
-}
-
-// test rows: functional delta at the test point, column functionals of the layout
-template <int L, int BJ>
-__device__ __forceinline__ void store_test(const AsmArgs& g, int t, int q, const double (&a)[5], const double (&b)[5], double e) {
-    if (q < g.size[BJ]) g.out[(long)t * g.ld + g.off[BJ] + q] = pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a, b) * e;
-}
-
-template <int L>
-__global__ __launch_bounds__(256) void assemble_test_kernel(AsmArgs g) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= g.M) return;
-    const double y1 = g.px[q], y2 = g.py[q];
-    const int t0 = blockIdx.y * TP;
-    const int tend = min(t0 + TP, g.Nt);
-    for (int t = t0; t < tend; ++t) {
-        const double d1 = g.tx[2 * t] - y1, d2 = g.tx[2 * t + 1] - y2;
-        const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
-        double a[5], b[5];
-        hermite_plain(g.p1, d1, a);
-        hermite_plain(g.p2, d2, b);
-        store_test<L, 0>(g, t, q, a, b, e);
-        if (Lay<L>::nb > 1) store_test<L, 1>(g, t, q, a, b, e);
-        if (Lay<L>::nb > 2) store_test<L, 2>(g, t, q, a, b, e);
-        if (Lay<L>::nb > 3) store_test<L, 3>(g, t, q, a, b, e);
-    }
-}
-
-// cross-covariance columns (gpk_assemble_cross): the entries of assemble_test_kernel, transposed -- out[(off[BJ] + p) * ld + t] for the
-// column point p of block BJ and the test point t.  Lanes run along t, two test points per lane (t, t + 1): for a fixed (block, column
-// point) a wave stores 1 KB contiguous with the 16-byte store (WIDE: base and ld even, Nt even), or the same two values as two
-// 8-byte stores (any alignment, odd Nt).  One kernel body for both: the values are the same bits either way.  The column point is
-// wave-uniform (scalar loads), and one exp + one pair of Hermite evaluations per point pair feeds every block of the layout.
-template <int L, int BJ, bool WIDE>
-__device__ __forceinline__ void store_cross(const AsmArgs& g, int p, int t, const double (&a0)[5], const double (&b0)[5], double e0,
-                                            const double (&a1)[5], const double (&b1)[5], double e1) {
-    if (p < g.size[BJ]) {                               // wave-uniform
-        const double v0 = pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a0, b0) * e0;
-        const double v1 = pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a1, b1) * e1;
-        double* const dst = g.out + (long)(g.off[BJ] + p) * g.ld + t;
-        if constexpr (WIDE) store2<0>(dst, v0, v1);
-        else { dst[0] = v0; if (t + 1 < g.Nt) dst[1] = v1; }
-    }
-}
-
-template <int L, bool WIDE>
-__global__ __launch_bounds__(256) void assemble_cross_kernel(AsmArgs g) {
-    const int t = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = t < g.Nt;
-    const int tb = min(t + 1, g.Nt - 1);                // odd Nt: the last lane computes its point twice and stores it once
-    const double x1a = live ? g.tx[2 * t] : 0.0, x2a = live ? g.tx[2 * t + 1] : 0.0;
-    const double x1b = live ? g.tx[2 * tb] : 0.0, x2b = live ? g.tx[2 * tb + 1] : 0.0;
-    const int p0 = blockIdx.y * CROSS_TP;
-    const int pend = min(p0 + CROSS_TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double y1 = g.px[p], y2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        const double d1a = x1a - y1, d2a = x2a - y2, d1b = x1b - y1, d2b = x2b - y2;
-        const double e0 = exp(-0.5 * (g.p1 * d1a * d1a + g.p2 * d2a * d2a));
-        const double e1 = exp(-0.5 * (g.p1 * d1b * d1b + g.p2 * d2b * d2b));
-        double a0[5], b0[5], a1[5], b1[5];
-        hermite_plain(g.p1, d1a, a0); hermite_plain(g.p2, d2a, b0);
-        hermite_plain(g.p1, d1b, a1); hermite_plain(g.p2, d2b, b1);
-        store_cross<L, 0, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 1) store_cross<L, 1, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 2) store_cross<L, 2, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
-        if (Lay<L>::nb > 3) store_cross<L, 3, WIDE>(g, p, t, a0, b0, e0, a1, b1, e1);
-    }
-}
-
-// prior between two point sets (gpk_assemble_prior): out[i * ld + j] = k(xa_i, xb_j), the value functional on both sides.  The shape of
-// assemble_cross_kernel: lanes along j, two columns per lane (16-byte store when WIDE, the same two values as 8-byte stores otherwise),
-// the row point wave-uniform (scalar loads), one exp per pair, a workgroup owns 512 columns x CROSS_TP rows.  Write-bound: 8 na nb bytes.
-// kappa is even in d and every entry is computed from its own d = xa_i - xb_j, with the one fma written out (kappa2_fma): the two
-// columns of a lane and the two triangles of a square call (xa == xb) go through the same roundings, so out[i][j] and out[j][i] are
-// the same bits and the diagonal is exp(-0) = 1.
-__device__ __forceinline__ double prior_value(double p1, double p2, double d1, double d2) {
-    double a[5], b[5];
-    hermite_plain(p1, d1, a);
-    hermite_plain(p2, d2, b);
-    return pair_coeff<F_DELTA, F_DELTA>(a, b) * kappa2_fma(p1, p2, d1, d2);
-}
-
-template <bool WIDE>
-__global__ __launch_bounds__(256) void assemble_prior_kernel(PriorArgs g) {
-    const int j = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = j < g.nb;
-    const int jb = min(j + 1, g.nb - 1);                // odd nb: the last lane computes its point twice and stores it once
-    const double y1a = live ? g.xb[2 * j] : 0.0, y2a = live ? g.xb[2 * j + 1] : 0.0;
-    const double y1b = live ? g.xb[2 * jb] : 0.0, y2b = live ? g.xb[2 * jb + 1] : 0.0;
-    const int i0 = blockIdx.y * CROSS_TP;
-    const int iend = min(i0 + CROSS_TP, g.na);
-    for (int i = i0; i < iend; ++i) {
-        const double x1 = g.xa[2 * i], x2 = g.xa[2 * i + 1];   // uniform address -> scalar loads
-        if (!live) continue;
-        const double v0 = prior_value(g.p1, g.p2, x1 - y1a, x2 - y2a);
-        const double v1 = prior_value(g.p1, g.p2, x1 - y1b, x2 - y2b);
-        double* const dst = g.out + (long)i * g.ld + j;
-        if constexpr (WIDE) store2<0>(dst, v0, v1);
-        else { dst[0] = v0; if (j + 1 < g.nb) dst[1] = v1; }
-    }
-}
-
-template <int L, int BJ>
-__device__ __forceinline__ double acc_test(const AsmArgs& g, int q, const double (&a)[5], const double (&b)[5]) {
-    return (q < g.size[BJ]) ? pair_coeff<F_DELTA, Lay<L>::f[BJ]>(a, b) * g.coeff[g.off[BJ] + q] : 0.0;
-}
-
-// out[t] = sum_c Theta_test[t, c] * coeff[c]; one workgroup per test point, lanes stride over column points.
-template <int L>
-__global__ __launch_bounds__(256) void extend_kernel(AsmArgs g) {
-    __shared__ double red[4];
-    const int t = blockIdx.x;
-    const double x1 = g.tx[2 * t], x2 = g.tx[2 * t + 1];
-    double s = 0.0;
-    for (int q = threadIdx.x; q < g.M; q += 256) {
-        const double d1 = x1 - g.px[q], d2 = x2 - g.py[q];
-        const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
-        double a[5], b[5];
-        hermite_plain(g.p1, d1, a);
-        hermite_plain(g.p2, d2, b);
-        double v = acc_test<L, 0>(g, q, a, b);
-        if (Lay<L>::nb > 1) v += acc_test<L, 1>(g, q, a, b);
-        if (Lay<L>::nb > 2) v += acc_test<L, 2>(g, q, a, b);
-        if (Lay<L>::nb > 3) v += acc_test<L, 3>(g, q, a, b);
-        s += v * e;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) g.out[t] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ---- multi-functional extension (DESIGN.md §K "Row functionals of the extension") ------------------------------------------------
-// out[k][t] = sum_b sum_q pair_coeff<F_k, f[b]>(h(p1,d1), h(p2,d2)) kappa(d) c[off_b + q], d = x_t - y_q, F_k over the functionals of
-// MASK (bit F = functional F: delta, d1, d2, d2^2, Laplacian; the GPK_FN_* bits of gpk.h).  Every row functional has per-axis order
-// <= 2 and so has every column functional: the pair needs h0..h4 only, and ONE exp + one pair of Hermite evaluations feeds all of them.
-// Mapping: a workgroup owns FN_TT test points (wave-uniform: scalar loads) and its 256 lanes stride over the column points as in
-// extend_kernel; each column point's coordinates and its nb coefficient slices are loaded once and serve all FN_TT test points, and each
-// lane keeps FN_TT x popcount(MASK) accumulators.  Points, zeroing and reduction: the frame of gpk_assemble_common.h.
-// sum_b pair_coeff<F, f[b]> c[b] (c[b] = 0 outside block b, as acc_test in extend_kernel)
-template <int L, int F>
-__device__ __forceinline__ double fn_sum(const double (&a)[5], const double (&b)[5], const double (&c)[4]) {
-    double v = pair_coeff<F, Lay<L>::f[0]>(a, b) * c[0];
-    if (Lay<L>::nb > 1) v += pair_coeff<F, Lay<L>::f[1]>(a, b) * c[1];
-    if (Lay<L>::nb > 2) v += pair_coeff<F, Lay<L>::f[2]>(a, b) * c[2];
-    if (Lay<L>::nb > 3) v += pair_coeff<F, Lay<L>::f[3]>(a, b) * c[3];
-    return v;
-}
-
-template <int L, int MASK, int F>
-__device__ __forceinline__ void fn_acc(double (&s)[fn_popc(MASK)], const double (&a)[5], const double (&b)[5], const double (&c)[4], double e) {
-    if ((MASK >> F) & 1) s[fn_row(MASK, F)] += fn_sum<L, F>(a, b, c) * e;
-}
-
-template <int L, int MASK>
-__global__ __launch_bounds__(256) void extend_fn_kernel(FnArgs g) {
-    constexpr int NF = fn_popc(MASK);
-    const int t0 = blockIdx.x * FN_TT;
-    double x1[FN_TT], x2[FN_TT], s[FN_TT][NF];
-    GPK_FN_LOAD_POINTS2(x1, x2, g.tx, t0, g.Nt);
-    fn_zero(s);
-    for (int q = threadIdx.x; q < g.M; q += 256) {
-        const double y1 = g.px[q], y2 = g.py[q];
-        double c[4];
-#pragma unroll
-        for (int bk = 0; bk < 4; ++bk) c[bk] = (bk < Lay<L>::nb && q < g.size[bk]) ? g.coeff[g.off[bk] + q] : 0.0;
-#pragma unroll
-        for (int i = 0; i < FN_TT; ++i) {
-            const double d1 = x1[i] - y1, d2 = x2[i] - y2;
-            const double e = exp(-0.5 * (g.p1 * d1 * d1 + g.p2 * d2 * d2));
-            double a[5], b[5];
-            hermite_plain(g.p1, d1, a);
-            hermite_plain(g.p2, d2, b);
-            fn_acc<L, MASK, F_DELTA>(s[i], a, b, c, e);
-            fn_acc<L, MASK, F_D1>(s[i], a, b, c, e);
-            fn_acc<L, MASK, F_D2>(s[i], a, b, c, e);
-            fn_acc<L, MASK, F_DD2>(s[i], a, b, c, e);
-            fn_acc<L, MASK, F_LAP>(s[i], a, b, c, e);
-        }
-    }
-    GPK_FN_REDUCE_STORE(s, NF, t0, g.Nt, g.out, g.ldo);
-}
-
-// one instantiation per (layout, mask)
-template <int L>
-void launch_extend_fn(int mask, int grid, hipStream_t st, const FnArgs& g) {
-    with_mask<31>(mask, [&](auto m) { extend_fn_kernel<L, decltype(m)::value><<<grid, 256, 0, st>>>(g); });
 }
 
 // r = residual of the equation at each test point from the extension's rows: the relations the Gauss-Newton systems eliminate
@@ -372,17 +130,14 @@ __global__ __launch_bounds__(256) void pde_residual_sl_kernel(double eps, SlCoef
 template <int L> constexpr int lay_size(int b, int Nd, int Nb) { return b < Lay<L>::nb ? (Lay<L>::db[b] ? Nd + Nb : Nd) : 0; }
 template <int L> constexpr int lay_N(int Nd, int Nb) { return lay_size<L>(0, Nd, Nb) + lay_size<L>(1, Nd, Nb) + lay_size<L>(2, Nd, Nb) + lay_size<L>(3, Nd, Nb); }
 
-// precisions, block offsets / sizes and the packed points: the fields AsmArgs and FnArgs share (the others are the caller's); the axes
-// of the periodic kernel
+// the family and its parameters, block offsets / sizes and the packed points: the fields AsmArgs and FnArgs share (the others are the
+// caller's)
 template <class Args>
-int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp, const double* Xd, int Nd, const double* Xb, int Nb,
-                PerArgs& per) {
+int fill_common(gpk_handle h, Args& g, KernelParams& k, int layout, int kernel, const double* kp, const double* Xd, int Nd,
+                const double* Xb, int Nb) {
     if (Nd <= 0 || Nb < 0 || !kp || !Xd) return gpk_bad_arg(h, "assemble: sizes/pointers");
-    double p[2];
-    if (matern_order(kernel)) GPK_TRY(matern_scales(h, kp, p));      // (the Matern family: inverse length scales)
-    else if (kernel == GPK_KERNEL_PERIODIC) { GPK_TRY(periodic_axes(h, kp, per)); p[0] = per.ax[0].p; p[1] = per.ax[1].p; }   // (per: read by the periodic kernels only)
-    else GPK_TRY(precisions(h, "assemble: kernel id", kernel, kp, 2, p));
-    g.p1 = p[0]; g.p2 = p[1];
+    GPK_TRY(kernel_params(h, "assemble: kernel id", kernel, kp, k));
+    g.p1 = k.p[0]; g.p2 = k.p[1];
     const bool known = with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         int o = 0;
@@ -399,38 +154,24 @@ int fill_common(gpk_handle h, Args& g, int layout, int kernel, const double* kp,
     return 0;
 }
 
-// value of <f, f> at d = 0 (SURVEY §8a-K last column): makes the adaptive trace ratios analytic
-template <int L> void diag_values(double p1, double p2, double (&c)[4]) {
-    double a[5], b[5];
-    hermite_plain(p1, 0.0, a);
-    hermite_plain(p2, 0.0, b);
-    c[0] = pair_coeff<Lay<L>::f[0], Lay<L>::f[0]>(a, b);
-    c[1] = pair_coeff<Lay<L>::f[1], Lay<L>::f[1]>(a, b);
-    c[2] = pair_coeff<Lay<L>::f[2], Lay<L>::f[2]>(a, b);
-    c[3] = pair_coeff<Lay<L>::f[3], Lay<L>::f[3]>(a, b);
-}
-
 }  // namespace
 
+const Family gpk_i_family_gauss = family_of<Gauss>();
 
 extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* kp, const double* Xd, int Nd,
                             const double* Xb, int Nb, double nugget, int nugget_type, double* Theta, int ld,
                             double* ratios) {
     if (!h || !Theta) return GPK_ERR_ARG;
     AsmArgs g{};
-    PerArgs per{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
-    const int matern = matern_order(kernel);                         // the kernel family is chosen here, on the host: 0 = Gaussian
-    const bool periodic = kernel == GPK_KERNEL_PERIODIC;
+    KernelParams k;
+    GPK_TRY(fill_common(h, g, k, layout, kernel, kp, Xd, Nd, Xb, Nb));
     int nb = 0, N = 0;
-    double c[4] = {0, 0, 0, 0};
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         nb = Lay<L>::nb; N = lay_N<L>(Nd, Nb);
-        if (!matern && !periodic) diag_values<L>(g.p1, g.p2, c);
     });
-    if (matern) gpk_i_matern_diag(matern, layout, g.p1, g.p2, c);
-    if (periodic) gpk_i_periodic_diag(layout, per, c);
+    double c[4] = {0, 0, 0, 0};
+    k.family->diag(layout, k, c);
     if (ld < N) return gpk_bad_arg(h, "assemble: ld < N");
     // ratio_k = trace(block k) / trace(last block)   (src/PDEs.py:62-66, 256-262, 397-402; IP.py:72-87)
     double r[4] = {0, 0, 0, 1.0};
@@ -443,19 +184,7 @@ extern "C" int gpk_assemble(gpk_handle h, int layout, int kernel, const double* 
     const bool pairs = pairs_eligible(h, Theta, ld, g.M, g.size[0], g.size[1], g.size[2], g.size[3]);   // (even sizes: even offsets)
     TimedLaunch timed(h);
     GPK_TRY(timed.start());
-    if (matern) gpk_i_matern_gram(matern, layout, pairs, h->tune.asm_nt, h->stream, g);
-    else if (periodic) gpk_i_periodic_gram(layout, pairs, h->tune.asm_nt, h->stream, g, per);
-    else with_layout(layout, [&](auto l) {
-        constexpr int L = decltype(l)::value;
-        const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP)), grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
-        if (!pairs) assemble_kernel<L><<<grid, 256, 0, h->stream>>>(g);
-        else switch (h->tune.asm_nt) {
-            case 1: assemble2_kernel<L, 1><<<grid2, 256, 0, h->stream>>>(g); break;
-            case 2: assemble2_kernel<L, 2><<<grid2, 256, 0, h->stream>>>(g); break;
-            case 3: assemble2_kernel<L, 3><<<grid2, 256, 0, h->stream>>>(g); break;
-            default: assemble2_kernel<L, 0><<<grid2, 256, 0, h->stream>>>(g); break;
-        }
-    });
+    k.family->gram(layout, pairs, h->tune.asm_nt, h->stream, g, k);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -466,16 +195,13 @@ extern "C" int gpk_assemble_test(gpk_handle h, int layout, int kernel, const dou
     if (!out || !Xt) return gpk_bad_arg(h, "assemble_test: pointers");
     if (Nt <= 0) return gpk_bad_arg(h, "assemble_test: Nt <= 0");
     AsmArgs g{};
-    PerArgs per{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
+    KernelParams k;
+    GPK_TRY(fill_common(h, g, k, layout, kernel, kp, Xd, Nd, Xb, Nb));
     int N = 0;
     with_layout(layout, [&](auto l) { N = lay_N<decltype(l)::value>(Nd, Nb); });
     if (ld < N) return gpk_bad_arg(h, "assemble_test: ld < N");      // (rows would overlap and the last one leave the Nt x ld region)
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
-    const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(Nt, TP));
-    if (const int matern = matern_order(kernel)) gpk_i_matern_test(matern, layout, h->stream, g);
-    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_test(layout, h->stream, g, per);
-    else with_layout(layout, [&](auto l) { assemble_test_kernel<decltype(l)::value><<<grid, 256, 0, h->stream>>>(g); });
+    k.family->test(layout, h->stream, g, k);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -489,18 +215,11 @@ extern "C" int gpk_assemble_cross(gpk_handle h, int layout, int kernel, const do
     if (Nt <= 0) return gpk_bad_arg(h, "assemble_cross: Nt <= 0");
     if (ld < Nt) return gpk_bad_arg(h, "assemble_cross: ld < Nt");
     AsmArgs g{};
-    PerArgs per{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
+    KernelParams k;
+    GPK_TRY(fill_common(h, g, k, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = ld; g.tx = Xt; g.Nt = Nt;
     const bool wide = pairs_eligible(h, out, ld, Nt);
-    const dim3 grid(gpk_ceil_div(gpk_ceil_div(Nt, 2), 256), gpk_ceil_div(g.M, CROSS_TP));
-    if (const int matern = matern_order(kernel)) gpk_i_matern_cross(matern, layout, wide, h->stream, g);
-    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_cross(layout, wide, h->stream, g, per);
-    else with_layout(layout, [&](auto l) {                           // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
-        constexpr int L = decltype(l)::value;
-        if (wide) assemble_cross_kernel<L, true><<<grid, 256, 0, h->stream>>>(g);
-        else assemble_cross_kernel<L, false><<<grid, 256, 0, h->stream>>>(g);
-    });
+    k.family->cross(layout, wide, h->stream, g, k);                  // (not timed: gpk_prof_read_assembly keeps reporting the Gram launch)
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -514,20 +233,12 @@ extern "C" int gpk_assemble_prior(gpk_handle h, int kernel, const double* kp, co
     if (nb <= 0) return gpk_bad_arg(h, "assemble_prior: nb <= 0");
     if (ld < nb) return gpk_bad_arg(h, "assemble_prior: ld < nb");
     PriorArgs g{};
-    double p[2];
-    const int matern = matern_order(kernel);
-    PerArgs per{};
-    if (matern) GPK_TRY(matern_scales(h, kp, p));
-    else if (kernel == GPK_KERNEL_PERIODIC) { GPK_TRY(periodic_axes(h, kp, per)); p[0] = per.ax[0].p; p[1] = per.ax[1].p; }
-    else GPK_TRY(precisions(h, "assemble_prior: kernel id", kernel, kp, 2, p));
-    g.p1 = p[0]; g.p2 = p[1];
+    KernelParams k;
+    GPK_TRY(kernel_params(h, "assemble_prior: kernel id", kernel, kp, k));
+    g.p1 = k.p[0]; g.p2 = k.p[1];
     g.xa = Xa; g.na = na; g.xb = Xb; g.nb = nb; g.out = out; g.ld = ld;
     const bool wide = pairs_eligible(h, out, ld, nb);
-    const dim3 grid(gpk_ceil_div(gpk_ceil_div(nb, 2), 256), gpk_ceil_div(na, CROSS_TP));
-    if (matern) gpk_i_matern_prior(matern, wide, h->stream, g);
-    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_prior(wide, h->stream, g, per);
-    else if (wide) assemble_prior_kernel<true><<<grid, 256, 0, h->stream>>>(g);
-    else assemble_prior_kernel<false><<<grid, 256, 0, h->stream>>>(g);
+    k.family->prior(wide, h->stream, g, k);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -575,12 +286,10 @@ extern "C" int gpk_extend(gpk_handle h, int layout, int kernel, const double* kp
                           const double* Xd, int Nd, const double* Xb, int Nb, const double* coeff, double* out) {
     if (!h || !out || !Xt || !coeff || Nt <= 0) return GPK_ERR_ARG;
     AsmArgs g{};
-    PerArgs per{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
+    KernelParams k;
+    GPK_TRY(fill_common(h, g, k, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.out = out; g.ld = 0; g.tx = Xt; g.Nt = Nt; g.coeff = coeff;
-    if (const int matern = matern_order(kernel)) gpk_i_matern_extend(matern, layout, h->stream, g);
-    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_extend(layout, h->stream, g, per);
-    else with_layout(layout, [&](auto l) { extend_kernel<decltype(l)::value><<<Nt, 256, 0, h->stream>>>(g); });
+    k.family->extend(layout, h->stream, g, k);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }
@@ -594,12 +303,10 @@ extern "C" int gpk_extend_functionals(gpk_handle h, int layout, int kernel, cons
     if (Nt <= 0) return gpk_bad_arg(h, "extend_functionals: Nt <= 0");
     if (ldo < Nt) return gpk_bad_arg(h, "extend_functionals: ldo < Nt");
     FnArgs g;
-    PerArgs per{};
-    GPK_TRY(fill_common(h, g, layout, kernel, kp, Xd, Nd, Xb, Nb, per));
+    KernelParams k;
+    GPK_TRY(fill_common(h, g, k, layout, kernel, kp, Xd, Nd, Xb, Nb));
     g.tx = Xt; g.Nt = Nt; g.coeff = coeff; g.out = out; g.ldo = ldo;
-    if (const int matern = matern_order(kernel)) gpk_i_matern_extend_fn(matern, layout, fmask, h->stream, g);
-    else if (kernel == GPK_KERNEL_PERIODIC) gpk_i_periodic_extend_fn(layout, fmask, h->stream, g, per);
-    else with_layout(layout, [&](auto l) { launch_extend_fn<decltype(l)::value>(fmask, gpk_ceil_div(Nt, FN_TT), h->stream, g); });
+    k.family->extend_fn(layout, fmask, h->stream, g, k);
     GPK_LAUNCH_CHECK(h);
     return 0;
 }

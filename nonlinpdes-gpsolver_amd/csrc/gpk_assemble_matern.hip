@@ -1,9 +1,9 @@
 // gpk_assemble_matern.hip -- the Matern family (nu = 5/2, 7/2, 9/2) in the fused Gram evaluator of the reference layouts.
 //
-// One counterpart for each kernel shape of gpk_assemble.hip -- one-point and two-point Gram kernel, test rows, cross columns, extension,
-// multi-functional extension -- with the same lane-to-point mapping, the same store pattern and the same fixed-order reductions; the
-// entry points of gpk_assemble.hip choose the family on the host and launch these through gpk_assemble_ref.h.  A translation unit of its
-// own: nothing here is seen by the compiler when it generates the Gaussian kernels.
+// The mathematics of the family and its policy; the kernels are the frames of gpk_assemble_frames.h -- one-point and two-point Gram
+// kernel, test rows, cross columns, prior, extension, multi-functional extension -- instantiated here for the three orders and exported
+// as a table (gpk_i_family_matern, gpk_assemble_ref.h), through which the entry points of gpk_assemble.hip launch them.  A translation
+// unit of its own: nothing here is seen by the compiler when it generates the Gaussian kernels.
 //
 // Math (DESIGN.md §K "Matern kernels").  nu = m + 1/2, a^2 = 2 nu, u_i = (x_i - y_i) / rho_i, t = a |u|, theta_j the reverse Bessel
 // polynomials.  kappa = phi(s), s = |u|^2 / 2, and
@@ -22,7 +22,7 @@
 //
 // Every kernel computes the partials with the same bits for the same point pair: the per-pair arithmetic is written with explicit fma
 // and compiled without contraction (as the bc / op evaluators, gpk_assemble_common.h), so the 8-byte and the 16-byte store paths agree.
-#include "gpk_assemble_ref.h"
+#include "gpk_assemble_frames.h"
 
 using namespace gpk_asm;
 
@@ -123,314 +123,47 @@ __host__ __device__ __forceinline__ double pair_coeff_m(const double (&D)[5][5])
     return s;
 }
 
-// ---- Gram kernels: the frames of assemble_kernel / assemble2_kernel (gpk_assemble.hip) -----------------------------------------------
-template <int L, int BI, int BJ>
-__device__ __forceinline__ void store_block(const AsmArgs& g, int p, int q, const double (&D)[5][5]) {
-    if (q < g.size[BJ]) {
-        double v = pair_coeff_m<Lay<L>::f[BI], Lay<L>::f[BJ]>(D);
-        if (BI == BJ && p == q) v += g.nug[BI];
-        g.out[(long)(g.off[BI] + p) * g.ld + g.off[BJ] + q] = v;
+// The policy of nu = M + 1/2 (gpk_assemble_frames.h).  The partials carry the whole entry: there is no weight to factor out, so the
+// extension kernels sum entry * c.  The products with c and the sums of the frames stay outside the pragma, as they always were.
+template <int M>
+struct Matern {
+    struct State { double D[5][5]; };
+    static constexpr bool write_through = false;
+
+    __host__ __device__ __forceinline__ static void eval(double r1, double r2, double d1, double d2, State& s) {
+        matern_partials<M>(r1, r2, d1, d2, s.D);
     }
-}
-
-template <int L, int BI>
-__device__ __forceinline__ void store_row(const AsmArgs& g, int p, int q, const double (&D)[5][5]) {
-    if (p < g.size[BI]) {                               // wave-uniform
-        store_block<L, BI, 0>(g, p, q, D);
-        if (Lay<L>::nb > 1) store_block<L, BI, 1>(g, p, q, D);
-        if (Lay<L>::nb > 2) store_block<L, BI, 2>(g, p, q, D);
-        if (Lay<L>::nb > 3) store_block<L, BI, 3>(g, p, q, D);
+    __device__ __forceinline__ static void eval2(double r1, double r2, double d1a, double d2a, State& s0, double d1b, double d2b, State& s1) {
+        eval(r1, r2, d1a, d2a, s0);
+        eval(r1, r2, d1b, d2b, s1);
     }
-}
-
-template <int L, int BI, int BJ, int NT>
-__device__ __forceinline__ void store_block2(const AsmArgs& g, int p, int q, const double (&D0)[5][5], const double (&D1)[5][5]) {
-    if (q < g.size[BJ]) {                                            // (sizes are even here: q and q + 1 are both inside or both outside)
-        double v0 = pair_coeff_m<Lay<L>::f[BI], Lay<L>::f[BJ]>(D0);
-        double v1 = pair_coeff_m<Lay<L>::f[BI], Lay<L>::f[BJ]>(D1);
-        if (BI == BJ) { if (p == q) v0 += g.nug[BI]; if (p == q + 1) v1 += g.nug[BI]; }
-        store2<NT>(g.out + (long)(g.off[BI] + p) * g.ld + g.off[BJ] + q, v0, v1);
+    template <int FX, int FY>
+    __host__ __device__ __forceinline__ static double entry(const State& s) { return pair_coeff_m<FX, FY>(s.D); }
+    template <int FX, int FY>
+    __device__ __forceinline__ static double scaled(const State& s, double c) { return pair_coeff_m<FX, FY>(s.D) * c; }
+    __device__ __forceinline__ static double weigh(const State&, double v) { return v; }
+    __device__ __forceinline__ static double weigh_fn(const State&, double v) { return v; }
+    // Only D[0][0] = G_0 is used, so the rest of matern_partials is dead code here: one sqrt and one exp per pair.  G_0 depends on d
+    // through squares alone (even in d to the bit), and at d = 0 it is theta_m(0) / theta_m(0) = 1.
+    __device__ __forceinline__ static double prior(double r1, double r2, double d1, double d2) {
+        State s;
+        eval(r1, r2, d1, d2, s);
+        return entry<F_DELTA, F_DELTA>(s);
     }
-}
+    static void at_zero(double r1, double r2, State& s) { eval(r1, r2, 0.0, 0.0, s); }
+};
 
-template <int L, int BI, int NT>
-__device__ __forceinline__ void store_row2(const AsmArgs& g, int p, int q, const double (&D0)[5][5], const double (&D1)[5][5]) {
-    if (p < g.size[BI]) {                               // wave-uniform
-        store_block2<L, BI, 0, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 1) store_block2<L, BI, 1, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 2) store_block2<L, BI, 2, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 3) store_block2<L, BI, 3, NT>(g, p, q, D0, D1);
-    }
-}
-
-template <int M, int L, int NT>
-__global__ __launch_bounds__(256) void matern_assemble2_kernel(AsmArgs g) {
-    const int q = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = q < g.M;                                       // (M even: q + 1 < M as well)
-    const double y1a = live ? g.px[q] : 0.0, y2a = live ? g.py[q] : 0.0;
-    const double y1b = live ? g.px[q + 1] : 0.0, y2b = live ? g.py[q + 1] : 0.0;
-    const int p0 = blockIdx.y * TP;
-    const int pend = min(p0 + TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double x1 = g.px[p], x2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        double D0[5][5], D1[5][5];
-        matern_partials<M>(g.p1, g.p2, x1 - y1a, x2 - y2a, D0);
-        matern_partials<M>(g.p1, g.p2, x1 - y1b, x2 - y2b, D1);
-        store_row2<L, 0, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 1) store_row2<L, 1, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 2) store_row2<L, 2, NT>(g, p, q, D0, D1);
-        if (Lay<L>::nb > 3) store_row2<L, 3, NT>(g, p, q, D0, D1);
-    }
-}
-
-template <int M, int L>
-__global__ __launch_bounds__(256) void matern_assemble_kernel(AsmArgs g) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const bool live = q < g.M;
-    const double y1 = live ? g.px[q] : 0.0, y2 = live ? g.py[q] : 0.0;
-    const int p0 = blockIdx.y * TP;
-    const int pend = min(p0 + TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double x1 = g.px[p], x2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        double D[5][5];
-        matern_partials<M>(g.p1, g.p2, x1 - y1, x2 - y2, D);
-        store_row<L, 0>(g, p, q, D);
-        if (Lay<L>::nb > 1) store_row<L, 1>(g, p, q, D);
-        if (Lay<L>::nb > 2) store_row<L, 2>(g, p, q, D);
-        if (Lay<L>::nb > 3) store_row<L, 3>(g, p, q, D);
-    }
-}
-
-// ---- test rows: functional delta at the test point, column functionals of the layout (assemble_test_kernel) ---------------------------
-template <int L, int BJ>
-__device__ __forceinline__ void store_test(const AsmArgs& g, int t, int q, const double (&D)[5][5]) {
-    if (q < g.size[BJ]) g.out[(long)t * g.ld + g.off[BJ] + q] = pair_coeff_m<F_DELTA, Lay<L>::f[BJ]>(D);
-}
-
-template <int M, int L>
-__global__ __launch_bounds__(256) void matern_assemble_test_kernel(AsmArgs g) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= g.M) return;
-    const double y1 = g.px[q], y2 = g.py[q];
-    const int t0 = blockIdx.y * TP;
-    const int tend = min(t0 + TP, g.Nt);
-    for (int t = t0; t < tend; ++t) {
-        double D[5][5];
-        matern_partials<M>(g.p1, g.p2, g.tx[2 * t] - y1, g.tx[2 * t + 1] - y2, D);
-        store_test<L, 0>(g, t, q, D);
-        if (Lay<L>::nb > 1) store_test<L, 1>(g, t, q, D);
-        if (Lay<L>::nb > 2) store_test<L, 2>(g, t, q, D);
-        if (Lay<L>::nb > 3) store_test<L, 3>(g, t, q, D);
-    }
-}
-
-// ---- cross-covariance columns: the test rows transposed, two test points per lane (assemble_cross_kernel) -----------------------------
-template <int L, int BJ, bool WIDE>
-__device__ __forceinline__ void store_cross(const AsmArgs& g, int p, int t, const double (&D0)[5][5], const double (&D1)[5][5]) {
-    if (p < g.size[BJ]) {                               // wave-uniform
-        const double v0 = pair_coeff_m<F_DELTA, Lay<L>::f[BJ]>(D0);
-        const double v1 = pair_coeff_m<F_DELTA, Lay<L>::f[BJ]>(D1);
-        double* const dst = g.out + (long)(g.off[BJ] + p) * g.ld + t;
-        if constexpr (WIDE) store2<0>(dst, v0, v1);
-        else { dst[0] = v0; if (t + 1 < g.Nt) dst[1] = v1; }
-    }
-}
-
-template <int M, int L, bool WIDE>
-__global__ __launch_bounds__(256) void matern_assemble_cross_kernel(AsmArgs g) {
-    const int t = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = t < g.Nt;
-    const int tb = min(t + 1, g.Nt - 1);                // odd Nt: the last lane computes its point twice and stores it once
-    const double x1a = live ? g.tx[2 * t] : 0.0, x2a = live ? g.tx[2 * t + 1] : 0.0;
-    const double x1b = live ? g.tx[2 * tb] : 0.0, x2b = live ? g.tx[2 * tb + 1] : 0.0;
-    const int p0 = blockIdx.y * CROSS_TP;
-    const int pend = min(p0 + CROSS_TP, g.M);
-    for (int p = p0; p < pend; ++p) {
-        const double y1 = g.px[p], y2 = g.py[p];        // uniform address -> scalar loads
-        if (!live) continue;
-        double D0[5][5], D1[5][5];
-        matern_partials<M>(g.p1, g.p2, x1a - y1, x2a - y2, D0);
-        matern_partials<M>(g.p1, g.p2, x1b - y1, x2b - y2, D1);
-        store_cross<L, 0, WIDE>(g, p, t, D0, D1);
-        if (Lay<L>::nb > 1) store_cross<L, 1, WIDE>(g, p, t, D0, D1);
-        if (Lay<L>::nb > 2) store_cross<L, 2, WIDE>(g, p, t, D0, D1);
-        if (Lay<L>::nb > 3) store_cross<L, 3, WIDE>(g, p, t, D0, D1);
-    }
-}
-
-// ---- prior between two point sets: out[i * ld + j] = k(xa_i, xb_j) (assemble_prior_kernel) ---------------------------------------------
-// Only D[0][0] = G_0 is used, so the rest of matern_partials is dead code here: one sqrt and one exp per pair.  G_0 depends on d through
-// squares alone, so a square call (xa == xb) gives out[i][j] and out[j][i] the same bits, and at d = 0 it is theta_m(0) / theta_m(0) = 1.
-template <int M, bool WIDE>
-__global__ __launch_bounds__(256) void matern_assemble_prior_kernel(PriorArgs g) {
-    const int j = 2 * (blockIdx.x * 256 + threadIdx.x);
-    const bool live = j < g.nb;
-    const int jb = min(j + 1, g.nb - 1);                // odd nb: the last lane computes its point twice and stores it once
-    const double y1a = live ? g.xb[2 * j] : 0.0, y2a = live ? g.xb[2 * j + 1] : 0.0;
-    const double y1b = live ? g.xb[2 * jb] : 0.0, y2b = live ? g.xb[2 * jb + 1] : 0.0;
-    const int i0 = blockIdx.y * CROSS_TP;
-    const int iend = min(i0 + CROSS_TP, g.na);
-    for (int i = i0; i < iend; ++i) {
-        const double x1 = g.xa[2 * i], x2 = g.xa[2 * i + 1];   // uniform address -> scalar loads
-        if (!live) continue;
-        double D0[5][5], D1[5][5];
-        matern_partials<M>(g.p1, g.p2, x1 - y1a, x2 - y2a, D0);
-        matern_partials<M>(g.p1, g.p2, x1 - y1b, x2 - y2b, D1);
-        const double v0 = pair_coeff_m<F_DELTA, F_DELTA>(D0), v1 = pair_coeff_m<F_DELTA, F_DELTA>(D1);
-        double* const dst = g.out + (long)i * g.ld + j;
-        if constexpr (WIDE) store2<0>(dst, v0, v1);
-        else { dst[0] = v0; if (j + 1 < g.nb) dst[1] = v1; }
-    }
-}
-
-// ---- extension: out[t] = sum_c Theta_test[t, c] * coeff[c] (extend_kernel) --------------------------------------------------------------
-template <int L, int BJ>
-__device__ __forceinline__ double acc_test(const AsmArgs& g, int q, const double (&D)[5][5]) {
-    return (q < g.size[BJ]) ? pair_coeff_m<F_DELTA, Lay<L>::f[BJ]>(D) * g.coeff[g.off[BJ] + q] : 0.0;
-}
-
-template <int M, int L>
-__global__ __launch_bounds__(256) void matern_extend_kernel(AsmArgs g) {
-    __shared__ double red[4];
-    const int t = blockIdx.x;
-    const double x1 = g.tx[2 * t], x2 = g.tx[2 * t + 1];
-    double s = 0.0;
-    for (int q = threadIdx.x; q < g.M; q += 256) {
-        double D[5][5];
-        matern_partials<M>(g.p1, g.p2, x1 - g.px[q], x2 - g.py[q], D);
-        double v = acc_test<L, 0>(g, q, D);
-        if (Lay<L>::nb > 1) v += acc_test<L, 1>(g, q, D);
-        if (Lay<L>::nb > 2) v += acc_test<L, 2>(g, q, D);
-        if (Lay<L>::nb > 3) v += acc_test<L, 3>(g, q, D);
-        s += v;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) g.out[t] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ---- multi-functional extension (extend_fn_kernel): the row functional F in place of delta ------------------------------------------------
-// sum_b pair_coeff_m<F, f[b]> c[b] (c[b] = 0 outside block b)
-template <int L, int F>
-__device__ __forceinline__ double fn_sum(const double (&D)[5][5], const double (&c)[4]) {
-    double v = pair_coeff_m<F, Lay<L>::f[0]>(D) * c[0];
-    if (Lay<L>::nb > 1) v += pair_coeff_m<F, Lay<L>::f[1]>(D) * c[1];
-    if (Lay<L>::nb > 2) v += pair_coeff_m<F, Lay<L>::f[2]>(D) * c[2];
-    if (Lay<L>::nb > 3) v += pair_coeff_m<F, Lay<L>::f[3]>(D) * c[3];
-    return v;
-}
-
-template <int L, int MASK, int F>
-__device__ __forceinline__ void fn_acc(double (&s)[fn_popc(MASK)], const double (&D)[5][5], const double (&c)[4]) {
-    if ((MASK >> F) & 1) s[fn_row(MASK, F)] += fn_sum<L, F>(D, c);
-}
-
-template <int M, int L, int MASK>
-__global__ __launch_bounds__(256) void matern_extend_fn_kernel(FnArgs g) {
-    constexpr int NF = fn_popc(MASK);
-    const int t0 = blockIdx.x * FN_TT;
-    double x1[FN_TT], x2[FN_TT], s[FN_TT][NF];
-    GPK_FN_LOAD_POINTS2(x1, x2, g.tx, t0, g.Nt);
-    fn_zero(s);
-    for (int q = threadIdx.x; q < g.M; q += 256) {
-        const double y1 = g.px[q], y2 = g.py[q];
-        double c[4];
-#pragma unroll
-        for (int bk = 0; bk < 4; ++bk) c[bk] = (bk < Lay<L>::nb && q < g.size[bk]) ? g.coeff[g.off[bk] + q] : 0.0;
-#pragma unroll
-        for (int i = 0; i < FN_TT; ++i) {
-            double D[5][5];
-            matern_partials<M>(g.p1, g.p2, x1[i] - y1, x2[i] - y2, D);
-            fn_acc<L, MASK, F_DELTA>(s[i], D, c);
-            fn_acc<L, MASK, F_D1>(s[i], D, c);
-            fn_acc<L, MASK, F_D2>(s[i], D, c);
-            fn_acc<L, MASK, F_DD2>(s[i], D, c);
-            fn_acc<L, MASK, F_LAP>(s[i], D, c);
+// the order of the parameters becomes the policy type
+struct MaternFamily {
+    template <class F> static void with(const KernelParams& k, F&& f) {
+        switch (k.m) {
+            case 2: f(Matern<2>{}); break;
+            case 3: f(Matern<3>{}); break;
+            default: f(Matern<4>{}); break;
         }
     }
-    GPK_FN_REDUCE_STORE(s, NF, t0, g.Nt, g.out, g.ldo);
-}
-
-// f(std::integral_constant<int, M>) for m = 2, 3, 4 (the callers pass matern_order of a Matern id)
-template <class F>
-void with_order(int m, F&& f) {
-    switch (m) {
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        default: f(std::integral_constant<int, 4>{}); break;
-    }
-}
-
-// f(M, L) as integral constants
-template <class F>
-void with_order_layout(int m, int layout, F&& f) {
-    with_order(m, [&](auto mm) { with_layout(layout, [&](auto l) { f(mm, l); }); });
-}
+};
 
 }  // namespace
 
-void gpk_i_matern_gram(int m, int layout, bool pairs, int nt, hipStream_t st, const AsmArgs& g) {
-    const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.M, TP)), grid2(gpk_ceil_div(g.M / 2, 256), gpk_ceil_div(g.M, TP));
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        constexpr int M = decltype(mm)::value, L = decltype(l)::value;
-        if (!pairs) matern_assemble_kernel<M, L><<<grid, 256, 0, st>>>(g);
-        else if (nt == 1) matern_assemble2_kernel<M, L, 1><<<grid2, 256, 0, st>>>(g);
-        else matern_assemble2_kernel<M, L, 0><<<grid2, 256, 0, st>>>(g);
-    });
-}
-
-void gpk_i_matern_test(int m, int layout, hipStream_t st, const AsmArgs& g) {
-    const dim3 grid(gpk_ceil_div(g.M, 256), gpk_ceil_div(g.Nt, TP));
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        matern_assemble_test_kernel<decltype(mm)::value, decltype(l)::value><<<grid, 256, 0, st>>>(g);
-    });
-}
-
-void gpk_i_matern_cross(int m, int layout, bool wide, hipStream_t st, const AsmArgs& g) {
-    const dim3 grid(gpk_ceil_div(gpk_ceil_div(g.Nt, 2), 256), gpk_ceil_div(g.M, CROSS_TP));
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        constexpr int M = decltype(mm)::value, L = decltype(l)::value;
-        if (wide) matern_assemble_cross_kernel<M, L, true><<<grid, 256, 0, st>>>(g);
-        else matern_assemble_cross_kernel<M, L, false><<<grid, 256, 0, st>>>(g);
-    });
-}
-
-void gpk_i_matern_prior(int m, bool wide, hipStream_t st, const PriorArgs& g) {
-    const dim3 grid(gpk_ceil_div(gpk_ceil_div(g.nb, 2), 256), gpk_ceil_div(g.na, CROSS_TP));
-    with_order(m, [&](auto mm) {
-        constexpr int M = decltype(mm)::value;
-        if (wide) matern_assemble_prior_kernel<M, true><<<grid, 256, 0, st>>>(g);
-        else matern_assemble_prior_kernel<M, false><<<grid, 256, 0, st>>>(g);
-    });
-}
-
-void gpk_i_matern_extend(int m, int layout, hipStream_t st, const AsmArgs& g) {
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        matern_extend_kernel<decltype(mm)::value, decltype(l)::value><<<g.Nt, 256, 0, st>>>(g);
-    });
-}
-
-// one instantiation per (nu, layout, mask)
-void gpk_i_matern_extend_fn(int m, int layout, int mask, hipStream_t st, const FnArgs& g) {
-    const int grid = gpk_ceil_div(g.Nt, FN_TT);
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        with_mask<31>(mask, [&](auto k) {
-            matern_extend_fn_kernel<decltype(mm)::value, decltype(l)::value, decltype(k)::value><<<grid, 256, 0, st>>>(g);
-        });
-    });
-}
-
-void gpk_i_matern_diag(int m, int layout, double r1, double r2, double (&c)[4]) {
-    with_order_layout(m, layout, [&](auto mm, auto l) {
-        constexpr int M = decltype(mm)::value, L = decltype(l)::value;
-        double D[5][5];
-        matern_partials<M>(r1, r2, 0.0, 0.0, D);
-        c[0] = pair_coeff_m<Lay<L>::f[0], Lay<L>::f[0]>(D);
-        c[1] = pair_coeff_m<Lay<L>::f[1], Lay<L>::f[1]>(D);
-        c[2] = pair_coeff_m<Lay<L>::f[2], Lay<L>::f[2]>(D);
-        c[3] = pair_coeff_m<Lay<L>::f[3], Lay<L>::f[3]>(D);
-    });
-}
+const Family gpk_i_family_matern = family_of<MaternFamily>();

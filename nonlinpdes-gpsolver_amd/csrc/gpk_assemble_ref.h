@@ -1,8 +1,9 @@
-// gpk_assemble_ref.h -- what the three translation units of the reference layouts share: gpk_assemble.hip (the Gaussian family, the host
-// side of every entry point), gpk_assemble_matern.hip (the Matern family: kernels and their launches) and gpk_assemble_periodic.hip (the
-// periodic kernel, likewise).  The layouts, the argument
-// structs of the kernels, the layout dispatch, and the launch interfaces of the Matern and the periodic kernels.  The kernels themselves stay in their
-// files: each family is compiled on its own, so that nothing added for one changes the code generated for the other.
+// gpk_assemble_ref.h -- what the three translation units of the reference layouts share besides the kernel frames: gpk_assemble.hip (the
+// Gaussian family, the host side of every entry point), gpk_assemble_matern.hip (the Matern family) and gpk_assemble_periodic.hip (the
+// periodic kernel per axis).  The layouts, the argument structs of the kernels, the layout dispatch, and the description of a kernel
+// family as the host sees it: its parameters (KernelParams, kernel_params) and its table of launch functions (Family).  The kernels
+// are the frames of gpk_assemble_frames.h, instantiated by each file for its own family: each family is compiled on its own, so that
+// nothing added for one changes the code generated for another.
 #pragma once
 #include "gpk_assemble_common.h"
 
@@ -77,7 +78,7 @@ inline int matern_scales(gpk_handle h, const double* kp, double (&r)[2]) {
 // ---- the periodic kernel (DESIGN.md §K "Periodic kernel"): kappa_k(d) = exp(-(2 p_k / w_k^2) sin^2(w_k d / 2)), w_k = 2 pi / L_k -------
 // One axis of the product kernel, as the periodic kernels read it.  L = 0: the Gaussian factor exp(-p d^2 / 2) and the Hermite table
 // (w2 = pw = 0, g = p / 2); L > 0: the periodic factor, exponent -g sin^2(w d / 2).  Passed to the kernels beside AsmArgs / FnArgs /
-// PriorArgs, which therefore stay as the Gaussian and the Matern kernels know them.
+// PriorArgs (the variadic tail of the frames), which therefore stay as the Gaussian and the Matern kernels know them.
 struct PerAxis {
     double p;                             // precision 2 / sigma^2
     double L;                             // period, 0: not periodic
@@ -105,25 +106,51 @@ inline int periodic_axes(gpk_handle h, const double* kp, PerArgs& k) {
     return 0;
 }
 
+// ---- a kernel family as the host sees it ------------------------------------------------------------------------------------------
+// The launch functions of one family on stream st, for a valid layout id: each translation unit exports one table (family_of,
+// gpk_assemble_frames.h).  gram: pairs as pairs_eligible, nt the store policy of gpk_tune key 55 (the write-through policies 2 / 3 exist
+// for the Gaussian family only: plain elsewhere); cross, prior: wide as pairs_eligible; diag: c[b] = <f_b, f_b> at d = 0 for the blocks
+// of the layout (SURVEY §8a-K last column: makes the adaptive trace ratios analytic).
+struct KernelParams;
+struct Family {
+    void (*gram)(int layout, bool pairs, int nt, hipStream_t st, const AsmArgs& g, const KernelParams& k);
+    void (*test)(int layout, hipStream_t st, const AsmArgs& g, const KernelParams& k);
+    void (*cross)(int layout, bool wide, hipStream_t st, const AsmArgs& g, const KernelParams& k);
+    void (*prior)(bool wide, hipStream_t st, const PriorArgs& g, const KernelParams& k);   // (no layout: the value functional on both sides)
+    void (*extend)(int layout, hipStream_t st, const AsmArgs& g, const KernelParams& k);
+    void (*extend_fn)(int layout, int mask, hipStream_t st, const FnArgs& g, const KernelParams& k);
+    void (*diag)(int layout, const KernelParams& k, double (&c)[4]);
+};
+
+// the family parameters of a call: p the precisions (Gaussian, periodic) or the inverse length scales (Matern), the p1, p2 of the
+// argument structs; m the Matern order (0: not Matern); per the axes of the periodic kernel (read by that family only)
+struct KernelParams {
+    const Family* family;
+    double p[2];
+    int m;
+    PerArgs per;
+};
+
 }  // namespace gpk_asm
 
-// Launches of gpk_assemble_periodic.hip on stream st: the interface of the Matern launches below, the axes in place of the order.
-void gpk_i_periodic_gram(int layout, bool pairs, int nt, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
-void gpk_i_periodic_test(int layout, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
-void gpk_i_periodic_cross(int layout, bool wide, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
-void gpk_i_periodic_prior(bool wide, hipStream_t st, const gpk_asm::PriorArgs& g, const gpk_asm::PerArgs& k);
-void gpk_i_periodic_extend(int layout, hipStream_t st, const gpk_asm::AsmArgs& g, const gpk_asm::PerArgs& k);
-void gpk_i_periodic_extend_fn(int layout, int mask, hipStream_t st, const gpk_asm::FnArgs& g, const gpk_asm::PerArgs& k);
-// value of <f_b, f_b> at d = 0 for the blocks of the layout: the table there is (1, 0, -p, 0, 3 p^2 + w^2 p) per axis
-void gpk_i_periodic_diag(int layout, const gpk_asm::PerArgs& k, double (&c)[4]);
+extern const gpk_asm::Family gpk_i_family_gauss;      // gpk_assemble.hip
+extern const gpk_asm::Family gpk_i_family_matern;     // gpk_assemble_matern.hip
+extern const gpk_asm::Family gpk_i_family_periodic;   // gpk_assemble_periodic.hip
 
-// Launches of gpk_assemble_matern.hip on stream st (m = matern_order(kernel), layout a valid id, the grids of the Gaussian kernels of
-// the same shape).  gram: pairs as pairs_eligible, nt = 1: non-temporal 16-byte stores (the write-through policies 2 / 3 of key 55: plain).
-void gpk_i_matern_gram(int m, int layout, bool pairs, int nt, hipStream_t st, const gpk_asm::AsmArgs& g);
-void gpk_i_matern_test(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
-void gpk_i_matern_cross(int m, int layout, bool wide, hipStream_t st, const gpk_asm::AsmArgs& g);
-void gpk_i_matern_prior(int m, bool wide, hipStream_t st, const gpk_asm::PriorArgs& g);   // (no layout: the value functional on both sides)
-void gpk_i_matern_extend(int m, int layout, hipStream_t st, const gpk_asm::AsmArgs& g);
-void gpk_i_matern_extend_fn(int m, int layout, int mask, hipStream_t st, const gpk_asm::FnArgs& g);
-// value of <f_b, f_b> at d = 0 for the blocks of the layout (analytic host values, as diag_values of the Gaussian family)
-void gpk_i_matern_diag(int m, int layout, double r1, double r2, double (&c)[4]);
+namespace gpk_asm {
+
+// (kernel id, host_kparams) -> the family and its parameters; an id that belongs to no family is reported as `who`
+inline int kernel_params(gpk_handle h, const char* who, int kernel, const double* kp, KernelParams& k) {
+    k = KernelParams{};
+    if ((k.m = matern_order(kernel))) { k.family = &gpk_i_family_matern; return matern_scales(h, kp, k.p); }
+    if (kernel == GPK_KERNEL_PERIODIC) {
+        k.family = &gpk_i_family_periodic;
+        GPK_TRY(periodic_axes(h, kp, k.per));
+        k.p[0] = k.per.ax[0].p; k.p[1] = k.per.ax[1].p;
+        return 0;
+    }
+    k.family = &gpk_i_family_gauss;
+    return precisions(h, who, kernel, kp, 2, k.p);
+}
+
+}  // namespace gpk_asm
