@@ -51,7 +51,8 @@ enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 
 /* nugget_type of src/PDEs.py:56,250,391 / src/InverseProblems.py:66 */
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
-enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5, GPK_GN_MONGE_AMPERE = 6 };
+enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5, GPK_GN_MONGE_AMPERE = 6,
+       GPK_GN_SEMILINEAR3D = 7 };
 /* GPK_GN_MONGE_AMPERE (no counterpart in the reference; DESIGN.md section K, "Fully nonlinear: Monge-Ampere"):
  *   det D^2 u = f, f > 0, convex branch, in the form  Delta u = sqrt((D u)^2 + (M u)^2 + 4 f),  D = d_11 - d_22,  M = 2 d_12
  * ((Delta u)^2 = (D u)^2 + (M u)^2 + 4 det D^2 u), on the rows of gpk_assemble_hess ([D u; M u; Delta u; u] per domain point, then the
@@ -67,6 +68,20 @@ enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY
  *   F(z) = [v1; v2; (N(v0, v1, v2) - f) / eps; v0; g],   A(z): 1 at (t, v1_t), (N_d + t, v2_t), (3 N_d + t, v0_t) and
  *   N_u / eps, N_p / eps, N_q / eps at (2 N_d + t, v0_t / v1_t / v2_t);  N_u = a1 p + a2 q + c1 + 3 c3 u^2, N_p = a1 u + 2 b p, N_q = a2 u + 2 b q.
  * gpk_gn_problem: p0 = eps (finite, not 0: -9001 otherwise), the five coefficients in gq_a1 .. gq_c3; nonlin must be 0 (-9001). */
+/* GPK_GN_SEMILINEAR3D (no counterpart in the reference; DESIGN.md section K, "Gradient layout in three dimensions"):
+ *   -psi[u] + N(u, grad u) = f,   N(u, g) = u (a1 g1 + a2 g2 + a3 g3) + b1 g1^2 + b2 g2^2 + b3 g3^2 + c1 u + c3 u^3,   g_k = d_k u,
+ * on the rows of gpk_assemble_grad3d ([d_1 u; d_2 u; d_3 u; psi[u]; u] per domain point, then the boundary functionals), unknowns
+ * z = [v0 = u | v1 | v2 | v3], n_z = 4 N_d, N = 5 N_d + N_b, one factor:
+ *   F(z) = [v1; v2; v3; N(v0, v1, v2, v3) - f; v0; g],   A(z): 1 at (t, v1_t), (N_d + t, v2_t), (2 N_d + t, v3_t), (4 N_d + t, v0_t) and
+ *   N_u, N_g1, N_g2, N_g3 at (3 N_d + t, v0_t / v1_t / v2_t / v3_t);  N_u = a . g + c1 + 3 c3 u^2,  N_gk = a_k u + 2 b_k g_k.
+ * psi carries its own scale (eps Laplace, nu Laplace_x - d_t, ...: the op3 of gpk_assemble_grad3d), so the PDE row is not divided by anything.
+ * gpk_gn_problem keeps its fields; the eight coefficients travel in doubles it already has:
+ *   (a1, a2, a3) = (gq_a1, gq_a2, p0),   (b1, b2, b3) = (gq_b, p1, pen_lambda),   c1 = gq_c1,   c3 = gq_c3;
+ * nonlin and p2 must be 0 (-9001).  gpk_gn_step runs it in the leading-zero layout with the unknowns in the order v1, v2, v3, v0: the
+ * column at position pos then starts in row pos, one slope-1 staircase (the closed form of the elliptic system).  Served by gpk_gn_dims,
+ * gpk_gn_worksize, gpk_gn_build(_rev), gpk_gn_measurement, gpk_gn_loss, gpk_gn_hessian_grad, gpk_gn_step, gpk_gn_direction, the line
+ * search, gpk_posterior_prepare and gpk_log_evidence; gpk_gn_structured_prepare, gpk_gn_gram_prepare and gpk_mg_gn_step on more than one
+ * GPU refuse it (-9001, named in gpk_last_error). */
 /* Reaction term tau(u) of the elliptic systems, -psi[u] + tau(u) = f ("Reaction terms"); parameters p0, p1, p2:
  *   POWER  p0 pow(u, p1)              (alpha u^m: the reference's equation, and what a zeroed gpk_gn_problem means)
  *   EXP    p0 exp(p1 u)               SINH   p0 sinh(p1 u)              SIN   p0 sin(p1 u)
@@ -109,7 +124,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_grad3d call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -166,6 +181,13 @@ int gpk_pde_residual_sl(gpk_handle h, double eps, const double* host_gq5, int Nt
  * extension (gpk_extend_functionals_hess).  One fixed order of operations ((d11 * d22 - d12 * d12) - f, no contraction): a repeated call
  * gives bit-identical output.  NULL pointers, Nt <= 0, ldf < Nt: -9001. */
 int gpk_pde_residual_ma(gpk_handle h, int Nt, const double* fields, int ldf, const double* rhs, double* out);
+/* The same for the equation of GPK_GN_SEMILINEAR3D, host_gq8 = (a1, a2, a3, b1, b2, b3, c1, c3):
+ *   r = -psi_u + N(u0, u1, u2, u3) - f,   rows 0..3 of fields (ld ldf >= Nt) = value, d1, d2, d3 of the extension (gpk_extend_functionals_grad3d),
+ * psi_u (Nt) = psi_t[u] at the test points, which the caller has combined from the extension rows.  One fixed order of operations
+ * ((N - psi_u) - f with the N of the Gauss-Newton build, no contraction): a repeated call gives bit-identical output.  NULL pointers, Nt <= 0,
+ * ldf < Nt: -9001. */
+int gpk_pde_residual_sl3d(gpk_handle h, const double* host_gq8, int Nt, const double* fields, int ldf, const double* psi_u,
+                          const double* rhs, double* out);
 /* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
  *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
  *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
@@ -297,6 +319,27 @@ int gpk_assemble_op3d(gpk_handle h, int kernel, const double* host_kparams, cons
 int gpk_extend_functionals_op3d(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                                 const double* Xd, int Nd, const double* Xb, int Nb, const double* op3, const double* bc3,
                                 const double* coeff, int fmask, double* out, int ldo);
+/* ---- Gradient layout in three dimensions ("Gradient layout in three dimensions"): the rows an equation that is
+ *      nonlinear in grad u needs, -psi[u] + N(u, grad u) = f on a box in R^3 or, with axis 3 as time, in two space dimensions.  No
+ *      reference call site.  Blocks 0, 1, 2 = d_1, d_2, d_3 on the Nd domain points, block 3 = psi_i on the domain points, block 4 = delta
+ *      on the domain points followed by phi_b on the Nb boundary points: N = 5Nd+Nb, Theta N x N with leading dimension ld >= N.  op3
+ *      (Nd,10) / NULL, bc3 (Nb,4) / NULL, points, host_kparams and precisions exactly as gpk_assemble_op3d (whose blocks 0, 1 are the
+ *      blocks 3, 4 here).  Kernels: Gaussian and anisotropic Gaussian (any other id: -9001).  gpk_potrf, gpk_potrs and the
+ *      GPK_GN_SEMILINEAR3D system apply to it.  Nugget as gpk_assemble_hess: adaptive = nugget * trace(block k) / trace(block 4) on the
+ *      blocks k = 0..3, nugget on block 4.  host_ratios4 (four doubles, may be NULL) = those ratios with the values at d = 0
+ *        <d_k, d_k> = p_k,   <psi, psi> and <phi, phi> as gpk_assemble_op3d,
+ *      written for every nugget type; the point sums are taken on the host in index order (op3 / bc3 != NULL: one small device-to-host
+ *      copy each, synchronises).  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte stores
+ *      otherwise, with the same values; nothing outside the N x N view is written); the launch is timed like gpk_assemble's when the
+ *      per-phase timing is on (gpk_prof_read_assembly).  Bad arguments: -9001, named in gpk_last_error. */
+int gpk_assemble_grad3d(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                        const double* op3, const double* bc3, double nugget, int nugget_type, double* Theta, int ld, double* host_ratios4);
+/* The ten monomial derivatives of the extension on the gradient layout at test points Xt (Nt,3), matrix-free: coeff (5Nd+Nb) =
+ * Theta^{-1} sol_vec with the Theta of gpk_assemble_grad3d for the same op3 and bc3.  fmask, out, ldo and the guarantees (fixed reduction
+ * order, a row has the same bits whichever other rows are requested) as gpk_extend_functionals_op3d. */
+int gpk_extend_functionals_grad3d(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                                  const double* Xd, int Nd, const double* Xb, int Nb, const double* op3, const double* bc3,
+                                  const double* coeff, int fmask, double* out, int ldo);
 /* solver_GP.collocation_pts_err / get_test_error (src/solver.py:169-178, 185-194): err_all[i] = |truth[i] - approx[i]| (device, may be
  * NULL), *host_max = max_i err_all[i], *host_l2 = sqrt(sum_i err_all[i]^2 / n) -- the reference's "L2 error".  All inputs on the
  * device (the extension already is); one pass, fixed summation order.  Synchronises. */
@@ -360,8 +403,9 @@ int gpk_syrk(gpk_handle h, int n, int k, double alpha, const double* A, int lda,
 typedef struct {
     int system;              /* GPK_GN_* */
     int Nd, Nb, Ndata;
-    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, -   MONGE_AMPERE: -, - */
-    double pen_lambda;       /* ELLIPTIC_RELAXED only */
+    double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, -   MONGE_AMPERE: -, -
+                              * SEMILINEAR3D: a3, b2 (the coefficients of u g3 and of g2^2) */
+    double pen_lambda;       /* ELLIPTIC_RELAXED: the penalty   SEMILINEAR3D: b3 (the coefficient of g3^2) */
     const double* rhs_f;     /* (Nd,)  */
     const double* bdy_g;     /* (Nb,)  */
     const double* data_u;    /* (Ndata,) DARCY only */
@@ -376,7 +420,8 @@ typedef struct {
     const double* G; int ldg; const double* pvec;
     /* optional (may be NULL), GPK_GN_DARCY only -- see gpk_gn_darcy_prepare */
     const double* Wa; int ldwa; const double* Ha; int ldha;
-    /* GPK_GN_SEMILINEAR only: the coefficients (a1, a2, b, c1, c3) of N(u, grad u); five consecutive doubles */
+    /* GPK_GN_SEMILINEAR: the coefficients (a1, a2, b, c1, c3) of N(u, grad u); five consecutive doubles.
+     * GPK_GN_SEMILINEAR3D: a1, a2, b1 (in gq_b), c1, c3 -- with a3 = p0, b2 = p1, b3 = pen_lambda the eight coefficients of its N */
     double gq_a1, gq_a2, gq_b, gq_c1, gq_c3;
     /* reaction term of ELLIPTIC(_RELAXED): GPK_NL_* with the parameters p0, p1 above and p2 (CUBIC only); 0 = alpha u^m.  Any other
      * system takes 0 only (-9001 otherwise) */

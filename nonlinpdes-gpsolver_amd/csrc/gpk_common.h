@@ -364,3 +364,25 @@ __host__ __device__ __forceinline__ void sl_dN(const double* gq, double u, doubl
     *Np = gq[0] * u + 2.0 * gq[2] * p;
     *Nq = gq[1] * u + 2.0 * gq[2] * q;
 }
+
+// Gradient-dependent nonlinearity of GPK_GN_SEMILINEAR3D (gpk.h; DESIGN.md section K, "Gradient layout in three dimensions"), c = (a1, a2,
+// a3, b1, b2, b3, c1, c3):  N(u, g) = u (a1 g1 + a2 g2 + a3 g3) + (b1 g1 g1 + b2 g2 g2 + b3 g3 g3) + u (c1 + c3 u u)  and its partial
+// derivatives.  The one place that knows the form: gn_build_kernel and pde_residual_sl3d_kernel call it.  ONE order of operations, left to
+// right as spelled, and no contraction (the pragma at the head of each body): the build and the residual give the same bits for the same
+// arguments.
+struct Sl3Coef { double c[8]; };
+__host__ __device__ __forceinline__ double sl3_N(const double* c, double u, double g1, double g2, double g3) {
+#pragma clang fp contract(off)
+    const double conv = u * ((c[0] * g1 + c[1] * g2) + c[2] * g3);
+    const double grad = (c[3] * (g1 * g1) + c[4] * (g2 * g2)) + c[5] * (g3 * g3);
+    const double reac = u * (c[6] + c[7] * (u * u));
+    return (conv + grad) + reac;
+}
+__host__ __device__ __forceinline__ void sl3_dN(const double* c, double u, double g1, double g2, double g3, double* Nu, double* N1, double* N2,
+                                                double* N3) {
+#pragma clang fp contract(off)
+    *Nu = ((c[0] * g1 + c[1] * g2) + c[2] * g3) + (c[6] + 3.0 * c[7] * (u * u));
+    *N1 = c[0] * u + 2.0 * c[3] * g1;
+    *N2 = c[1] * u + 2.0 * c[4] * g2;
+    *N3 = c[2] * u + 2.0 * c[5] * g3;
+}

@@ -30,6 +30,8 @@ int gn_dims(const gpk_gn_problem* p, Dims& d) {
         case GPK_GN_SEMILINEAR:
         case GPK_GN_MONGE_AMPERE:
             d.nz = 3 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 4 * Nd + Nb, 0, p->Dinv}; d.rows = 4 * Nd + Nb; break;
+        case GPK_GN_SEMILINEAR3D:
+            d.nz = 4 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 5 * Nd + Nb, 0, p->Dinv}; d.rows = 5 * Nd + Nb; break;
         case GPK_GN_DARCY:
             if (p->Ndata < 0 || p->Ndata > Nd) return GPK_ERR_ARG;
             d.nz = 6 * Nd; d.ngroups = 3;
@@ -58,7 +60,8 @@ struct BuildArgs {
     int system, Nd, Nb, Ndata;
     double p0, p1, lam;
     int nonlin; double p2;   // reaction term of the elliptic systems (GPK_NL_*; nl_tau / nl_dtau of gpk_common.h)
-    double gq[5];            // GPK_GN_SEMILINEAR: (a1, a2, b, c1, c3) of N(u, grad u) (sl_N / sl_dN of gpk_common.h)
+    double gq[8];            // GPK_GN_SEMILINEAR: (a1, a2, b, c1, c3) of N(u, grad u) (sl_N / sl_dN of gpk_common.h); GPK_GN_SEMILINEAR3D: (a1, a2,
+                             // a3, b1, b2, b3, c1, c3) (sl3_N / sl3_dN), gathered from the doubles of gpk_gn_problem by build_args
     const double* f; const double* gb; const double* data; const double* z;
     double* S; long lds; int fcol; int write_A;
     int rev;           // leading-zero layout of gn_step: unknown j is stored in column nz-1-pos(j), and that column of A(z) is zero above
@@ -67,7 +70,9 @@ struct BuildArgs {
                        // same order; its v0 columns start in row 2 N_d + t = pos, see step_profile).  3: Burgers, the three
                        // unknowns of point t (columns t, N_d + t, 2 N_d + t all start in row t) interleaved: pos(j) = 3t + group,
                        // a staircase of slope 1/3 (column zero above row pos/3; GpkLz::div = 3).  4: Darcy (round 4), unknown groups
-                       // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below
+                       // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below.  5: the semilinear
+                       // system in three dimensions, unknown groups [v0 | v1 | v2 | v3] taken in the order v1, v2, v3, v0: their first
+                       // non-zeros sit in rows t, N_d + t, 2 N_d + t and 3 N_d + t (N_u in the PDE row) = pos exactly
     int nz;
     int family;        // elliptic system, gpk_gn_structured_prepare: 1 = only the unit entries of the first row group ([I; 0; 0], no F),
                        // 2 = only those of the second ([0; I; 0]) together with F(z); 0 = the normal [A(z) | F(z)]
@@ -80,6 +85,7 @@ __host__ __device__ __forceinline__ int stair_pos(int rev, int Nd, int j) {
         const int to = blk == 0 ? 4 : blk == 1 ? 2 : blk == 2 ? 3 : blk == 3 ? 5 : blk == 4 ? 0 : 1;
         return to * Nd + j % Nd;
     }
+    if (rev == 5) return ((j / Nd + 3) % 4) * Nd + j % Nd;
     return rev == 2 ? ((j / Nd + 2) % 3) * Nd + j % Nd : rev == 3 ? 3 * (j % Nd) + j / Nd : j;
 }
 
@@ -208,6 +214,18 @@ __device__ __forceinline__ void gn_build_rows(const BuildArgs& a, const int t, c
             putF(a, 2 * Nd + t, (sl_N(a.gq, v0, v1, v2) - a.f[t]) / eps);
             putF(a, 3 * Nd + t, v0);
         } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
+    } else if (a.system == GPK_GN_SEMILINEAR3D) {           // gpk.h, GPK_GN_SEMILINEAR3D: rows [d_1 u; d_2 u; d_3 u; psi[u]; u], PDE row N(v0, v1, v2, v3) - f
+        if (t < Nd) {
+            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t], v3 = z[3 * Nd + t];
+            double Nu, N1, N2, N3;
+            sl3_dN(a.gq, v0, v1, v2, v3, &Nu, &N1, &N2, &N3);
+            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0); putA(a, 2 * Nd + t, 3 * Nd + t, 1.0);
+            putA(a, 3 * Nd + t, t, Nu); putA(a, 3 * Nd + t, Nd + t, N1); putA(a, 3 * Nd + t, 2 * Nd + t, N2); putA(a, 3 * Nd + t, 3 * Nd + t, N3);
+            putA(a, 4 * Nd + t, t, 1.0);
+            putF(a, t, v1); putF(a, Nd + t, v2); putF(a, 2 * Nd + t, v3);
+            putF(a, 3 * Nd + t, sl3_N(a.gq, v0, v1, v2, v3) - a.f[t]);
+            putF(a, 4 * Nd + t, v0);
+        } else if (t < Nd + Nb) putF(a, 5 * Nd + (t - Nd), a.gb[t - Nd]);
     } else if (a.system == GPK_GN_MONGE_AMPERE) {           // gpk.h, GPK_GN_MONGE_AMPERE: rows [D u; M u; Delta u; u], PDE row s = sqrt(v1^2 + v2^2 + 4 f)
         if (t < Nd) {
             const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t];
@@ -344,7 +362,11 @@ BuildArgs build_args(const gpk_gn_problem* p, const double* z, double* S, long l
     a.system = p->system; a.Nd = p->Nd; a.Nb = p->Nb; a.Ndata = p->Ndata;
     a.p0 = p->p0; a.p1 = p->p1; a.lam = p->pen_lambda;
     a.nonlin = p->nonlin; a.p2 = p->p2;
-    a.gq[0] = p->gq_a1; a.gq[1] = p->gq_a2; a.gq[2] = p->gq_b; a.gq[3] = p->gq_c1; a.gq[4] = p->gq_c3;
+    a.gq[0] = p->gq_a1; a.gq[1] = p->gq_a2; a.gq[2] = p->gq_b; a.gq[3] = p->gq_c1; a.gq[4] = p->gq_c3; a.gq[5] = a.gq[6] = a.gq[7] = 0.0;
+    if (p->system == GPK_GN_SEMILINEAR3D) {                          // (a1, a2, a3) = (gq_a1, gq_a2, p0), (b1, b2, b3) = (gq_b, p1, pen_lambda)
+        const double c[8] = {p->gq_a1, p->gq_a2, p->p0, p->gq_b, p->p1, p->pen_lambda, p->gq_c1, p->gq_c3};
+        for (int k = 0; k < 8; ++k) a.gq[k] = c[k];
+    }
     a.f = p->rhs_f; a.gb = p->bdy_g; a.data = p->data_u; a.z = z;
     a.S = S; a.lds = lds; a.fcol = fcol; a.write_A = write_A;
     return a;
@@ -364,6 +386,8 @@ int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
         if (p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR takes nonlin = 0 only (its nonlinearity is gq_a1 .. gq_c3)");
         if (!(std::isfinite(p->p0) && p->p0 != 0.0)) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR needs a finite eps (p0) other than 0");
     }
+    if (p->system == GPK_GN_SEMILINEAR3D && (p->nonlin != GPK_NL_POWER || p->p2 != 0.0))
+        return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR3D takes nonlin = 0 and p2 = 0 only (its nonlinearity is gq_a1 .. gq_c3, p0, p1, pen_lambda)");
     if (p->system == GPK_GN_MONGE_AMPERE && p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_MONGE_AMPERE takes nonlin = 0 only");
     if (p->nonlin != GPK_NL_POWER && p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_ELLIPTIC_RELAXED)
         return gpk_bad_arg(h, "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED");
@@ -452,8 +476,9 @@ int exact_loss_chain(gpk_handle h, const Dims& d, bool after_main, bool* on_side
 }
 
 // The column layout gpk_gn_step runs a system in (BuildArgs::rev): 1 elliptic systems, 2 Eikonal, 3 Burgers, 4 Darcy on the GEMM-only
-// solve path, 0 = dense schedule.
+// solve path, 5 the semilinear system in three dimensions, 0 = dense schedule.
 int step_layout(gpk_handle h, const gpk_gn_problem* p) {
+    if (p->system == GPK_GN_SEMILINEAR3D) return h->tune.eikonal_lz ? 5 : 0;
     const bool darcy_lz = p->system == GPK_GN_DARCY && h->tune.eikonal_lz && h->tune.use_dinv && p->Dinv && p->Dinv2 && p->dinv_block > 0;
     return (p->system == GPK_GN_ELLIPTIC || p->system == GPK_GN_ELLIPTIC_RELAXED) ? 1
          : ((p->system == GPK_GN_EIKONAL || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE) && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
@@ -467,9 +492,12 @@ int step_layout(gpk_handle h, const gpk_gn_problem* p) {
 // rows above Eikonal's first entry, which the second segment would skip -- dropping dN/du from H with no other symptom.  Its exact
 // profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row 2 N_d + t = n_z - 1 - c).
 // The Monge-Ampere system has exactly Eikonal's pattern (v0 does not enter its PDE row) and takes the two-segment profile.
+// The semilinear system in three dimensions (layout 5, order v1, v2, v3, v0): the column at position pos holds its first non-zero in row
+// pos -- the 1 of the rows d_k u for the gradient unknowns, N_u in the PDE row 3 N_d + t for v0_t -- so the closed form with lead = n_z is
+// exact, as for the elliptic system.
 GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
     if (rev == 2 && (p->system == GPK_GN_EIKONAL || p->system == GPK_GN_MONGE_AMPERE) && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
-    return (rev >= 1 && rev <= 3) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
+    return ((rev >= 1 && rev <= 3) || rev == 5) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
 // the GEMM-only solve path is available and switched on, with the block size given (the structured modes of the other systems need it)
@@ -740,7 +768,7 @@ enum class StepProduct { None, SyrkPotrf, Darcy };
 // No side effects.  A mode is chosen only when everything it reads has been prepared; an incomplete preparation falls through to the
 // next line and in the end to Plain.  (The elliptic system has layout 1, and its relaxed form is a system of its own: always Plain.)
 StepMode select_mode(gpk_handle h, const gpk_gn_problem* p, const Dims& d, int rev) {
-    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE) return StepMode::Plain;   // (no structured form yet)
+    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE || p->system == GPK_GN_SEMILINEAR3D) return StepMode::Plain;   // (no structured form yet)
     const bool ops = p->W1 && p->W2 && p->ldw >= d.nz + 1;           // gpk_gn_structured_prepare
     const bool gram = p->G && p->ldg >= d.nz;                        // gpk_gn_gram_prepare
     if (p->system == GPK_GN_ELLIPTIC && ops && p->v0) return gram && p->pvec ? StepMode::GramElliptic : StepMode::StructuredElliptic;
@@ -904,6 +932,7 @@ extern "C" int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* p, 
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
     if (p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "structured solve: not for the relaxed system");
     if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR is not served (its PDE row has three z-dependent entries per point)");
+    if (p->system == GPK_GN_SEMILINEAR3D) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR3D is not served (its PDE row has four z-dependent entries per point)");
     if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "structured solve: GPK_GN_MONGE_AMPERE is not served yet (its structured form exists: A(z) = A_1 diag(d(z)) + A_2 as for Eikonal)");
     if (elliptic && !v0) return GPK_ERR_ARG;
     const int nc = d.nz + 1;
@@ -941,6 +970,7 @@ extern "C" int gpk_gn_gram_prepare(gpk_handle h, const gpk_gn_problem* p, double
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
     if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR is not served (it has no structured form)");
+    if (p->system == GPK_GN_SEMILINEAR3D) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR3D is not served (it has no structured form)");
     if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "gram_prepare: GPK_GN_MONGE_AMPERE is not served yet (no structured prepare)");
     if (p->system == GPK_GN_ELLIPTIC_RELAXED || !p->W1 || !p->W2 || (elliptic && !p->v0))
         return gpk_bad_arg(h, "gram_prepare: needs W1/W2 (and v0 for the elliptic system) of gpk_gn_structured_prepare; not for the relaxed system");
@@ -1325,7 +1355,7 @@ extern "C" int gpk_gn_build_rev(gpk_handle h, const gpk_gn_problem* p, const dou
     if (!h || !z || !S || !p) return GPK_ERR_ARG;
     // (round 6: also the Eikonal and Burgers systems in the staircase orders of their gpk_gn_step -- the sharded step uses them)
     const int rev = step_layout(h, p);
-    if (rev < 1 || rev > 4 || p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "gn_build_rev: not for the relaxed system / needs the leading-zero layout");
+    if (rev < 1 || rev > 5 || p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "gn_build_rev: not for the relaxed system / needs the leading-zero layout");
     Dims d;
     gpk_gn_problem q = *p;
     if (gn_dims(&q, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");

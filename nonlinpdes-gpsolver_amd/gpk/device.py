@@ -36,7 +36,7 @@ def dinv_block_for(n):
         db //= 2
     return db
 SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4, 'Semilinear2d': 5,
-          'MongeAmpere2d': 6}
+          'MongeAmpere2d': 6, 'Semilinear3d': 7}
 NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
 EVIDENCE_TERMS = ('log_Z', 'J', 'logdet_theta', 'logdet_H', 'gamma_term', 'two_pi_term')   # host_terms[6] of gpk_log_evidence
 
@@ -146,10 +146,12 @@ class GNProblem:
     """Device-side description of one equation's Gauss-Newton system (gpk_gn_problem)."""
 
     def __init__(self, ctx, system, Nd, Nb, rhs_f, bdy_g, L, p0=0.0, p1=0.0, pen_lambda=0.0, data_u=None, L2=None, dinv=True, structured=False,
-                 cache_a=None, nonlin=0, p2=0.0, gq=None):
+                 cache_a=None, nonlin=0, p2=0.0, gq=None, gq8=None):
         """nonlin, p2 (elliptic systems only): the reaction term tau(u) -- a GPK_NL_* id or its name in NONLIN -- with the parameters
         p0, p1, p2; 0 / 'power' is p0 u^p1, the reference's equation.
         gq ('Semilinear2d' only): the coefficients (a1, a2, b, c1, c3) of N(u, grad u); p0 is eps there.
+        gq8 ('Semilinear3d' only): the coefficients (a1, a2, a3, b1, b2, b3, c1, c3) of its N(u, grad u).  The struct has no fields of
+        their own for a3, b2, b3: they travel in p0, p1, pen_lambda (include/gpk.h), so those three arguments must be left at 0.
         structured: False (default: the reference's operation sequence every step), True / 1 (prepare_structured), 2 (+ prepare_gram).
         cache_a (Darcy only): keep the iteration-independent a-part of the step (prepare_darcy: bit-identical iterates, less work per step);
         None = on unless GPK_DARCY_CACHE=0.
@@ -176,6 +178,13 @@ class GNProblem:
             if len(gq) != 5:
                 raise ValueError(f'gq: the five coefficients (a1, a2, b, c1, c3), got {len(gq)}')
             s.gq_a1, s.gq_a2, s.gq_b, s.gq_c1, s.gq_c3 = gq
+        if gq8 is not None:
+            gq8 = [float(v) for v in gq8]
+            if len(gq8) != 8:
+                raise ValueError(f'gq8: the eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), got {len(gq8)}')
+            if s.system != SYSTEM['Semilinear3d'] or gq is not None or (s.p0, s.p1, s.pen_lambda) != (0.0, 0.0, 0.0):
+                raise ValueError("gq8: for the system 'Semilinear3d' only, without gq and with p0 = p1 = pen_lambda = 0 (they carry a3, b2, b3)")
+            s.gq_a1, s.gq_a2, s.p0, s.gq_b, s.p1, s.pen_lambda, s.gq_c1, s.gq_c3 = gq8
         s.rhs_f, s.bdy_g = self.rhs_f.ptr, self.bdy_g.ptr
         s.data_u = self.data_u.ptr if self.data_u is not None else None
         s.L, s.ldl = L.ptr, L.ld
@@ -586,6 +595,48 @@ class Context:
         of assemble_op3d."""
         return self._extend_functionals('extend_functionals_op3d', FUNCTIONAL_OP3, 3, self.lib.gpk_extend_functionals_op3d, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb, self._coeffs3(op3, bc3), coeff, which)
+
+    # ---- gradient layout in three dimensions (gpk_assemble_grad3d, gpk_extend_functionals_grad3d, gpk_pde_residual_sl3d) ----
+    def assemble_grad3d(self, kernel, kernel_parameter, Xd, Xb, op3, bc3, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 3-D gradient layout (blocks d1, d2, d3, psi on Xd, delta / phi on [Xd; Xb]; op3 and bc3 as for
+        assemble_op3d): (DeviceArray N x N with N = 5 Nd + Nb, [trace(block k) / trace(block 4) for k = 0..3]).  out: a DeviceArray to
+        write into (any leading dimension >= N)."""
+        require_gaussian_family(kernel, 'gpk_assemble_grad3d')
+        Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3) for X in (Xd, Xb))
+        Nd, Nb = Xd.shape[0], Xb.shape[0]
+        N = 5 * Nd + Nb
+        dXd, dXb = self.points(Xd, 3), self.points(Xb, 3)
+        held = self._coeffs3(op3, bc3)(Nd, Nb)                              # (kept alive until the call has been issued)
+        extra = [a.ptr if a is not None else None for a in held]
+        T = out if out is not None else DeviceArray(self, N, N)
+        ratios = (C.c_double * 4)()
+        self._chk(self.lib.gpk_assemble_grad3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
+                                               *extra, float(nugget), NUGGET[nugget_type], T.ptr, T.ld, ratios))
+        self.synchronize()
+        return T, list(ratios)
+
+    def extend_functionals_grad3d(self, kernel, kernel_parameter, Xt, Xd, Xb, op3, bc3, coeff, which=OP3_NAMES):
+        """Value / derivatives up to order two of the extension on the 3-D gradient layout at Xt (gpk_extend_functionals_grad3d): a
+        (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP3).  coeff = Theta^{-1} sol_vec (5 Nd + Nb
+        values) with the Theta of assemble_grad3d."""
+        return self._extend_functionals('extend_functionals_grad3d', FUNCTIONAL_OP3, 3, self.lib.gpk_extend_functionals_grad3d, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, self._coeffs3(op3, bc3), coeff, which)
+
+    def pde_residual_sl3d(self, gq8, fields, psi_u, rhs):
+        """Pointwise residual -psi_u + N(u0, u1, u2, u3) - f of the 3-D semilinear equation with gq8 = (a1, a2, a3, b1, b2, b3, c1, c3)
+        (gpk_pde_residual_sl3d), as an (Nt,) DeviceArray.  fields: (4, Nt) value, d1, d2, d3; psi_u: (Nt,) psi[u] at the test points;
+        rhs as for pde_residual."""
+        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
+        Nt = du.cols
+        dp = psi_u if isinstance(psi_u, DeviceArray) else self.array(np.asarray(psi_u, dtype=np.float64).ravel())
+        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        out = DeviceArray(self, Nt)
+        gq8 = [float(v) for v in gq8]
+        if len(gq8) != 8:
+            raise ValueError(f'gq8: the eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), got {len(gq8)}')
+        self._chk(self.lib.gpk_pde_residual_sl3d(self.h, (C.c_double * 8)(*gq8), Nt, du.ptr, du.ld, dp.ptr, dr.ptr, out.ptr))
+        self.synchronize()
+        return out
 
     def pde_residual(self, system, params, fields_u, fields_a, rhs):
         """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array

@@ -1,6 +1,7 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
 same elliptic equation on a box in three space dimensions, and Semilinear2d, the semilinear equation with a gradient-dependent
-nonlinearity on the Eikonal layout (neither has a counterpart in the reference).  Five classes on _GPEquation; the two
+nonlinearity on the Eikonal layout, and Semilinear3d, its counterpart in three dimensions and in time on the gradient layout (none has a
+counterpart in the reference).  The classes stand on _GPEquation; the two
 elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
 _family() what sets it apart.
 
@@ -18,7 +19,7 @@ import gpk
 
 from gpk.device import require_gaussian_family
 from ._runtime import eval_callback, get_context
-from .nonlinearity import GradientNonlinearity, Nonlinearity
+from .nonlinearity import GradientNonlinearity, GradientNonlinearity3d, Nonlinearity
 from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
@@ -1180,3 +1181,132 @@ class MongeAmpere2d(_GPEquation):
 
     def _posterior_unserved(self):
         return 'MongeAmpere2d: gpk_assemble_cross has no rectangular evaluator for the Hessian layout yet'
+
+
+class Semilinear3d(Nonlinear_elliptic3d):
+    """-psi[u] + N(u, grad u) = f on a box in R^3, B u = g on its faces, with the gradient-dependent nonlinearity
+    N(u, g) = u (a1 g1 + a2 g2 + a3 g3) + b1 g1^2 + b2 g2^2 + b3 g3^2 + c1 u + c3 u^3 (src/nonlinearity.py, GradientNonlinearity3d): the
+    3-D counterpart of Semilinear2d -- viscous Burgers / convection, viscous Hamilton-Jacobi and KPZ, the regularised Eikonal equation --
+    and, with axis 3 as time (operator=parabolic_form(nu), sampled_pts(time_dependent=True), a3 = b3 = 0), their time-dependent forms in
+    two space dimensions: u_t - nu Laplace_x u + u (a1 u_x1 + a2 u_x2) = f, u_t - nu Laplace_x u + b |grad_x u|^2 = f.  No counterpart in
+    the reference.  psi is eps Laplace by default; operator= / set_domain_operator and bc= / set_boundary_operator behave exactly as on
+    Nonlinear_elliptic3d, whose points, samplers, callbacks and operator handling this class inherits.  The Gram matrix is the gradient
+    layout's (rows d_1 u, d_2 u, d_3 u, psi[u], u per domain point, then the boundary functionals: gpk_assemble_grad3d, Gaussian kernels
+    only), the Gauss-Newton system is GPK_GN_SEMILINEAR3D with unknowns [u | d_1 u | d_2 u | d_3 u].  log_evidence is the base class's;
+    posterior_variance / posterior_covariance / posterior_sample raise NotImplementedError (the layout has no rectangular cross evaluator);
+    there is no relaxed formulation.  eq.line_search (src/linesearch.py) is honoured.  Plain Gauss-Newton steps: convection-dominated
+    settings do not converge from the zero start, as for Semilinear2d."""
+    _layout = 'Gradient3d'
+    _system = 'Semilinear3d'
+    _blocks_per_point = 4
+
+    def __init__(self, eps=0.1, nonlinearity=('burgers', 1.0, 1.0), bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1], [0, 1]]),
+                 bc='dirichlet', robin_beta=1.0, operator=None):
+        """nonlinearity: a GradientNonlinearity3d, the eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), or a preset -- ('burgers', a1,
+        a2[, a3]), ('hamilton_jacobi', b1, b2[, b3]), ('eikonal',).  eps: psi = eps Laplace when no operator is given (finite; not read
+        otherwise).  bc, robin_beta, operator: as for Nonlinear_elliptic3d."""
+        if operator is None and not onp.isfinite(eps):
+            raise ValueError(f'Semilinear3d: eps must be finite, got {eps!r}')
+        _EllipticEquation.__init__(self, None, None, bdy, rhs, domain, bc, robin_beta, operator, None)
+        del self.alpha, self.m                                 # (the elliptic classes' reaction term: this equation has none)
+        self.eps = eps
+        self.nonlinearity = GradientNonlinearity3d.make(nonlinearity)
+
+    def _gn_params(self):
+        return 0.0, 0.0, 0.0                                   # (p0, p1, pen_lambda carry a3, b2, b3: GNProblem fills them from gq8)
+
+    def _nl_args(self):
+        return dict(gq8=self.nonlinearity.params)
+
+    def _tau(self):
+        raise NotImplementedError('Semilinear3d has no reaction term tau(u): its nonlinearity is N(u, grad u)')
+
+    # ---- psi: the operator given, or eps Laplace ---------------------------------------------------------------------------------------
+    def _default_psi(self, n):
+        return onp.tile(float(self.eps) * onp.asarray(self._laplacian_row), (n, 1))
+
+    def _set_points(self, X_domain, X_boundary):
+        super()._set_points(X_domain, X_boundary)
+        self._psi_is_default = self.domain_coeffs is None
+        if self._psi_is_default:
+            self.domain_coeffs = self._default_psi(self.N_domain)
+
+    def set_domain_operator(self, coeffs):
+        super().set_domain_operator(coeffs)
+        self._psi_is_default = False
+
+    # ---- one evaluator family ----------------------------------------------------------------------------------------------------------
+    def _family(self):
+        return 'grad'
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        return ctx.assemble_grad3d(kernel, kernel_parameter, self.X_domain, self.X_boundary, self.domain_coeffs, self.boundary_coeffs,
+                                   nugget, nugget_type)
+
+    def _fields(self, X_test, which):
+        coeff = self._coeff(self._dL, self.sol_vec)
+        return get_context().extend_functionals_grad3d(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                       self.domain_coeffs, self.boundary_coeffs, coeff, which=which)
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
+        """kernel_parameter: sigma (Gaussian) or three length scales (anisotropic_Gaussian); stores the four trace ratios in `ratio`"""
+        require_gaussian_family(kernel, 'Semilinear3d')
+        self.ratio = list(self._assemble(kernel, kernel_parameter, nugget, nugget_type)[:4])
+
+    # ---- Gauss-Newton ------------------------------------------------------------------------------------------------------------------
+    def _split(self, z):
+        Nd = self.N_domain
+        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:3 * Nd], z[3 * Nd:]
+
+    def GN_loss(self, z, z_old):
+        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
+        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
+        v = self._split(z)
+        o = self._split(z_old)
+        d = self.nonlinearity.dN(*o)
+        row = self.nonlinearity.N(*o) + sum(dk * (vk - ok) for dk, vk, ok in zip(d, v, o)) - self.rhs_f
+        return self._tri_loss(onp.concatenate([v[1], v[2], v[3], row, v[0], self.bdy_g]))
+
+    def Hessian_GN(self, z, z_old):
+        return self._hessian(z_old)
+
+    def _initial(self, initial_sol, n):
+        if isinstance(initial_sol, str) and initial_sol == 'zero':
+            return onp.zeros(n)
+        return super()._initial(initial_sol, n)
+
+    def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
+        """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
+        sol = self._initial(initial_sol, 4 * self.N_domain)
+        self.init_sol = sol
+        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
+        v0, v1, v2, v3 = self._split(sol)
+        self.sol_vec = onp.concatenate([v1, v2, v3, self.nonlinearity.N(v0, v1, v2, v3) - self.rhs_f, v0, self.bdy_g])
+        self.sol_sampled_pts = v0
+
+    # ---- residual ----------------------------------------------------------------------------------------------------------------------
+    def PDE_residual(self, X_test, coeffs_t=None):
+        """pointwise residual -psi_t[u] + N(u, grad u) - f at X_test from the derivatives of the GP solution (gpk_pde_residual_sl3d; rhs
+        evaluated at X_test): psi_t from the callable `operator`, eps Laplace when none was given, or coeffs_t (Nt, 10) (needed when the
+        operator was set per point; ValueError otherwise)"""
+        X_test = self._pts(X_test)
+        n = len(self._op_names)
+        if coeffs_t is None:
+            if self.operator is not None:
+                coeffs_t = self._operator_at(X_test)
+            elif self._psi_is_default:
+                coeffs_t = self._default_psi(X_test.shape[0])
+            else:
+                raise ValueError('the domain operator was set per point (set_domain_operator): pass its coefficients at the test '
+                                 f'points as coeffs_t (Nt,{n})')
+        coeffs_t = onp.asarray(coeffs_t, dtype=onp.float64)
+        if coeffs_t.shape != (X_test.shape[0], n):
+            raise ValueError(f'coeffs_t must have shape ({X_test.shape[0]}, {n}), got {coeffs_t.shape}')
+        rows = self._fields(X_test, self._op_names).download().reshape(n, -1)
+        psi = (coeffs_t.T * rows).sum(axis=0)                     # psi_t[u]: a combination of the rows, per test point
+        rhs = eval_callback(self.get_rhs, *self._columns(X_test))
+        self.test_residual = get_context().pde_residual_sl3d(self.nonlinearity.params, rows[:4], psi, rhs).download().reshape(-1)
+        return self.test_residual
+
+    def _posterior_unserved(self):
+        return 'Semilinear3d: gpk_assemble_cross has no rectangular evaluator for the gradient layout in three dimensions'

@@ -124,3 +124,61 @@ class GradientNonlinearity(object):
     def describe(self):
         a1, a2, b, c1, c3 = self.params
         return f'u*({a1}*u_x1 + {a2}*u_x2) + {b}*|grad u|^2 + {c1}*u + {c3}*u^3'
+
+
+class GradientNonlinearity3d(object):
+    """N(u, g) = u (a1 g1 + a2 g2 + a3 g3) + b1 g1^2 + b2 g2^2 + b3 g3^2 + c1 u + c3 u^3 of -psi[u] + N(u, grad u) = f in three dimensions
+    (g_k = d_k u; with axis 3 as time set a3 = b3 = 0) and its four partial derivatives on the host (numpy): the mirror of sl3_N / sl3_dN
+    of csrc/gpk_common.h, written in the same order of operations.  params = (a1, a2, a3, b1, b2, b3, c1, c3), what GNProblem takes as gq8.
+
+        ('burgers', a1, a2[, a3])            u (a . g)                 viscous Burgers / convection along a
+        ('hamilton_jacobi', b1, b2[, b3])    sum_k b_k g_k^2           viscous Hamilton-Jacobi, KPZ
+        ('eikonal',)                         g1^2 + g2^2 + g3^2        the regularised Eikonal equation (with f^2 as right-hand side)
+    """
+    PRESETS = {'burgers': (2, 3), 'hamilton_jacobi': (2, 3), 'eikonal': (0,)}
+
+    def __init__(self, a1=0.0, a2=0.0, a3=0.0, b1=0.0, b2=0.0, b3=0.0, c1=0.0, c3=0.0):
+        self.params = tuple(float(v) for v in (a1, a2, a3, b1, b2, b3, c1, c3))
+        if not all(onp.isfinite(self.params)):
+            raise ValueError(f'GradientNonlinearity3d: the coefficients must be finite, got {self.params}')
+        self.a1, self.a2, self.a3, self.b1, self.b2, self.b3, self.c1, self.c3 = self.params
+
+    @classmethod
+    def make(cls, spec):
+        """spec: a GradientNonlinearity3d, the eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), or a preset (name, parameters...)"""
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str) or not hasattr(spec, '__len__') or len(spec) < 1:
+            raise ValueError(f"nonlinearity {spec!r}: a GradientNonlinearity3d, (a1, a2, a3, b1, b2, b3, c1, c3) or a preset such as "
+                             "('burgers', 1.0, 1.0)")
+        if isinstance(spec[0], str):
+            name, args = spec[0], tuple(spec[1:])
+            if name not in cls.PRESETS:
+                raise ValueError(f'nonlinearity preset {name!r}: one of {tuple(cls.PRESETS)}')
+            if len(args) not in cls.PRESETS[name]:
+                raise ValueError(f'nonlinearity preset {name!r} takes {" or ".join(str(n) for n in cls.PRESETS[name])} parameters, got {len(args)}')
+            args = args + (0.0,) * (3 - len(args))
+            if name == 'burgers':
+                return cls(a1=args[0], a2=args[1], a3=args[2])
+            if name == 'hamilton_jacobi':
+                return cls(b1=args[0], b2=args[1], b3=args[2])
+            return cls(b1=1.0, b2=1.0, b3=1.0)
+        if len(spec) != 8:
+            raise ValueError(f'nonlinearity {spec!r}: eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), got {len(spec)}')
+        return cls(*spec)
+
+    def N(self, u, g1, g2, g3):
+        a1, a2, a3, b1, b2, b3, c1, c3 = self.params
+        conv = u * ((a1 * g1 + a2 * g2) + a3 * g3)
+        grad = (b1 * (g1 * g1) + b2 * (g2 * g2)) + b3 * (g3 * g3)
+        return (conv + grad) + u * (c1 + c3 * (u * u))
+
+    def dN(self, u, g1, g2, g3):
+        """(N_u, N_g1, N_g2, N_g3)"""
+        a1, a2, a3, b1, b2, b3, c1, c3 = self.params
+        return (((a1 * g1 + a2 * g2) + a3 * g3) + (c1 + 3.0 * c3 * (u * u)), a1 * u + 2.0 * b1 * g1, a2 * u + 2.0 * b2 * g2,
+                a3 * u + 2.0 * b3 * g3)
+
+    def describe(self):
+        a1, a2, a3, b1, b2, b3, c1, c3 = self.params
+        return f'u*({a1}*u_x1 + {a2}*u_x2 + {a3}*u_x3) + {b1}*u_x1^2 + {b2}*u_x2^2 + {b3}*u_x3^2 + {c1}*u + {c3}*u^3'

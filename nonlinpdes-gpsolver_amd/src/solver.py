@@ -4,7 +4,7 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d
+from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d, Semilinear3d
 from .nonlinearity import GradientNonlinearity, Nonlinearity
 
 
@@ -45,6 +45,16 @@ def _gradient_nl_of(c):
     if spec is None:
         spec = getattr(c, 'nl_params', None)
     return GradientNonlinearity.make(('burgers', 1.0, 1.0) if spec is None else spec)
+
+
+def _gradient_nl3_of(c):
+    """the GradientNonlinearity3d of a Semilinear3d configuration: cfg.nonlinearity (an instance, eight coefficients or a preset), else
+    cfg.nl_params = (a1, a2, a3, b1, b2, b3, c1, c3), else the class's default ('burgers', 1, 1)"""
+    from .nonlinearity import GradientNonlinearity3d
+    spec = getattr(c, 'nonlinearity', None)
+    if spec is None:
+        spec = getattr(c, 'nl_params', None)
+    return GradientNonlinearity3d.make(('burgers', 1.0, 1.0) if spec is None else spec)
 
 
 def _form_line(c, default):
@@ -121,6 +131,16 @@ _EQUATIONS = {
         lambda c: ['[Equation type] Semilinear equation with a gradient-dependent nonlinearity',
                    f'[Equation form] - eps*Delta u + N(u, grad u) = f, N = {_gradient_nl_of(c).describe()}'],
         lambda c: f'[Equation parameter] eps = {c.eps}, (a1, a2, b, c1, c3) = {_gradient_nl_of(c).params}'),
+    'Semilinear3d': (
+        # (cfg.eps; cfg.nonlinearity / cfg.nl_params as for Semilinear2d with eight coefficients; cfg.bc / cfg.robin_beta / cfg.operator /
+        #  cfg.time_dependent as for Nonlinear_elliptic3d)
+        lambda c, **k: Semilinear3d(eps=getattr(c, 'eps', 0.1), nonlinearity=_gradient_nl3_of(c), bc=getattr(c, 'bc', 'dirichlet'),
+                                    robin_beta=getattr(c, 'robin_beta', 1.0), operator=_operator_of(c), **k),
+        lambda c: ['[Equation type] Semilinear equation with a gradient-dependent nonlinearity in three dimensions',
+                   ('[Equation form] - eps*Delta u' if _operator_of(c) is None else '[Equation form] - psi[u]')
+                   + f' + N(u, grad u) = f, N = {_gradient_nl3_of(c).describe()}']
+        + _operator_lines(c) + _time_lines(c) + _bc_lines(c),
+        lambda c: f"[Equation parameter] eps = {getattr(c, 'eps', 0.1)}, (a1, a2, a3, b1, b2, b3, c1, c3) = {_gradient_nl3_of(c).params}"),
     'MongeAmpere2d': (
         lambda c, **k: MongeAmpere2d(**k),
         lambda c: ['[Equation type] Monge-Ampere equation (fully nonlinear)',
@@ -246,7 +266,7 @@ class solver_GP(object):
         _say(print_option, 'pts_user', 'pts_n', e=self.eqn)
 
     def auto_sample(self, N_domain, N_boundary, sampled_type='random', print_option=True):
-        if self.PDE_type == 'Nonlinear_elliptic3d' and getattr(self.config, 'time_dependent', False):
+        if self.PDE_type in ('Nonlinear_elliptic3d', 'Semilinear3d') and getattr(self.config, 'time_dependent', False):
             self.eqn.sampled_pts(N_domain, N_boundary, sampled_type=sampled_type, time_dependent=True)
         else:
             self.eqn.sampled_pts(N_domain, N_boundary, sampled_type=sampled_type)
@@ -437,8 +457,8 @@ class solver_GP(object):
 
     # ---- figures (cosmetic; need matplotlib only): src/_figures.py ---------------------------------------------------------
     def _planar_only(self):
-        if self.PDE_type == 'Nonlinear_elliptic3d':
-            raise NotImplementedError('the plot helpers draw planar point sets and contours; not available for Nonlinear_elliptic3d')
+        if self.PDE_type in ('Nonlinear_elliptic3d', 'Semilinear3d'):
+            raise NotImplementedError(f'the plot helpers draw planar point sets and contours; not available for {self.PDE_type}')
 
     def show_sample(self):
         self._planar_only()
