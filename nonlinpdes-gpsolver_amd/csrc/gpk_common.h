@@ -316,6 +316,7 @@ int gpk_i_gn_dims(gpk_handle h, const gpk_gn_problem* p, int* nz, int* rows);
 // [A(z) | F] (storage order) under it: Eikonal its two-segment profile on the GEMM-only solve path, Burgers the closed form of slope 1/3;
 // dense for the layouts 0 and 4 (Darcy's two factors have a profile each: the u-part's is gpk_i_gn_darcy_u_profile)
 int gpk_i_gn_layout(gpk_handle h, const gpk_gn_problem* p);
+bool gpk_i_gn_sharded(const gpk_gn_problem* p);                                        // gpk_mg_gn_step admits the system (GnTraits::sharded)
 GpkLz gpk_i_gn_profile(gpk_handle h, const gpk_gn_problem* p, int rev);
 GpkLz gpk_i_gn_darcy_u_profile(int Nd);
 int gpk_i_gn_darcy_add_a(gpk_handle h, const gpk_gn_problem* p, double* Hb, int ldh, int r0, int r1, const double* aF, int ldaf);

@@ -19,32 +19,77 @@ struct Group { const double* L; int ldl; int n; int off; const double* Dinv; };
 
 struct Dims { int nz; int rows; int ngroups; Group g[3]; };
 
+// ---- what a Gauss-Newton system IS: one record per GPK_GN_* id, read by everything below and by gpk_mg.hip (gpk_i_gn_sharded) ----------
+// A new system is described here, in one PDE-row record (Row* below, if it is of the gradient-unknown form) and nowhere else.
+struct GnTraits {
+    int unknowns;       // unknown groups per collocation point: n_z = unknowns * N_d (0: not a system id)
+    int rows;           // rows per domain point of the group factored with L: it has rows * N_d + N_b rows.  Darcy (a second factored group,
+                        // data rows) and the relaxed system (penalty rows) add their further groups by hand in gn_dims
+    int grad_k;         // the gradient-unknown form with k = 2 or 3 (0: another form): unknowns [v_0 | v_1 | .. | v_k], rows [v_1; ..; v_k; PDE row;
+                        // v_0; g] with unit entries everywhere but in the PDE row -- written by ONE frame, gn_build_gradient_rows
+    int lz_layout;      // the column layout (BuildArgs::rev) gpk_gn_step runs the system in when the leading-zero schedule is on
+                        // (tune.eikonal_lz; the elliptic systems' layout 1 does not ask): 1 elliptic, 2 the gradient-unknown form with k = 2,
+                        // 3 Burgers, 4 Darcy (on the GEMM-only solve path only, see step_layout), 5 the gradient-unknown form with k = 3
+    bool v0_free_pde_row;   // v_0 does not enter the PDE row, so that the v_0 columns start N_d rows LATER, in the value row: Eikonal's exact
+                        // two-segment profile (eikonal_profile) holds.  The Monge-Ampere system has exactly Eikonal's pattern and takes it.
+                        // The semilinear system shares Eikonal's layout 2 but must NEVER take that profile: its v_0 columns carry N_u / eps in
+                        // row 2 N_d + t, N_d rows above Eikonal's first entry, which the second segment would skip -- dropping dN/du from H
+                        // with no other symptom.  Its exact profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row
+                        // 2 N_d + t = n_z - 1 - c).  The semilinear system in three dimensions (layout 5, order v1, v2, v3, v0): the column at
+                        // position pos holds its first non-zero in row pos -- the 1 of the rows d_k u for the gradient unknowns, N_u in the PDE
+                        // row 3 N_d + t for v0_t -- so the closed form with lead = n_z is exact, as for the elliptic system.
+    bool sharded;       // gpk_mg_gn_step admits it (in its leading-zero layout)
+    bool p2_reserved;   // p2 must be 0 as well where nonlin must be GPK_NL_POWER
+    const char* no_reaction;    // the system has no reaction term of the GPK_NL_* family: the refusal of nonlin != GPK_NL_POWER (nullptr: it has one)
+    const char* bad_eps;        // its PDE row is divided by eps = p0, checked to be finite and not 0: the refusal (nullptr: not checked)
+    const char* no_structured;  // why gpk_gn_structured_prepare does not serve it (nullptr: served; gpk_gn_step then looks for the prepared forms)
+    const char* no_gram;        // why gpk_gn_gram_prepare does not
+};
+
+__host__ __device__ constexpr GnTraits gn_traits(int system) {
+    constexpr const char* other_nl = "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED";
+    switch (system) {
+        case GPK_GN_ELLIPTIC: return {1, 2, 0, 1, false, true, false, nullptr, nullptr, nullptr, nullptr};
+        case GPK_GN_ELLIPTIC_RELAXED:
+            return {2, 2, 0, 1, false, false, false, nullptr, nullptr, "structured solve: not for the relaxed system",
+                    "gram_prepare: needs W1/W2 (and v0 for the elliptic system) of gpk_gn_structured_prepare; not for the relaxed system"};
+        case GPK_GN_BURGERS: return {3, 4, 0, 3, false, true, false, other_nl, nullptr, nullptr, nullptr};
+        case GPK_GN_EIKONAL: return {3, 4, 2, 2, true, true, false, other_nl, nullptr, nullptr, nullptr};
+        case GPK_GN_DARCY: return {6, 4, 0, 4, false, true, false, other_nl, nullptr, nullptr, nullptr};
+        case GPK_GN_SEMILINEAR:
+            return {3, 4, 2, 2, false, false, false, "gn: GPK_GN_SEMILINEAR takes nonlin = 0 only (its nonlinearity is gq_a1 .. gq_c3)",
+                    "gn: GPK_GN_SEMILINEAR needs a finite eps (p0) other than 0",
+                    "structured solve: GPK_GN_SEMILINEAR is not served (its PDE row has three z-dependent entries per point)",
+                    "gram_prepare: GPK_GN_SEMILINEAR is not served (it has no structured form)"};
+        case GPK_GN_MONGE_AMPERE:
+            return {3, 4, 2, 2, true, false, false, "gn: GPK_GN_MONGE_AMPERE takes nonlin = 0 only", nullptr,
+                    "structured solve: GPK_GN_MONGE_AMPERE is not served yet (its structured form exists: A(z) = A_1 diag(d(z)) + A_2 as for Eikonal)",
+                    "gram_prepare: GPK_GN_MONGE_AMPERE is not served yet (no structured prepare)"};
+        case GPK_GN_SEMILINEAR3D:
+            return {4, 5, 3, 5, false, false, true,
+                    "gn: GPK_GN_SEMILINEAR3D takes nonlin = 0 and p2 = 0 only (its nonlinearity is gq_a1 .. gq_c3, p0, p1, pen_lambda)", nullptr,
+                    "structured solve: GPK_GN_SEMILINEAR3D is not served (its PDE row has four z-dependent entries per point)",
+                    "gram_prepare: GPK_GN_SEMILINEAR3D is not served (it has no structured form)"};
+        default: return {0, 0, 0, 0, false, false, false, nullptr, nullptr, nullptr, nullptr};
+    }
+}
+
 int gn_dims(const gpk_gn_problem* p, Dims& d) {
     const int Nd = p->Nd, Nb = p->Nb;
-    if (Nd <= 0 || Nb < 0) return GPK_ERR_ARG;
-    switch (p->system) {
-        case GPK_GN_ELLIPTIC:
-            d.nz = Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 2 * Nd + Nb, 0, p->Dinv}; d.rows = 2 * Nd + Nb; break;
-        case GPK_GN_BURGERS:
-        case GPK_GN_EIKONAL:
-        case GPK_GN_SEMILINEAR:
-        case GPK_GN_MONGE_AMPERE:
-            d.nz = 3 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 4 * Nd + Nb, 0, p->Dinv}; d.rows = 4 * Nd + Nb; break;
-        case GPK_GN_SEMILINEAR3D:
-            d.nz = 4 * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, 5 * Nd + Nb, 0, p->Dinv}; d.rows = 5 * Nd + Nb; break;
-        case GPK_GN_DARCY:
-            if (p->Ndata < 0 || p->Ndata > Nd) return GPK_ERR_ARG;
-            d.nz = 6 * Nd; d.ngroups = 3;
-            d.g[0] = {p->L2, p->ldl2, 3 * Nd, 0, p->Dinv2};
-            d.g[1] = {p->L, p->ldl, 4 * Nd + Nb, 3 * Nd, p->Dinv};
-            d.g[2] = {nullptr, 0, p->Ndata, 7 * Nd + Nb, nullptr};
-            d.rows = 7 * Nd + Nb + p->Ndata; break;
-        case GPK_GN_ELLIPTIC_RELAXED:
-            d.nz = 2 * Nd; d.ngroups = 2;
-            d.g[0] = {p->L, p->ldl, 2 * Nd + Nb, 0, p->Dinv};
-            d.g[1] = {nullptr, 0, Nd, 2 * Nd + Nb, nullptr};
-            d.rows = 3 * Nd + Nb; break;
-        default: return GPK_ERR_ARG;
+    const GnTraits t = gn_traits(p->system);
+    if (Nd <= 0 || Nb < 0 || t.unknowns == 0) return GPK_ERR_ARG;
+    d.nz = t.unknowns * Nd; d.ngroups = 1; d.g[0] = {p->L, p->ldl, t.rows * Nd + Nb, 0, p->Dinv}; d.rows = t.rows * Nd + Nb;
+    if (p->system == GPK_GN_DARCY) {                                 // the a-part with its own factor in front, the data rows behind
+        if (p->Ndata < 0 || p->Ndata > Nd) return GPK_ERR_ARG;
+        d.ngroups = 3;
+        d.g[0] = {p->L2, p->ldl2, 3 * Nd, 0, p->Dinv2};
+        d.g[1] = {p->L, p->ldl, 4 * Nd + Nb, 3 * Nd, p->Dinv};
+        d.g[2] = {nullptr, 0, p->Ndata, 7 * Nd + Nb, nullptr};
+        d.rows = 7 * Nd + Nb + p->Ndata;
+    } else if (p->system == GPK_GN_ELLIPTIC_RELAXED) {               // the penalty rows, without a factor
+        d.ngroups = 2;
+        d.g[1] = {nullptr, 0, Nd, 2 * Nd + Nb, nullptr};
+        d.rows = 3 * Nd + Nb;
     }
     return 0;
 }
@@ -67,7 +112,7 @@ struct BuildArgs {
     int rev;           // leading-zero layout of gn_step: unknown j is stored in column nz-1-pos(j), and that column of A(z) is zero above
                        // row pos(j).  1: pos(j) = j (elliptic systems).  2: Eikonal, unknown groups [v0 | v1 | v2] taken in the
                        // order v1, v2, v0: their first non-zeros sit in rows t, N_d + t, 3 N_d + t >= pos (the semilinear system runs the
-                       // same order; its v0 columns start in row 2 N_d + t = pos, see step_profile).  3: Burgers, the three
+                       // same order; its v0 columns start in row 2 N_d + t = pos, see GnTraits::v0_free_pde_row).  3: Burgers, the three
                        // unknowns of point t (columns t, N_d + t, 2 N_d + t all start in row t) interleaved: pos(j) = 3t + group,
                        // a staircase of slope 1/3 (column zero above row pos/3; GpkLz::div = 3).  4: Darcy (round 4), unknown groups
                        // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below.  5: the semilinear
@@ -78,6 +123,11 @@ struct BuildArgs {
                        // 2 = only those of the second ([0; I; 0]) together with F(z); 0 = the normal [A(z) | F(z)]
 };
 
+// the layouts 2 (k = 2) and 5 (k = 3) of the gradient-unknown form: the groups [v0 | v1 | .. | vk] taken in the order v1, .., vk, v0
+// (k a compile-time constant: the remainder is then no division)
+template <int k>
+__host__ __device__ __forceinline__ int stair_pos_gradient(int Nd, int j) { return ((j / Nd + k) % (k + 1)) * Nd + j % Nd; }
+
 // position of unknown j in the staircase order (see BuildArgs::rev)
 __host__ __device__ __forceinline__ int stair_pos(int rev, int Nd, int j) {
     if (rev == 4) {                                                   // natural group (w0 w1 w2 v0 v1 v2) -> block of the staircase order
@@ -85,8 +135,9 @@ __host__ __device__ __forceinline__ int stair_pos(int rev, int Nd, int j) {
         const int to = blk == 0 ? 4 : blk == 1 ? 2 : blk == 2 ? 3 : blk == 3 ? 5 : blk == 4 ? 0 : 1;
         return to * Nd + j % Nd;
     }
-    if (rev == 5) return ((j / Nd + 3) % 4) * Nd + j % Nd;
-    return rev == 2 ? ((j / Nd + 2) % 3) * Nd + j % Nd : rev == 3 ? 3 * (j % Nd) + j / Nd : j;
+    if (rev == 2) return stair_pos_gradient<2>(Nd, j);
+    if (rev == 5) return stair_pos_gradient<3>(Nd, j);
+    return rev == 3 ? 3 * (j % Nd) + j / Nd : j;
 }
 
 // Darcy system, leading-zero layout (round 4).  Column c of S holds the unknown at staircase position p = n_z - 1 - c, blocks
@@ -137,6 +188,82 @@ struct ZTrial {
     const double* z; const double* delta; double alpha;
     __device__ __forceinline__ double operator[](int i) const { return gn_point(z[i], alpha, delta[i]); }
 };
+
+// ---- the PDE row of the gradient-unknown systems at collocation point t, v = (v_0, .., v_k): one record per system with its id and k, its
+// partial derivatives dR[j] = dR / dv_j (j >= 1, and j = 0 where has_v0 says that v_0 enters the row) and its value.  Where has_v0 is
+// false the frame writes NO entry in the v_0 column of the row -- not a zero: under a leading-zero layout it would land above the
+// two-segment profile (GnTraits::v0_free_pde_row).  Two functions, not one: the frame evaluates the partials in front of the stores of
+// A and the value behind them, where they always stood, and each system's arithmetic is spelled as it always was -- the compiler fuses
+// products into sums per basic block, so moving the value in front of those (conditional) stores changes its last bit.
+struct RowEikonal {                                         // src/PDEs.py:420-428 (F), :441-449 (A)
+    static constexpr int system = GPK_GN_EIKONAL, k = 2; static constexpr bool has_v0 = false;
+    static __device__ __forceinline__ void partials(const BuildArgs& a, int, const double* v, double* dR) {
+        const double eps = a.p0, v1 = v[1], v2 = v[2];
+        dR[1] = 2.0 * v1 / eps; dR[2] = 2.0 * v2 / eps;
+    }
+    static __device__ __forceinline__ double value(const BuildArgs& a, int t, const double* v) {
+        const double eps = a.p0, v1 = v[1], v2 = v[2], ft = a.f[t];
+        return -(ft * ft - v1 * v1 - v2 * v2) / eps;
+    }
+};
+struct RowSemilinear {                                      // gpk.h, GPK_GN_SEMILINEAR: the Eikonal rows, PDE row (N(v0, v1, v2) - f) / eps
+    static constexpr int system = GPK_GN_SEMILINEAR, k = 2; static constexpr bool has_v0 = true;
+    static __device__ __forceinline__ void partials(const BuildArgs& a, int, const double* v, double* dR) {
+        const double eps = a.p0;
+        double Nu, Np, Nq;
+        sl_dN(a.gq, v[0], v[1], v[2], &Nu, &Np, &Nq);
+        dR[0] = Nu / eps; dR[1] = Np / eps; dR[2] = Nq / eps;
+    }
+    static __device__ __forceinline__ double value(const BuildArgs& a, int t, const double* v) {
+        const double eps = a.p0;
+        return (sl_N(a.gq, v[0], v[1], v[2]) - a.f[t]) / eps;
+    }
+};
+struct RowMongeAmpere {                                     // gpk.h, GPK_GN_MONGE_AMPERE: rows [D u; M u; Delta u; u], PDE row s = sqrt(v1^2 + v2^2 + 4 f)
+    static constexpr int system = GPK_GN_MONGE_AMPERE, k = 2; static constexpr bool has_v0 = false;
+    static __device__ __forceinline__ double value(const BuildArgs& a, int t, const double* v) {
+        const double v1 = v[1], v2 = v[2];
+        return sqrt(v1 * v1 + v2 * v2 + 4.0 * a.f[t]);      // (a negative radicand gives NaN, which the step carries like any other)
+    }
+    static __device__ __forceinline__ void partials(const BuildArgs& a, int t, const double* v, double* dR) {
+        const double s = value(a, t, v);
+        dR[1] = v[1] / s; dR[2] = v[2] / s;
+    }
+};
+struct RowSemilinear3d {                                    // gpk.h, GPK_GN_SEMILINEAR3D: rows [d_1 u; d_2 u; d_3 u; psi[u]; u], PDE row N(v0, v1, v2, v3) - f
+    static constexpr int system = GPK_GN_SEMILINEAR3D, k = 3; static constexpr bool has_v0 = true;
+    static __device__ __forceinline__ void partials(const BuildArgs& a, int, const double* v, double* dR) {
+        sl3_dN(a.gq, v[0], v[1], v[2], v[3], &dR[0], &dR[1], &dR[2], &dR[3]);
+    }
+    static __device__ __forceinline__ double value(const BuildArgs& a, int t, const double* v) {
+        return sl3_N(a.gq, v[0], v[1], v[2], v[3]) - a.f[t];
+    }
+};
+
+// The ONE frame of the gradient-unknown systems (GnTraits::grad_k = Row::k), collocation index t: unit entries and F = v_j in the rows of
+// v_j, the PDE row, the unit entry and v_0 in the value row; g on the boundary.  v[] and dR[] are indexed by unrolled constants only: registers.
+template <class Row, class Z>
+__device__ __forceinline__ void gn_build_gradient_rows(const BuildArgs& a, const int t, const Z z) {
+    constexpr int K = Row::k;
+    static_assert(gn_traits(Row::system).grad_k == K && gn_traits(Row::system).v0_free_pde_row == !Row::has_v0, "the PDE row and the record of its system agree");
+    const int Nd = a.Nd;
+    if (t < Nd) {
+        double v[K + 1], dR[K + 1];
+#pragma unroll
+        for (int j = 0; j <= K; ++j) v[j] = z[j * Nd + t];
+        Row::partials(a, t, v, dR);
+#pragma unroll
+        for (int j = 1; j <= K; ++j) putA(a, (j - 1) * Nd + t, j * Nd + t, 1.0);
+        if (Row::has_v0) putA(a, K * Nd + t, t, dR[0]);
+#pragma unroll
+        for (int j = 1; j <= K; ++j) putA(a, K * Nd + t, j * Nd + t, dR[j]);
+        putA(a, (K + 1) * Nd + t, t, 1.0);
+#pragma unroll
+        for (int j = 1; j <= K; ++j) putF(a, (j - 1) * Nd + t, v[j]);
+        putF(a, K * Nd + t, Row::value(a, t, v));
+        putF(a, (K + 1) * Nd + t, v[0]);
+    } else if (t < Nd + a.Nb) putF(a, (K + 2) * Nd + (t - Nd), a.gb[t - Nd]);
+}
 
 // collocation index t: writes the few non-zeros of A(z) and the entries of F(z) it owns
 template <class Z>
@@ -190,53 +317,11 @@ __device__ __forceinline__ void gn_build_rows(const BuildArgs& a, const int t, c
             putF(a, t, nu * v3 + a.f[t] - alpha * v0 * v2);
             putF(a, Nd + t, v2); putF(a, 2 * Nd + t, v3); putF(a, 3 * Nd + t, v0);
         } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
-    } else if (a.system == GPK_GN_EIKONAL) {                // src/PDEs.py:420-428 (F), :441-449 (A)
-        const double eps = a.p0;
-        if (t < Nd) {
-            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t], ft = a.f[t];
-            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0);
-            putA(a, 2 * Nd + t, Nd + t, 2.0 * v1 / eps); putA(a, 2 * Nd + t, 2 * Nd + t, 2.0 * v2 / eps);
-            putA(a, 3 * Nd + t, t, 1.0);
-            putF(a, t, v1); putF(a, Nd + t, v2);
-            putF(a, 2 * Nd + t, -(ft * ft - v1 * v1 - v2 * v2) / eps);
-            putF(a, 3 * Nd + t, v0);
-        } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
-    } else if (a.system == GPK_GN_SEMILINEAR) {             // gpk.h, GPK_GN_SEMILINEAR: the Eikonal rows, PDE row (N(v0, v1, v2) - f) / eps
-        const double eps = a.p0;
-        if (t < Nd) {
-            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t];
-            double Nu, Np, Nq;
-            sl_dN(a.gq, v0, v1, v2, &Nu, &Np, &Nq);
-            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0);
-            putA(a, 2 * Nd + t, t, Nu / eps); putA(a, 2 * Nd + t, Nd + t, Np / eps); putA(a, 2 * Nd + t, 2 * Nd + t, Nq / eps);
-            putA(a, 3 * Nd + t, t, 1.0);
-            putF(a, t, v1); putF(a, Nd + t, v2);
-            putF(a, 2 * Nd + t, (sl_N(a.gq, v0, v1, v2) - a.f[t]) / eps);
-            putF(a, 3 * Nd + t, v0);
-        } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
-    } else if (a.system == GPK_GN_SEMILINEAR3D) {           // gpk.h, GPK_GN_SEMILINEAR3D: rows [d_1 u; d_2 u; d_3 u; psi[u]; u], PDE row N(v0, v1, v2, v3) - f
-        if (t < Nd) {
-            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t], v3 = z[3 * Nd + t];
-            double Nu, N1, N2, N3;
-            sl3_dN(a.gq, v0, v1, v2, v3, &Nu, &N1, &N2, &N3);
-            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0); putA(a, 2 * Nd + t, 3 * Nd + t, 1.0);
-            putA(a, 3 * Nd + t, t, Nu); putA(a, 3 * Nd + t, Nd + t, N1); putA(a, 3 * Nd + t, 2 * Nd + t, N2); putA(a, 3 * Nd + t, 3 * Nd + t, N3);
-            putA(a, 4 * Nd + t, t, 1.0);
-            putF(a, t, v1); putF(a, Nd + t, v2); putF(a, 2 * Nd + t, v3);
-            putF(a, 3 * Nd + t, sl3_N(a.gq, v0, v1, v2, v3) - a.f[t]);
-            putF(a, 4 * Nd + t, v0);
-        } else if (t < Nd + Nb) putF(a, 5 * Nd + (t - Nd), a.gb[t - Nd]);
-    } else if (a.system == GPK_GN_MONGE_AMPERE) {           // gpk.h, GPK_GN_MONGE_AMPERE: rows [D u; M u; Delta u; u], PDE row s = sqrt(v1^2 + v2^2 + 4 f)
-        if (t < Nd) {
-            const double v0 = z[t], v1 = z[Nd + t], v2 = z[2 * Nd + t];
-            const double s = sqrt(v1 * v1 + v2 * v2 + 4.0 * a.f[t]);   // (a negative radicand gives NaN, which the step carries like any other)
-            putA(a, t, Nd + t, 1.0); putA(a, Nd + t, 2 * Nd + t, 1.0);
-            putA(a, 2 * Nd + t, Nd + t, v1 / s); putA(a, 2 * Nd + t, 2 * Nd + t, v2 / s);
-            putA(a, 3 * Nd + t, t, 1.0);
-            putF(a, t, v1); putF(a, Nd + t, v2);
-            putF(a, 2 * Nd + t, s);
-            putF(a, 3 * Nd + t, v0);
-        } else if (t < Nd + Nb) putF(a, 4 * Nd + (t - Nd), a.gb[t - Nd]);
+    } else if (gn_traits(a.system).grad_k != 0) {           // the gradient-unknown form: one frame, the system's PDE row and its k
+        if (a.system == GPK_GN_EIKONAL) gn_build_gradient_rows<RowEikonal>(a, t, z);
+        else if (a.system == GPK_GN_SEMILINEAR) gn_build_gradient_rows<RowSemilinear>(a, t, z);
+        else if (a.system == GPK_GN_MONGE_AMPERE) gn_build_gradient_rows<RowMongeAmpere>(a, t, z);
+        else if (a.system == GPK_GN_SEMILINEAR3D) gn_build_gradient_rows<RowSemilinear3d>(a, t, z);
     } else if (a.system == GPK_GN_DARCY) {                  // src/InverseProblems.py:106-117 (F), :127-143 (A)
         const double gam = a.p0;                            // noise_level
         const int U = 3 * Nd, D = 7 * Nd + Nb;
@@ -379,18 +464,12 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
     return 0;
 }
 
-// the reaction term is one of the family, and only the elliptic systems have one; the semilinear system divides its PDE row by eps
+// the reaction term is one of the family, and only the systems whose record says so have one; a PDE row divided by eps needs a usable eps
 int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
     if (!gpk_nl_valid(p->nonlin)) return gpk_bad_arg(h, "gn: nonlin is not one of GPK_NL_POWER .. GPK_NL_CUBIC");
-    if (p->system == GPK_GN_SEMILINEAR) {
-        if (p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR takes nonlin = 0 only (its nonlinearity is gq_a1 .. gq_c3)");
-        if (!(std::isfinite(p->p0) && p->p0 != 0.0)) return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR needs a finite eps (p0) other than 0");
-    }
-    if (p->system == GPK_GN_SEMILINEAR3D && (p->nonlin != GPK_NL_POWER || p->p2 != 0.0))
-        return gpk_bad_arg(h, "gn: GPK_GN_SEMILINEAR3D takes nonlin = 0 and p2 = 0 only (its nonlinearity is gq_a1 .. gq_c3, p0, p1, pen_lambda)");
-    if (p->system == GPK_GN_MONGE_AMPERE && p->nonlin != GPK_NL_POWER) return gpk_bad_arg(h, "gn: GPK_GN_MONGE_AMPERE takes nonlin = 0 only");
-    if (p->nonlin != GPK_NL_POWER && p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_ELLIPTIC_RELAXED)
-        return gpk_bad_arg(h, "gn: nonlin != GPK_NL_POWER needs GPK_GN_ELLIPTIC or GPK_GN_ELLIPTIC_RELAXED");
+    const GnTraits t = gn_traits(p->system);
+    if (t.no_reaction && (p->nonlin != GPK_NL_POWER || (t.p2_reserved && p->p2 != 0.0))) return gpk_bad_arg(h, t.no_reaction);
+    if (t.bad_eps && !(std::isfinite(p->p0) && p->p0 != 0.0)) return gpk_bad_arg(h, t.bad_eps);
     return 0;
 }
 
@@ -475,28 +554,23 @@ int exact_loss_chain(gpk_handle h, const Dims& d, bool after_main, bool* on_side
     return 0;
 }
 
-// The column layout gpk_gn_step runs a system in (BuildArgs::rev): 1 elliptic systems, 2 Eikonal, 3 Burgers, 4 Darcy on the GEMM-only
-// solve path, 5 the semilinear system in three dimensions, 0 = dense schedule.
+// The column layout gpk_gn_step runs a system in (BuildArgs::rev): GnTraits::lz_layout -- the elliptic systems' layout 1 always, the
+// others when the leading-zero schedule is on, Darcy's layout 4 on the GEMM-only solve path only -- or 0 = dense schedule.
 int step_layout(gpk_handle h, const gpk_gn_problem* p) {
-    if (p->system == GPK_GN_SEMILINEAR3D) return h->tune.eikonal_lz ? 5 : 0;
-    const bool darcy_lz = p->system == GPK_GN_DARCY && h->tune.eikonal_lz && h->tune.use_dinv && p->Dinv && p->Dinv2 && p->dinv_block > 0;
-    return (p->system == GPK_GN_ELLIPTIC || p->system == GPK_GN_ELLIPTIC_RELAXED) ? 1
-         : ((p->system == GPK_GN_EIKONAL || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE) && h->tune.eikonal_lz) ? 2 : (p->system == GPK_GN_BURGERS && h->tune.eikonal_lz) ? 3 : darcy_lz ? 4 : 0;
+    const int lz = gn_traits(p->system).lz_layout;
+    if (lz == 1) return 1;
+    if (!h->tune.eikonal_lz) return 0;
+    if (lz == 4 && !(h->tune.use_dinv && p->Dinv && p->Dinv2 && p->dinv_block > 0)) return 0;
+    return lz;
 }
 
 // The leading-zero profile of [A(z) | F] under that layout, a pure function of the problem and the handle's switches: the closed form
 // with lead = n_z (slope 1/3 for Burgers); for Eikonal on the GEMM-only solve path the exact two-segment profile for the solve and the
 // products (the substitution path keeps the conservative closed form).  Dense for the layouts 0 and 4: Darcy's two factors have a
 // profile each (darcy_u_profile; the a-part's closed form on its own columns), passed where they are used.
-// The semilinear system shares Eikonal's layout 2 but NEVER its two-segment profile: its v0 columns carry N_u / eps in row 2 N_d + t, N_d
-// rows above Eikonal's first entry, which the second segment would skip -- dropping dN/du from H with no other symptom.  Its exact
-// profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row 2 N_d + t = n_z - 1 - c).
-// The Monge-Ampere system has exactly Eikonal's pattern (v0 does not enter its PDE row) and takes the two-segment profile.
-// The semilinear system in three dimensions (layout 5, order v1, v2, v3, v0): the column at position pos holds its first non-zero in row
-// pos -- the 1 of the rows d_k u for the gradient unknowns, N_u in the PDE row 3 N_d + t for v0_t -- so the closed form with lead = n_z is
-// exact, as for the elliptic system.
+// Which systems of layout 2 may take the two-segment profile, and why the others must not: GnTraits::v0_free_pde_row.
 GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
-    if (rev == 2 && (p->system == GPK_GN_EIKONAL || p->system == GPK_GN_MONGE_AMPERE) && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
+    if (rev == 2 && gn_traits(p->system).v0_free_pde_row && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
     return ((rev >= 1 && rev <= 3) || rev == 5) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
@@ -768,7 +842,7 @@ enum class StepProduct { None, SyrkPotrf, Darcy };
 // No side effects.  A mode is chosen only when everything it reads has been prepared; an incomplete preparation falls through to the
 // next line and in the end to Plain.  (The elliptic system has layout 1, and its relaxed form is a system of its own: always Plain.)
 StepMode select_mode(gpk_handle h, const gpk_gn_problem* p, const Dims& d, int rev) {
-    if (!h->tune.structured || p->system == GPK_GN_SEMILINEAR || p->system == GPK_GN_MONGE_AMPERE || p->system == GPK_GN_SEMILINEAR3D) return StepMode::Plain;   // (no structured form yet)
+    if (!h->tune.structured || gn_traits(p->system).no_structured) return StepMode::Plain;   // (no structured form served)
     const bool ops = p->W1 && p->W2 && p->ldw >= d.nz + 1;           // gpk_gn_structured_prepare
     const bool gram = p->G && p->ldg >= d.nz;                        // gpk_gn_gram_prepare
     if (p->system == GPK_GN_ELLIPTIC && ops && p->v0) return gram && p->pvec ? StepMode::GramElliptic : StepMode::StructuredElliptic;
@@ -930,10 +1004,7 @@ extern "C" int gpk_gn_structured_prepare(gpk_handle h, const gpk_gn_problem* p, 
     Dims d;
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
-    if (p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "structured solve: not for the relaxed system");
-    if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR is not served (its PDE row has three z-dependent entries per point)");
-    if (p->system == GPK_GN_SEMILINEAR3D) return gpk_bad_arg(h, "structured solve: GPK_GN_SEMILINEAR3D is not served (its PDE row has four z-dependent entries per point)");
-    if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "structured solve: GPK_GN_MONGE_AMPERE is not served yet (its structured form exists: A(z) = A_1 diag(d(z)) + A_2 as for Eikonal)");
+    if (gn_traits(p->system).no_structured) return gpk_bad_arg(h, gn_traits(p->system).no_structured);
     if (elliptic && !v0) return GPK_ERR_ARG;
     const int nc = d.nz + 1;
     if (lds < nc || ldw < nc) return gpk_bad_arg(h, "structured solve: lds/ldw < nz+1");
@@ -969,10 +1040,8 @@ extern "C" int gpk_gn_gram_prepare(gpk_handle h, const gpk_gn_problem* p, double
     Dims d;
     GPK_TRY(check_prob(h, p, d));
     const bool elliptic = p->system == GPK_GN_ELLIPTIC;
-    if (p->system == GPK_GN_SEMILINEAR) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR is not served (it has no structured form)");
-    if (p->system == GPK_GN_SEMILINEAR3D) return gpk_bad_arg(h, "gram_prepare: GPK_GN_SEMILINEAR3D is not served (it has no structured form)");
-    if (p->system == GPK_GN_MONGE_AMPERE) return gpk_bad_arg(h, "gram_prepare: GPK_GN_MONGE_AMPERE is not served yet (no structured prepare)");
-    if (p->system == GPK_GN_ELLIPTIC_RELAXED || !p->W1 || !p->W2 || (elliptic && !p->v0))
+    if (gn_traits(p->system).no_gram) return gpk_bad_arg(h, gn_traits(p->system).no_gram);
+    if (!p->W1 || !p->W2 || (elliptic && !p->v0))
         return gpk_bad_arg(h, "gram_prepare: needs W1/W2 (and v0 for the elliptic system) of gpk_gn_structured_prepare; not for the relaxed system");
     const int nz = d.nz;
     if (ldg < nz || p->ldw < nz + 1) return gpk_bad_arg(h, "gram_prepare: ldg/ldw");
@@ -1394,6 +1463,7 @@ int gpk_i_gn_exact_loss(gpk_handle h, const gpk_gn_problem* p, const double* z, 
 }
 
 int gpk_i_gn_layout(gpk_handle h, const gpk_gn_problem* p) { return step_layout(h, p); }
+bool gpk_i_gn_sharded(const gpk_gn_problem* p) { return gn_traits(p->system).sharded; }
 GpkLz gpk_i_gn_profile(gpk_handle h, const gpk_gn_problem* p, int rev) {
     Dims d;
     return gn_dims(p, d) == 0 ? step_profile(h, p, d.nz, rev) : GpkLz();

@@ -663,7 +663,7 @@ extern "C" int gpk_mg_gn_step(gpk_mg_handle mg, const gpk_gn_problem* p, double*
     // profile; the a-part contributes the constant H_a and one replicated F column).  The relaxed system is one-GPU only.
     const int rev = gpk_i_gn_layout(h, p);
     const bool darcy = p->system == GPK_GN_DARCY;
-    if ((p->system != GPK_GN_ELLIPTIC && p->system != GPK_GN_EIKONAL && p->system != GPK_GN_BURGERS && !darcy) || rev < 1 || rev > 4 || (darcy != (rev == 4)))
+    if (!gpk_i_gn_sharded(p) || rev < 1 || rev > 4 || (darcy != (rev == 4)))
         return gpk_bad_arg(h, "gpk_mg_gn_step: elliptic, Eikonal, Burgers and Darcy systems only (leading-zero layout)");
     if (!p->Dinv || !S2) return gpk_bad_arg(h, "gpk_mg_gn_step: needs the inverted diagonal blocks (Dinv) and S2");
     if (darcy && (!p->Wa || !p->Ha || !p->Dinv2)) return gpk_bad_arg(h, "gpk_mg_gn_step: the Darcy system needs its cached a-part (gpk_gn_darcy_prepare) and Dinv2");

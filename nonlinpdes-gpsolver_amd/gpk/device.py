@@ -454,29 +454,30 @@ class Context:
         self.synchronize()
         return out
 
-    def _assemble_two_block(self, entry, dim, kernel, kernel_parameter, Xd, Xb, coeffs, nugget, nugget_type, out):
-        """The two-block Gram calls (assemble3d / assemble_bc / assemble_op): points (n, dim) to the device, the library `entry` (its
-        arguments: handle, kernel, points, the device arrays or None of coeffs(Nd, Nb), nugget, Theta, ratio) -> (Theta, trace ratio)."""
+    def _assemble_blocks(self, entry, dim, kernel, kernel_parameter, Xd, Xb, coeffs, nugget, nugget_type, out, rows=2, nratios=None):
+        """The Gram calls of the Gaussian-only layouts (assemble3d / assemble_bc / assemble_op / assemble_op3d: two blocks; assemble_hess,
+        assemble_grad3d: `rows` rows per domain point, N = rows Nd + Nb): points (n, dim) to the device, the library `entry` (its
+        arguments: handle, kernel, points, the device arrays or None of coeffs(Nd, Nb), nugget, Theta, ratios) -> (Theta, the trace ratio
+        of the two-block layouts, or the list of the `nratios` ratios)."""
         require_gaussian_family(kernel, entry.__name__)
         Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, dim) for X in (Xd, Xb))
         Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 2 * Nd + Nb
+        N = rows * Nd + Nb
         dXd, dXb = self.points(Xd, dim), self.points(Xb, dim)
         held = coeffs(Nd, Nb) if coeffs else ()                               # (kept alive until the call has been issued)
         extra = [a.ptr if a is not None else None for a in held]
         T = out if out is not None else DeviceArray(self, N, N)
-        ratio = C.c_double()
+        ratios = (C.c_double * (nratios or 1))()
         kp = (kernel_params3d if dim == 3 else kernel_params)(kernel, kernel_parameter)
-        self._chk(entry(self.h, KERNEL[kernel], kp, dXd.ptr, Nd, dXb.ptr, Nb, *extra, float(nugget), NUGGET[nugget_type], T.ptr, T.ld,
-                        C.byref(ratio)))
+        self._chk(entry(self.h, KERNEL[kernel], kp, dXd.ptr, Nd, dXb.ptr, Nb, *extra, float(nugget), NUGGET[nugget_type], T.ptr, T.ld, ratios))
         self.synchronize()
-        return T, ratio.value
+        return T, (list(ratios) if nratios else ratios[0])
 
     # ---- three space dimensions (gpk_assemble3d, gpk_extend_functionals3d) ----
     def assemble3d(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
         """Gram matrix of the 3-D elliptic layout (Laplacian on Xd, delta on [Xd; Xb]; points (n,3)): (DeviceArray N x N with
         N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any leading dimension >= N)."""
-        return self._assemble_two_block(self.lib.gpk_assemble3d, 3, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out)
+        return self._assemble_blocks(self.lib.gpk_assemble3d, 3, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out)
 
     def extend_functionals3d(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd3', 'laplacian')):
         """Value / derivatives of the 3-D extension at Xt (gpk_extend_functionals3d): a (len(which), Nt) DeviceArray, row k = functional
@@ -487,18 +488,13 @@ class Context:
     # ---- boundary functionals: Neumann / Robin / mixed conditions for the 2-D elliptic layout (gpk_assemble_bc, gpk_extend_functionals_bc) ----
     def _boundary_coeffs(self, bc, Nb):
         """(Nb,3) coefficients (c0, c1, c2) of the boundary functionals on the device, or None (= NULL: all (1,0,0))"""
-        if bc is None:
-            return None
-        bc = np.ascontiguousarray(bc, dtype=np.float64)
-        if bc.shape != (Nb, 3):
-            raise ValueError(f'boundary coefficients must have shape ({Nb}, 3): (c0, c1, c2) per boundary point, got {bc.shape}')
-        return DeviceArray(self, max(Nb, 1), 3, ld=3).upload(bc) if Nb else DeviceArray(self, 1, 3, ld=3)
+        return self._coeff_rows(bc, Nb, 3, 'boundary coefficients', ': (c0, c1, c2) per boundary point')
 
     def assemble_bc(self, kernel, kernel_parameter, Xd, Xb, bc, nugget=0.0, nugget_type='none', out=None):
         """Gram matrix of the 2-D elliptic layout with the functional bc[b] = (c0, c1, c2) -> c0 delta + c1 d/dx1 + c2 d/dx2 at boundary
         point b (bc = None: delta everywhere): (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to
         write into (any leading dimension >= N)."""
-        return self._assemble_two_block(self.lib.gpk_assemble_bc, 2, kernel, kernel_parameter, Xd, Xb,
+        return self._assemble_blocks(self.lib.gpk_assemble_bc, 2, kernel, kernel_parameter, Xd, Xb,
                                         lambda Nd, Nb: (self._boundary_coeffs(bc, Nb),), nugget, nugget_type, out)
 
     def extend_functionals_bc(self, kernel, kernel_parameter, Xt, Xd, Xb, bc, coeff, which=('value', 'd1', 'd2', 'laplacian')):
@@ -510,19 +506,14 @@ class Context:
     # ---- variable-coefficient operator on the domain points of the 2-D elliptic layout (gpk_assemble_op, gpk_extend_functionals_op) ----
     def _domain_coeffs(self, op, Nd):
         """(Nd,6) coefficients (c0, b1, b2, a11, a12, a22) of the domain functionals on the device, or None (= NULL: the Laplacian)"""
-        if op is None:
-            return None
-        op = np.ascontiguousarray(op, dtype=np.float64)
-        if op.shape != (Nd, 6):
-            raise ValueError(f'domain coefficients must have shape ({Nd}, 6): (c0, b1, b2, a11, a12, a22) per domain point, got {op.shape}')
-        return DeviceArray(self, Nd, 6, ld=6).upload(op)
+        return self._coeff_rows(op, Nd, 6, 'domain coefficients', ': (c0, b1, b2, a11, a12, a22) per domain point')
 
     def assemble_op(self, kernel, kernel_parameter, Xd, Xb, op, bc, nugget=0.0, nugget_type='none', out=None):
         """Gram matrix of the 2-D elliptic layout with the functional op[i] = (c0, b1, b2, a11, a12, a22) -> c0 delta + b1 d/dx1 +
         b2 d/dx2 + a11 d2/dx1^2 + a12 d2/dx1dx2 + a22 d2/dx2^2 at domain point i (op = None: the Laplacian) and bc[b] at boundary point b
         as in assemble_bc: (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  out: a DeviceArray to write into (any
         leading dimension >= N)."""
-        return self._assemble_two_block(self.lib.gpk_assemble_op, 2, kernel, kernel_parameter, Xd, Xb,
+        return self._assemble_blocks(self.lib.gpk_assemble_op, 2, kernel, kernel_parameter, Xd, Xb,
                                         lambda Nd, Nb: (self._domain_coeffs(op, Nd), self._boundary_coeffs(bc, Nb)), nugget, nugget_type, out)
 
     def extend_functionals_op(self, kernel, kernel_parameter, Xt, Xd, Xb, op, bc, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
@@ -537,17 +528,8 @@ class Context:
     def assemble_hess(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
         """Gram matrix of the Hessian layout (blocks D, M, Laplacian on Xd, delta on [Xd; Xb]): (DeviceArray N x N with N = 4 Nd + Nb,
         [trace(block k) / trace(block 3) for k = 0, 1, 2]).  out: a DeviceArray to write into (any leading dimension >= N)."""
-        require_gaussian_family(kernel, 'gpk_assemble_hess')
-        Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 2) for X in (Xd, Xb))
-        Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 4 * Nd + Nb
-        dXd, dXb = self.points(Xd), self.points(Xb)
-        T = out if out is not None else DeviceArray(self, N, N)
-        ratios = (C.c_double * 3)()
-        self._chk(self.lib.gpk_assemble_hess(self.h, KERNEL[kernel], kernel_params(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
-                                             float(nugget), NUGGET[nugget_type], T.ptr, T.ld, ratios))
-        self.synchronize()
-        return T, list(ratios)
+        return self._assemble_blocks(self.lib.gpk_assemble_hess, 2, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out,
+                                     rows=4, nratios=3)
 
     def extend_functionals_hess(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
         """Value / derivatives up to order two of the extension on the Hessian layout at Xt (gpk_extend_functionals_hess): a
@@ -556,25 +538,36 @@ class Context:
         return self._extend_functionals('extend_functionals_hess', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_hess, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
 
-    def pde_residual_ma(self, fields, rhs):
-        """Pointwise residual d11 d22 - d12^2 - f of the Monge-Ampere equation (gpk_pde_residual_ma), as an (Nt,) DeviceArray.
-        fields: (3, Nt) d11, d12, d22 of the extension; rhs as for pde_residual."""
-        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
+    def _on_device(self, a, fields=False):
+        """a DeviceArray as it is; a host array uploaded as (rows, Nt) fields or as one vector"""
+        if isinstance(a, DeviceArray):
+            return a
+        return self.array(np.atleast_2d(a) if fields else np.asarray(a, dtype=np.float64).ravel())
+
+    def _pde_residual(self, entry, const, fields, rhs, more=()):
+        """The five pde_residual* calls: the fields (rows, Nt) and the rhs to the device, the library `entry` (its arguments: handle, the
+        constant block `const`, Nt, the fields and their leading dimension, the arguments `more`, rhs, output) -> the (Nt,) DeviceArray."""
+        du = self._on_device(fields, fields=True)
         Nt = du.cols
-        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
+        dr = self._on_device(rhs)
         out = DeviceArray(self, Nt)
-        self._chk(self.lib.gpk_pde_residual_ma(self.h, Nt, du.ptr, du.ld, dr.ptr, out.ptr))
+        self._chk(entry(self.h, *const, Nt, du.ptr, du.ld, *more, dr.ptr, out.ptr))
         self.synchronize()
         return out
 
+    def pde_residual_ma(self, fields, rhs):
+        """Pointwise residual d11 d22 - d12^2 - f of the Monge-Ampere equation (gpk_pde_residual_ma), as an (Nt,) DeviceArray.
+        fields: (3, Nt) d11, d12, d22 of the extension; rhs as for pde_residual."""
+        return self._pde_residual(self.lib.gpk_pde_residual_ma, (), fields, rhs)
+
     # ---- operator and boundary functionals in three dimensions (gpk_assemble_op3d, gpk_extend_functionals_op3d) ----
-    def _coeff_rows(self, c, n, width, what):
-        """(n, width) coefficient rows on the device, or None (= NULL: the library's default functional)"""
+    def _coeff_rows(self, c, n, width, what, per_point=''):
+        """(n, width) coefficient rows on the device (n = 0: a placeholder row), or None (= NULL: the library's default functional)"""
         if c is None:
             return None
         c = np.ascontiguousarray(c, dtype=np.float64)
         if c.shape != (n, width):
-            raise ValueError(f'{what} must have shape ({n}, {width}), got {c.shape}')
+            raise ValueError(f'{what} must have shape ({n}, {width}){per_point}, got {c.shape}')
         return DeviceArray(self, n, width, ld=width).upload(c) if n else DeviceArray(self, 1, width, ld=width)
 
     def _coeffs3(self, op3, bc3):
@@ -586,7 +579,7 @@ class Context:
         point i (op3 = None: the Laplacian) and bc3[b] = (c0, c1, c2, c3) -> c0 delta + c . grad at boundary point b (None: delta):
         (DeviceArray N x N with N = 2 Nd + Nb, trace ratio of block 0).  A mixed coefficient multiplies its mixed derivative once.
         out: a DeviceArray to write into (any leading dimension >= N)."""
-        return self._assemble_two_block(self.lib.gpk_assemble_op3d, 3, kernel, kernel_parameter, Xd, Xb, self._coeffs3(op3, bc3),
+        return self._assemble_blocks(self.lib.gpk_assemble_op3d, 3, kernel, kernel_parameter, Xd, Xb, self._coeffs3(op3, bc3),
                                         nugget, nugget_type, out)
 
     def extend_functionals_op3d(self, kernel, kernel_parameter, Xt, Xd, Xb, op3, bc3, coeff, which=OP3_NAMES):
@@ -601,19 +594,8 @@ class Context:
         """Gram matrix of the 3-D gradient layout (blocks d1, d2, d3, psi on Xd, delta / phi on [Xd; Xb]; op3 and bc3 as for
         assemble_op3d): (DeviceArray N x N with N = 5 Nd + Nb, [trace(block k) / trace(block 4) for k = 0..3]).  out: a DeviceArray to
         write into (any leading dimension >= N)."""
-        require_gaussian_family(kernel, 'gpk_assemble_grad3d')
-        Xd, Xb = (np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3) for X in (Xd, Xb))
-        Nd, Nb = Xd.shape[0], Xb.shape[0]
-        N = 5 * Nd + Nb
-        dXd, dXb = self.points(Xd, 3), self.points(Xb, 3)
-        held = self._coeffs3(op3, bc3)(Nd, Nb)                              # (kept alive until the call has been issued)
-        extra = [a.ptr if a is not None else None for a in held]
-        T = out if out is not None else DeviceArray(self, N, N)
-        ratios = (C.c_double * 4)()
-        self._chk(self.lib.gpk_assemble_grad3d(self.h, KERNEL[kernel], kernel_params3d(kernel, kernel_parameter), dXd.ptr, Nd, dXb.ptr, Nb,
-                                               *extra, float(nugget), NUGGET[nugget_type], T.ptr, T.ld, ratios))
-        self.synchronize()
-        return T, list(ratios)
+        return self._assemble_blocks(self.lib.gpk_assemble_grad3d, 3, kernel, kernel_parameter, Xd, Xb, self._coeffs3(op3, bc3),
+                                     nugget, nugget_type, out, rows=5, nratios=4)
 
     def extend_functionals_grad3d(self, kernel, kernel_parameter, Xt, Xd, Xb, op3, bc3, coeff, which=OP3_NAMES):
         """Value / derivatives up to order two of the extension on the 3-D gradient layout at Xt (gpk_extend_functionals_grad3d): a
@@ -626,61 +608,34 @@ class Context:
         """Pointwise residual -psi_u + N(u0, u1, u2, u3) - f of the 3-D semilinear equation with gq8 = (a1, a2, a3, b1, b2, b3, c1, c3)
         (gpk_pde_residual_sl3d), as an (Nt,) DeviceArray.  fields: (4, Nt) value, d1, d2, d3; psi_u: (Nt,) psi[u] at the test points;
         rhs as for pde_residual."""
-        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
-        Nt = du.cols
-        dp = psi_u if isinstance(psi_u, DeviceArray) else self.array(np.asarray(psi_u, dtype=np.float64).ravel())
-        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
-        out = DeviceArray(self, Nt)
         gq8 = [float(v) for v in gq8]
         if len(gq8) != 8:
             raise ValueError(f'gq8: the eight coefficients (a1, a2, a3, b1, b2, b3, c1, c3), got {len(gq8)}')
-        self._chk(self.lib.gpk_pde_residual_sl3d(self.h, (C.c_double * 8)(*gq8), Nt, du.ptr, du.ld, dp.ptr, dr.ptr, out.ptr))
-        self.synchronize()
-        return out
+        dp = self._on_device(psi_u)
+        return self._pde_residual(self.lib.gpk_pde_residual_sl3d, ((C.c_double * 8)(*gq8),), fields, rhs, (dp.ptr,))
 
     def pde_residual(self, system, params, fields_u, fields_a, rhs):
         """Pointwise residual of the equation (gpk_pde_residual) as an (Nt,) DeviceArray.  fields_u: (4, Nt) DeviceArray or host array
         with rows value, d1, d2, laplacian (Burgers: value, u_t, u_x, u_xx); fields_a: (3, Nt) value, d1, d2 of a (Darcy_flow2d only,
         else None); params: the equation's _gn_params() (its first two entries are used); rhs: f at the test points."""
-        du = fields_u if isinstance(fields_u, DeviceArray) else self.array(np.atleast_2d(fields_u))
-        da = None
-        if fields_a is not None:
-            da = fields_a if isinstance(fields_a, DeviceArray) else self.array(np.atleast_2d(fields_a))
-        Nt = du.cols
-        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
-        out = DeviceArray(self, Nt)
+        da = self._on_device(fields_a, fields=True) if fields_a is not None else None
         p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]]) if params is not None else None
-        self._chk(self.lib.gpk_pde_residual(self.h, SYSTEM[system], p, Nt, du.ptr, du.ld, da.ptr if da is not None else None,
-                                            da.ld if da is not None else 0, dr.ptr, out.ptr))
-        self.synchronize()
-        return out
+        return self._pde_residual(self.lib.gpk_pde_residual, (SYSTEM[system], p), fields_u, rhs, (da.ptr, da.ld) if da is not None else (None, 0))
 
     def pde_residual_nl(self, nonlin, params, fields_u, rhs):
         """Pointwise residual -u3 + tau(u0) - f of the elliptic equation with the reaction term `nonlin` (a GPK_NL_* id or its name in
         NONLIN) and params = (p0, p1, p2) (gpk_pde_residual_nl), as an (Nt,) DeviceArray.  fields_u, rhs as for pde_residual."""
-        du = fields_u if isinstance(fields_u, DeviceArray) else self.array(np.atleast_2d(fields_u))
-        Nt = du.cols
-        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
-        out = DeviceArray(self, Nt)
         p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]])
         kind = NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)
-        self._chk(self.lib.gpk_pde_residual_nl(self.h, kind, p, Nt, du.ptr, du.ld, dr.ptr, out.ptr))
-        self.synchronize()
-        return out
+        return self._pde_residual(self.lib.gpk_pde_residual_nl, (kind, p), fields_u, rhs)
 
     def pde_residual_sl(self, eps, gq, fields, rhs):
         """Pointwise residual -eps u3 + N(u0, u1, u2) - f of the semilinear equation with gq = (a1, a2, b, c1, c3)
         (gpk_pde_residual_sl), as an (Nt,) DeviceArray.  fields: (4, Nt) value, d1, d2, laplacian; rhs as for pde_residual."""
-        du = fields if isinstance(fields, DeviceArray) else self.array(np.atleast_2d(fields))
-        Nt = du.cols
-        dr = rhs if isinstance(rhs, DeviceArray) else self.array(np.asarray(rhs, dtype=np.float64).ravel())
-        out = DeviceArray(self, Nt)
         gq = [float(v) for v in gq]
         if len(gq) != 5:
             raise ValueError(f'gq: the five coefficients (a1, a2, b, c1, c3), got {len(gq)}')
-        self._chk(self.lib.gpk_pde_residual_sl(self.h, float(eps), (C.c_double * 5)(*gq), Nt, du.ptr, du.ld, dr.ptr, out.ptr))
-        self.synchronize()
-        return out
+        return self._pde_residual(self.lib.gpk_pde_residual_sl, (float(eps), (C.c_double * 5)(*gq)), fields, rhs)
 
     def error_metrics(self, truth, approx):
         """(|truth - approx| as a numpy array, its maximum, sqrt(sum of squares / n)) computed on the device (gpk_error_metrics);

@@ -68,6 +68,7 @@ class _GPEquation(object):
     _blocks_per_point = 1       # unknown groups per collocation point
     _dim = 2                    # columns of a point
     _structured_optin = True    # _problem() honours GPK_STRUCTURED
+    _zero_start = False         # GN_method accepts initial_sol='zero'
     _bad_nugget_type = 'the reference leaves self.Theta unset here'
 
     # ---- user data -------------------------------------------------------------------------------------------------
@@ -241,6 +242,8 @@ class _GPEquation(object):
             if initial_sol.shape != (n,):
                 raise ValueError(f'initial_sol: {initial_sol.shape} values for {n} unknowns')
             return onp.array(initial_sol, dtype=onp.float64)
+        if self._zero_start and isinstance(initial_sol, str) and initial_sol == 'zero':
+            return onp.zeros(n)
         if initial_sol == 'rdm':
             return random.normal(0.0, 1.0, (n))
         raise UnboundLocalError("local variable 'sol' referenced before assignment")   # as the reference
@@ -312,6 +315,14 @@ class _GPEquation(object):
         self.loss_hist = loss_hist
         self._z_star = (prob, z.download())                   # the final iterate and the system it belongs to (posterior_variance)
         return self._z_star[1]
+
+    def _gn_solve(self, n_unknowns, max_iter, step_size, initial_sol, print_hist, problem=None, finish=None):
+        """what every GN_method does: the start, the iteration on the device, then (sol_vec, sol_sampled_pts) of the final iterate from the
+        class's _sol_vec.  problem / finish: the relaxed formulation's own system and closing step in place of _problem / _sol_vec."""
+        sol = self._initial(initial_sol, n_unknowns)
+        self.init_sol = sol
+        sol = self._gn_iterate((problem or self._problem)(), sol, max_iter, step_size, print_hist)
+        self.sol_vec, self.sol_sampled_pts = (finish or self._sol_vec)(sol)
 
     def extend_sol(self, X_test):
         ctx = get_context()
@@ -635,11 +646,10 @@ class _EllipticEquation(_GPEquation):
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
         """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        self.sol_vec = onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g])
-        self.sol_sampled_pts = sol
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
+
+    def _sol_vec(self, sol):
+        return onp.concatenate([self._tau().tau(sol) - self.rhs_f, sol, self.bdy_g]), sol
 
     # ---- the solution away from the collocation points -------------------------------------------------------------------------------
     def extend_sol(self, X_test):
@@ -832,11 +842,8 @@ class Nonlinear_elliptic2d(_EllipticEquation):
     def GN_relaxed_method(self, max_iter=3, step_size=1, initial_sol='rdm', pen_lambda=1e-10, print_hist=True):
         """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
         print(f'Relaxed approach: penalization parameter = {pen_lambda}')
-        sol = self._initial(initial_sol, 2 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._relaxed_problem(pen_lambda), sol, max_iter, step_size, print_hist)
-        self.sol_vec = onp.concatenate([sol, self.bdy_g])
-        self.sol_sampled_pts = sol[self.N_domain:]
+        self._gn_solve(2 * self.N_domain, max_iter, step_size, initial_sol, print_hist, problem=lambda: self._relaxed_problem(pen_lambda),
+                       finish=lambda sol: (onp.concatenate([sol, self.bdy_g]), sol[self.N_domain:]))
 
 
 class Nonlinear_elliptic3d(_EllipticEquation):
@@ -957,16 +964,41 @@ class Burgers(_GPEquation):
 
     def GN_method(self, max_iter=10, step_size=1, initial_sol='rdm', print_hist=True):
         """initial_sol: 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, 3 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
+
+    def _sol_vec(self, sol):
         Nd = self.N_domain
         v0, v2, v3 = sol[:Nd], sol[Nd:2 * Nd], sol[2 * Nd:]
-        self.sol_vec = onp.concatenate((self.nu * v3 + self.rhs_f - self.alpha * v0 * v2, v2, v3, v0, self.bdy_g), axis=0)
-        self.sol_sampled_pts = v0
+        return onp.concatenate((self.nu * v3 + self.rhs_f - self.alpha * v0 * v2, v2, v3, v0, self.bdy_g), axis=0), v0
 
 
-class Eikonal(_GPEquation):
+class _GradientUnknowns(object):
+    """Mixin of the equations whose unknowns per domain point are the value v_0 and k further fields v_1 .. v_k (derivatives of u) that
+    have Gram rows of their own: _blocks_per_point = k + 1, unknowns [v_0 | v_1 | .. | v_k], rows [v_1; ..; v_k; PDE row; v_0; g] --
+    Eikonal, Semilinear2d, MongeAmpere2d (k = 2) and Semilinear3d (k = 3).  A class says what its PDE row is, in two hooks:
+    _pde_row(v) at an iterate and _pde_row_linearised(v, o), the row linearised at the iterate o and evaluated at v (v, o: tuples
+    (v_0, .., v_k)).  Everything else about its Gauss-Newton iteration is written here, once."""
+    _zero_start = True
+
+    def _split(self, z):
+        Nd, k = self.N_domain, self._blocks_per_point - 1
+        return tuple(z[j * Nd:(j + 1) * Nd] for j in range(k)) + (z[k * Nd:],)
+
+    def GN_loss(self, z, z_old):
+        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
+        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
+        v = self._split(z)
+        return self._tri_loss(onp.concatenate([*v[1:], self._pde_row_linearised(v, self._split(z_old)), v[0], self.bdy_g]))
+
+    def Hessian_GN(self, z, z_old):
+        return self._hessian(z_old)          # hessian(GN_loss)(z, z_old) does not depend on z (quadratic in z)
+
+    def _sol_vec(self, sol):
+        v = self._split(sol)
+        return onp.concatenate([*v[1:], self._pde_row(v), v[0], self.bdy_g]), v[0]
+
+
+class Eikonal(_GradientUnknowns, _GPEquation):
     """|grad u|^2 = f^2 + eps*Delta u (reference src/PDEs.py:352-505)."""
     _layout = 'Eikonal'
     _system = 'Eikonal'
@@ -984,35 +1016,20 @@ class Eikonal(_GPEquation):
     def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.2, nugget=1e-8, nugget_type='adaptive'):
         self._assemble(kernel, kernel_parameter, nugget, nugget_type)     # the reference does not store `ratio` here
 
-    def GN_loss(self, z, z_old):
-        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        Nd = self.N_domain
-        v1o, v2o = z_old[Nd:2 * Nd], z_old[2 * Nd:]
-        v0, v1, v2 = z[:Nd], z[Nd:2 * Nd], z[2 * Nd:]
-        v3 = -(self.rhs_f ** 2 - 2 * v1 * v1o - 2 * v2 * v2o) / self.eps
-        return self._tri_loss(onp.concatenate([v1, v2, v3, v0, self.bdy_g]))
+    def _pde_row(self, v):
+        _, v1, v2 = v
+        return -(self.rhs_f ** 2 - v1 ** 2 - v2 ** 2) / self.eps
 
-    def Hessian_GN(self, z, z_old):
-        return self._hessian(z_old)
-
-    def _initial(self, initial_sol, n):
-        if isinstance(initial_sol, str) and initial_sol == 'zero':
-            return onp.zeros(n)
-        return super()._initial(initial_sol, n)
+    def _pde_row_linearised(self, v, o):
+        (_, v1, v2), (_, v1o, v2o) = v, o
+        return -(self.rhs_f ** 2 - 2 * v1 * v1o - 2 * v2 * v2o) / self.eps      # the reference's spelling (src/PDEs.py:441-449)
 
     def GN_method(self, max_iter=3, step_size=1, initial_sol='rdm', print_hist=True):
         """initial_sol: 'rdm' (standard normal draw) or 'zero', or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, 3 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        Nd = self.N_domain
-        v0, v1, v2 = sol[:Nd], sol[Nd:2 * Nd], sol[2 * Nd:]
-        v3 = -(self.rhs_f ** 2 - v1 ** 2 - v2 ** 2) / self.eps
-        self.sol_vec = onp.concatenate([v1, v2, v3, v0, self.bdy_g])
-        self.sol_sampled_pts = v0
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
 
 
-class Semilinear2d(_GPEquation):
+class Semilinear2d(_GradientUnknowns, _GPEquation):
     """-eps Laplace(u) + N(u, grad u) = f on a rectangle, u = g on its boundary, with the gradient-dependent nonlinearity
     N(u, p, q) = u (a1 p + a2 q) + b (p^2 + q^2) + c1 u + c3 u^3 (src/nonlinearity.py, GradientNonlinearity): steady viscous Burgers /
     convection, viscous Hamilton-Jacobi and stationary KPZ, the regularised Eikonal equation (b = 1, f -> f^2), Allen-Cahn-type reaction
@@ -1047,43 +1064,24 @@ class Semilinear2d(_GPEquation):
         """kernel: Gaussian, anisotropic_Gaussian, Matern52, Matern72 or Matern92 (the Eikonal layout takes all five)"""
         self._assemble(kernel, kernel_parameter, nugget, nugget_type)
 
-    def _split(self, z):
-        Nd = self.N_domain
-        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:]
+    def _pde_row(self, v):
+        return (self.nonlinearity.N(*v) - self.rhs_f) / self.eps
 
-    def GN_loss(self, z, z_old):
-        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
-        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        v0, v1, v2 = self._split(z)
-        u, p, q = self._split(z_old)
+    def _pde_row_linearised(self, v, o):
+        (v0, v1, v2), (u, p, q) = v, o
         Nu, Np, Nq = self.nonlinearity.dN(u, p, q)
-        v3 = (self.nonlinearity.N(u, p, q) + Nu * (v0 - u) + Np * (v1 - p) + Nq * (v2 - q) - self.rhs_f) / self.eps
-        return self._tri_loss(onp.concatenate([v1, v2, v3, v0, self.bdy_g]))
-
-    def Hessian_GN(self, z, z_old):
-        return self._hessian(z_old)
-
-    def _initial(self, initial_sol, n):
-        if isinstance(initial_sol, str) and initial_sol == 'zero':
-            return onp.zeros(n)
-        return super()._initial(initial_sol, n)
+        return (self.nonlinearity.N(u, p, q) + Nu * (v0 - u) + Np * (v1 - p) + Nq * (v2 - q) - self.rhs_f) / self.eps
 
     def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
         """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, 3 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        v0, v1, v2 = self._split(sol)
-        v3 = (self.nonlinearity.N(v0, v1, v2) - self.rhs_f) / self.eps
-        self.sol_vec = onp.concatenate([v1, v2, v3, v0, self.bdy_g])
-        self.sol_sampled_pts = v0
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
 
     def _residual(self, fields_u, fields_a, rhs):
         """-eps Laplace(u) + N(u, grad u) - f on rows of the extension (gpk_pde_residual_sl)"""
         return get_context().pde_residual_sl(self.eps, self.nonlinearity.params, fields_u, rhs).download().reshape(-1)
 
 
-class MongeAmpere2d(_GPEquation):
+class MongeAmpere2d(_GradientUnknowns, _GPEquation):
     """det D^2 u = f (f > 0) on a rectangle, u = g on its boundary: the Monge-Ampere equation, convex solution.  Fully nonlinear (the
     equation is nonlinear in the second derivatives), no counterpart in the reference.  Solved in the convex-branch form
         Laplace(u) = sqrt((D u)^2 + (M u)^2 + 4 f),   D = d_11 - d_22,  M = 2 d_12      ((Laplace u)^2 = (D u)^2 + (M u)^2 + 4 det D^2 u)
@@ -1117,39 +1115,21 @@ class MongeAmpere2d(_GPEquation):
     def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
         return ctx.assemble_hess(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
 
-    def _split(self, z):
-        Nd = self.N_domain
-        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:]
-
     def _root(self, v1, v2):
         with onp.errstate(invalid='ignore'):
             return onp.sqrt(v1 * v1 + v2 * v2 + 4.0 * self.rhs_f)
 
-    def GN_loss(self, z, z_old):
-        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
-        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        v0, v1, v2 = self._split(z)
-        _, p, q = self._split(z_old)
+    def _pde_row(self, v):
+        return self._root(v[1], v[2])
+
+    def _pde_row_linearised(self, v, o):
+        (_, v1, v2), (_, p, q) = v, o
         s = self._root(p, q)
-        v3 = s + (p * (v1 - p) + q * (v2 - q)) / s
-        return self._tri_loss(onp.concatenate([v1, v2, v3, v0, self.bdy_g]))
-
-    def Hessian_GN(self, z, z_old):
-        return self._hessian(z_old)
-
-    def _initial(self, initial_sol, n):
-        if isinstance(initial_sol, str) and initial_sol == 'zero':
-            return onp.zeros(n)
-        return super()._initial(initial_sol, n)
+        return s + (p * (v1 - p) + q * (v2 - q)) / s
 
     def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
         """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, 3 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        v0, v1, v2 = self._split(sol)
-        self.sol_vec = onp.concatenate([v1, v2, self._root(v1, v2), v0, self.bdy_g])
-        self.sol_sampled_pts = v0
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
 
     def extend_sol(self, X_test):
         ctx = get_context()
@@ -1183,7 +1163,7 @@ class MongeAmpere2d(_GPEquation):
         return 'MongeAmpere2d: gpk_assemble_cross has no rectangular evaluator for the Hessian layout yet'
 
 
-class Semilinear3d(Nonlinear_elliptic3d):
+class Semilinear3d(_GradientUnknowns, Nonlinear_elliptic3d):
     """-psi[u] + N(u, grad u) = f on a box in R^3, B u = g on its faces, with the gradient-dependent nonlinearity
     N(u, g) = u (a1 g1 + a2 g2 + a3 g3) + b1 g1^2 + b2 g2^2 + b3 g3^2 + c1 u + c3 u^3 (src/nonlinearity.py, GradientNonlinearity3d): the
     3-D counterpart of Semilinear2d -- viscous Burgers / convection, viscous Hamilton-Jacobi and KPZ, the regularised Eikonal equation --
@@ -1254,35 +1234,16 @@ class Semilinear3d(Nonlinear_elliptic3d):
         self.ratio = list(self._assemble(kernel, kernel_parameter, nugget, nugget_type)[:4])
 
     # ---- Gauss-Newton ------------------------------------------------------------------------------------------------------------------
-    def _split(self, z):
-        Nd = self.N_domain
-        return z[:Nd], z[Nd:2 * Nd], z[2 * Nd:3 * Nd], z[3 * Nd:]
+    def _pde_row(self, v):
+        return self.nonlinearity.N(*v) - self.rhs_f
 
-    def GN_loss(self, z, z_old):
-        """the quadratic model of the loss at z_old, evaluated at z: ||L^{-1} (F(z_old) + A(z_old) (z - z_old))||^2"""
-        z = onp.asarray(z, float); z_old = onp.asarray(z_old, float)
-        v = self._split(z)
-        o = self._split(z_old)
+    def _pde_row_linearised(self, v, o):
         d = self.nonlinearity.dN(*o)
-        row = self.nonlinearity.N(*o) + sum(dk * (vk - ok) for dk, vk, ok in zip(d, v, o)) - self.rhs_f
-        return self._tri_loss(onp.concatenate([v[1], v[2], v[3], row, v[0], self.bdy_g]))
-
-    def Hessian_GN(self, z, z_old):
-        return self._hessian(z_old)
-
-    def _initial(self, initial_sol, n):
-        if isinstance(initial_sol, str) and initial_sol == 'zero':
-            return onp.zeros(n)
-        return super()._initial(initial_sol, n)
+        return self.nonlinearity.N(*o) + sum(dk * (vk - ok) for dk, vk, ok in zip(d, v, o)) - self.rhs_f
 
     def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
         """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
-        sol = self._initial(initial_sol, 4 * self.N_domain)
-        self.init_sol = sol
-        sol = self._gn_iterate(self._problem(), sol, max_iter, step_size, print_hist)
-        v0, v1, v2, v3 = self._split(sol)
-        self.sol_vec = onp.concatenate([v1, v2, v3, self.nonlinearity.N(v0, v1, v2, v3) - self.rhs_f, v0, self.bdy_g])
-        self.sol_sampled_pts = v0
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
 
     # ---- residual ----------------------------------------------------------------------------------------------------------------------
     def PDE_residual(self, X_test, coeffs_t=None):

@@ -1,6 +1,7 @@
 """The surface of the equation classes, pinned (no GPU): public names, signatures and the class attributes the device layer is
 addressed with, against tests/golden/pdes_surface.json (written by tests/golden/gen/make_pdes_surface.py before the two elliptic
-classes were put on one base).  A refactoring of src/PDEs.py must reproduce it exactly."""
+classes were put on one base; Semilinear2d, MongeAmpere2d and Semilinear3d added before the Gauss-Newton methods of the classes were
+put on one driver and one mixin, the five earlier entries unchanged).  A refactoring of src/PDEs.py must reproduce it exactly."""
 import inspect
 import json
 import os
@@ -15,7 +16,8 @@ OPTIONAL_ATTRS = ('_op_names', '_BC')
 def _classes():
     from src import InverseProblems, PDEs
     return {'Nonlinear_elliptic2d': PDEs.Nonlinear_elliptic2d, 'Nonlinear_elliptic3d': PDEs.Nonlinear_elliptic3d,
-            'Burgers': PDEs.Burgers, 'Eikonal': PDEs.Eikonal, 'Darcy_flow2d': InverseProblems.Darcy_flow2d}
+            'Burgers': PDEs.Burgers, 'Eikonal': PDEs.Eikonal, 'Darcy_flow2d': InverseProblems.Darcy_flow2d,
+            'Semilinear2d': PDEs.Semilinear2d, 'MongeAmpere2d': PDEs.MongeAmpere2d, 'Semilinear3d': PDEs.Semilinear3d}
 
 
 def surface():
