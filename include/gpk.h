@@ -52,7 +52,7 @@ enum { GPK_KERNEL_GAUSSIAN = 0, GPK_KERNEL_ANISOTROPIC = 1, GPK_KERNEL_MATERN52 
 enum { GPK_NUGGET_NONE = 0, GPK_NUGGET_IDENTITY = 1, GPK_NUGGET_ADAPTIVE = 2 };
 /* Gauss-Newton systems (measurement vector F(z) and Jacobian A(z) of each equation class) */
 enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY = 3, GPK_GN_ELLIPTIC_RELAXED = 4, GPK_GN_SEMILINEAR = 5, GPK_GN_MONGE_AMPERE = 6,
-       GPK_GN_SEMILINEAR3D = 7 };
+       GPK_GN_SEMILINEAR3D = 7, GPK_GN_QUASILINEAR = 9 };   /* (8 is not a system id: it stays invalid, -9001) */
 /* GPK_GN_MONGE_AMPERE (no counterpart in the reference; DESIGN.md section K, "Fully nonlinear: Monge-Ampere"):
  *   det D^2 u = f, f > 0, convex branch, in the form  Delta u = sqrt((D u)^2 + (M u)^2 + 4 f),  D = d_11 - d_22,  M = 2 d_12
  * ((Delta u)^2 = (D u)^2 + (M u)^2 + 4 det D^2 u), on the rows of gpk_assemble_hess ([D u; M u; Delta u; u] per domain point, then the
@@ -82,6 +82,25 @@ enum { GPK_GN_ELLIPTIC = 0, GPK_GN_BURGERS = 1, GPK_GN_EIKONAL = 2, GPK_GN_DARCY
  * gpk_gn_worksize, gpk_gn_build(_rev), gpk_gn_measurement, gpk_gn_loss, gpk_gn_hessian_grad, gpk_gn_step, gpk_gn_direction, the line
  * search, gpk_posterior_prepare and gpk_log_evidence; gpk_gn_structured_prepare, gpk_gn_gram_prepare and gpk_mg_gn_step on more than one
  * GPU refuse it (-9001, named in gpk_last_error). */
+/* GPK_GN_QUASILINEAR (no counterpart in the reference; DESIGN.md section K, "Quasilinear equations: the 2-jet layout"):
+ *   a second-order equation in the plane whose second-order coefficients depend on grad u, solved for the Laplacian:  Delta u = G(x; v),
+ * on the rows of gpk_assemble_jet2 ([d_1 u; d_2 u; D u; M u; Delta u; u] per domain point, D = d_11 - d_22, M = 2 d_12, then the boundary
+ * values), unknowns z = [v0 = u | v1 = d_1 u | v2 = d_2 u | v3 = D u | v4 = M u], n_z = 5 N_d, N = 6 N_d + N_b, one factor:
+ *   F(z) = [v1; v2; v3; v4; G(x; v); v0; g],   A(z): 1 at (t, v1_t), (N_d + t, v2_t), (2 N_d + t, v3_t), (3 N_d + t, v4_t), (5 N_d + t, v0_t)
+ *   and dG/dv0 .. dG/dv4 at (4 N_d + t, v0_t / v1_t / v2_t / v3_t / v4_t) -- the v0 entry is written for every kind, also where it is 0.
+ * The equation kind travels in `nonlin` as a GPK_QL_* id (read as such for this system only), its parameters in p0, p1, p2; rhs_f = f.
+ * With p = v1, q = v2, g^2 = p^2 + q^2, W^2 = 1 + g^2, Q = v3 (p^2 - q^2) + 2 p q v4:
+ *   GPK_QL_MEAN_CURVATURE  (p0 = kappa)          div(grad u / sqrt(1 + |grad u|^2)) = f + kappa u      G = (2 W^3 (f + kappa v0) + Q) / (1 + W^2)
+ *   GPK_QL_P_LAPLACE       (p0 = m, p1 = delta)  div((delta^2 + |grad u|^2)^((m-2)/2) grad u) = f      G = (2 f (delta^2 + g^2)^((4-m)/2) - (m - 2) Q) / (2 delta^2 + m g^2)
+ *   GPK_QL_GAUSS_CURVATURE (p0 = e)              det D^2 u = f (1 + |grad u|^2)^e, convex branch       G = sqrt(v3^2 + v4^2 + 4 f W^(2e))
+ * (m = 2: Poisson's equation, a linear system; e = 0: GPK_GN_MONGE_AMPERE's root).  Both denominators are positive at every iterate and
+ * the zero start is admissible; a negative radicand gives NaN, carried like any other.  An unknown kind, a parameter that is not finite,
+ * m <= 0 or delta <= 0: -9001, nothing is launched.  gpk_gn_step runs it in the leading-zero layout with the unknowns in the order v1, v2,
+ * v3, v4, v0: the column at position pos starts in row pos (dG/dv0 in the PDE row 4 N_d + t), one slope-1 staircase.  Served by
+ * gpk_gn_dims, gpk_gn_worksize, gpk_gn_build(_rev), gpk_gn_measurement, gpk_gn_loss, gpk_gn_hessian_grad, gpk_gn_step, gpk_gn_direction,
+ * the line search, gpk_posterior_prepare and gpk_log_evidence; gpk_gn_structured_prepare, gpk_gn_gram_prepare and gpk_mg_gn_step refuse
+ * it (-9001, named in gpk_last_error). */
+enum { GPK_QL_MEAN_CURVATURE = 0, GPK_QL_P_LAPLACE = 1, GPK_QL_GAUSS_CURVATURE = 2 };
 /* Reaction term tau(u) of the elliptic systems, -psi[u] + tau(u) = f ("Reaction terms"); parameters p0, p1, p2:
  *   POWER  p0 pow(u, p1)              (alpha u^m: the reference's equation, and what a zeroed gpk_gn_problem means)
  *   EXP    p0 exp(p1 u)               SINH   p0 sinh(p1 u)              SIN   p0 sin(p1 u)
@@ -124,7 +143,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_grad3d call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_jet2 / gpk_assemble_grad3d call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -188,6 +207,16 @@ int gpk_pde_residual_ma(gpk_handle h, int Nt, const double* fields, int ldf, con
  * ldf < Nt: -9001. */
 int gpk_pde_residual_sl3d(gpk_handle h, const double* host_gq8, int Nt, const double* fields, int ldf, const double* psi_u,
                           const double* rhs, double* out);
+/* The same for the equations of GPK_GN_QUASILINEAR in their DIVERGENCE / DETERMINANT form (not Delta u - G), kind = GPK_QL_*,
+ * host_params3 = (p0, p1, p2) as in gpk_gn_problem; rows 0..5 of fields (ld ldf >= Nt) = value, d1, d2, d11, d12, d22 of the extension
+ * (gpk_extend_functionals_jet2).  With T = u1^2 u11 + 2 u1 u2 u12 + u2^2 u22, g^2 = u1^2 + u2^2:
+ *   MEAN_CURVATURE   ((1 + g^2) Delta u - T) / (1 + g^2)^(3/2) - (f + kappa u)
+ *   P_LAPLACE        (delta^2 + g^2)^((m-4)/2) ((delta^2 + g^2) Delta u + (m - 2) T) - f
+ *   GAUSS_CURVATURE  (u11 u22 - u12^2) - f (1 + g^2)^e
+ * One fixed order of operations, no contraction: a repeated call gives bit-identical output.  A kind or parameters the system refuses,
+ * NULL pointers, Nt <= 0, ldf < Nt: -9001. */
+int gpk_pde_residual_ql(gpk_handle h, int kind, const double* host_params3, int Nt, const double* fields, int ldf, const double* rhs,
+                        double* out);
 /* ---- three space dimensions: the nonlinear elliptic equation on a box in R^3 (no reference call site: the reference's assembly is written
  *      for (n,2) points; the method is the same -- DESIGN.md section K, "Three dimensions").  Points are (n,3) row-major, contiguous.
  *      host_kparams: Gaussian {sigma} (p_k = 1/sigma^2 on all three axes); anisotropic {sigma_1, sigma_2, sigma_3} (p_k = 2/sigma_k^2).
@@ -278,6 +307,25 @@ int gpk_assemble_hess(gpk_handle h, int kernel, const double* host_kparams, cons
  * is functional-major, row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.  Fixed
  * reduction order: a repeated call gives bit-identical output, and a row has the same bits whichever other rows are requested. */
 int gpk_extend_functionals_hess(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                                const double* Xd, int Nd, const double* Xb, int Nb,
+                                const double* coeff, int fmask, double* out, int ldo);
+/* ---- 2-jet layout: the first AND second derivatives of u at the domain points as separate row blocks (DESIGN.md section K,
+ *      "Quasilinear equations: the 2-jet layout").  No reference call site.  Block 0 = d_1, block 1 = d_2, block 2 = D = d_11 - d_22,
+ *      block 3 = M = 2 d_12, block 4 = Laplacian, each on the Nd domain points; block 5 = delta on the Nd+Nb domain and boundary points.
+ *      N = 6Nd+Nb, Theta N x N, ld >= N: gpk_potrf, gpk_potrs and the GPK_GN_QUASILINEAR system apply to it.  Blocks 2..5 hold the
+ *      entries of gpk_assemble_hess for the same points.  Theta is symmetric to the bit.  Kernels: Gaussian and anisotropic Gaussian
+ *      (any other id: -9001).  host_kparams, Xd, Xb as gpk_assemble.  Nugget as gpk_assemble_hess: adaptive = nugget * trace(block k) /
+ *      trace(block 5) on the blocks 0..4, nugget on block 5.  host_ratios5 (five doubles, may be NULL) = those ratios, with the values at d = 0
+ *        <d_k,d_k> = p_k,   <D,D> = 3 p1^2 - 2 p1 p2 + 3 p2^2,   <M,M> = 4 p1 p2,   <Lap,Lap> = 3 p1^2 + 2 p1 p2 + 3 p2^2,   <delta,delta> = 1,
+ *      written for every nugget type.  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte
+ *      stores otherwise, with the same values; nothing outside the N x N view is written); the launch is timed like gpk_assemble's
+ *      when the per-phase timing is on (gpk_prof_read_assembly).  Bad arguments: -9001, named in gpk_last_error. */
+int gpk_assemble_jet2(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                      double nugget, int nugget_type, double* Theta, int ld, double* host_ratios5);
+/* The six monomial derivatives of the extension on the 2-jet layout at test points Xt (Nt,2), matrix-free: coeff (6Nd+Nb) =
+ * Theta^{-1} sol_vec with the Theta of gpk_assemble_jet2.  fmask, out, ldo and the contract (fixed reduction order, a row's bits do not
+ * depend on the other rows requested) as gpk_extend_functionals_hess. */
+int gpk_extend_functionals_jet2(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                                 const double* Xd, int Nd, const double* Xb, int Nb,
                                 const double* coeff, int fmask, double* out, int ldo);
 /* ---- Operator and boundary functionals in three dimensions ("Operator and boundary functionals in three dimensions"):
@@ -404,7 +452,7 @@ typedef struct {
     int system;              /* GPK_GN_* */
     int Nd, Nb, Ndata;
     double p0, p1;           /* ELLIPTIC(_RELAXED): alpha, m   BURGERS: alpha, nu   EIKONAL: eps, -   DARCY: noise_level, -   SEMILINEAR: eps, -   MONGE_AMPERE: -, -
-                              * SEMILINEAR3D: a3, b2 (the coefficients of u g3 and of g2^2) */
+                              * SEMILINEAR3D: a3, b2 (the coefficients of u g3 and of g2^2)   QUASILINEAR: the first two parameters of its GPK_QL_* kind */
     double pen_lambda;       /* ELLIPTIC_RELAXED: the penalty   SEMILINEAR3D: b3 (the coefficient of g3^2) */
     const double* rhs_f;     /* (Nd,)  */
     const double* bdy_g;     /* (Nb,)  */
@@ -423,8 +471,8 @@ typedef struct {
     /* GPK_GN_SEMILINEAR: the coefficients (a1, a2, b, c1, c3) of N(u, grad u); five consecutive doubles.
      * GPK_GN_SEMILINEAR3D: a1, a2, b1 (in gq_b), c1, c3 -- with a3 = p0, b2 = p1, b3 = pen_lambda the eight coefficients of its N */
     double gq_a1, gq_a2, gq_b, gq_c1, gq_c3;
-    /* reaction term of ELLIPTIC(_RELAXED): GPK_NL_* with the parameters p0, p1 above and p2 (CUBIC only); 0 = alpha u^m.  Any other
-     * system takes 0 only (-9001 otherwise) */
+    /* reaction term of ELLIPTIC(_RELAXED): GPK_NL_* with the parameters p0, p1 above and p2 (CUBIC only); 0 = alpha u^m.
+     * QUASILINEAR: the equation kind GPK_QL_* with the parameters p0, p1, p2.  Any other system takes 0 only (-9001 otherwise) */
     int nonlin; double p2;
 } gpk_gn_problem;
 

@@ -387,3 +387,79 @@ __host__ __device__ __forceinline__ void sl3_dN(const double* c, double u, doubl
     *N2 = c[1] * u + 2.0 * c[4] * g2;
     *N3 = c[2] * u + 2.0 * c[5] * g3;
 }
+
+// Quasilinear equations of GPK_GN_QUASILINEAR (gpk.h, GPK_QL_*; DESIGN.md section K, "Quasilinear equations: the 2-jet layout"), solved for
+// the Laplacian: Laplace(u) = G(f; v0, p, q, D, M) with v0 = u, (p, q) = grad u, D = u_11 - u_22, M = 2 u_12.  g2 = p p + q q, W2 = 1 + g2,
+// Q = D (p p - q q) + 2 p q M (= 2 (p p u_11 + 2 p q u_12 + q q u_22) - g2 Laplace(u)), prm = (p0, p1, p2) of gpk_gn_problem:
+//   GPK_QL_MEAN_CURVATURE  (kappa = prm[0])            G = (2 W^3 (f + kappa v0) + Q) / (1 + W2)
+//   GPK_QL_P_LAPLACE       (m = prm[0], delta = prm[1]) G = (2 f s^((4 - m) / 2) - (m - 2) Q) / (2 delta^2 + m g2),  s = delta^2 + g2
+//   GPK_QL_GAUSS_CURVATURE (e = prm[0])                G = sqrt(D D + M M + 4 f W2^e)         (a negative radicand gives NaN)
+// ql_dG: dG[0..4] = the partial derivatives by v0, p, q, D, M.  ql_residual: the equation in its divergence / determinant form from
+// (u, u_1, u_2, u_11, u_12, u_22).  The one place that knows the three forms: gn_build_kernel, the trial build of the line search and
+// pde_residual_ql_kernel call it.  ONE order of operations, left to right as spelled, and no contraction.
+__host__ __device__ __forceinline__ double ql_G(int kind, const double* prm, double f, double v0, double p, double q, double D, double M) {
+#pragma clang fp contract(off)
+    const double pp = p * p, qq = q * q, g2 = pp + qq;
+    if (kind == GPK_QL_GAUSS_CURVATURE) return sqrt((D * D + M * M) + 4.0 * f * pow(1.0 + g2, prm[0]));
+    const double Q = D * (pp - qq) + 2.0 * (p * q) * M;
+    if (kind == GPK_QL_P_LAPLACE) {
+        const double m = prm[0], dd = prm[1] * prm[1], s = dd + g2;
+        return (2.0 * f * pow(s, 0.5 * (4.0 - m)) - (m - 2.0) * Q) / (2.0 * dd + m * g2);
+    }
+    const double W2 = 1.0 + g2, W = sqrt(W2);
+    return (2.0 * (W2 * W) * (f + prm[0] * v0) + Q) / (1.0 + W2);
+}
+__host__ __device__ __forceinline__ void ql_dG(int kind, const double* prm, double f, double v0, double p, double q, double D, double M,
+                                               double* dG) {
+#pragma clang fp contract(off)
+    const double pp = p * p, qq = q * q, g2 = pp + qq;
+    if (kind == GPK_QL_GAUSS_CURVATURE) {
+        const double e = prm[0], W2 = 1.0 + g2;
+        const double G = sqrt((D * D + M * M) + 4.0 * f * pow(W2, e));
+        const double c = 4.0 * f * e * pow(W2, e - 1.0);
+        dG[0] = 0.0; dG[1] = c * p / G; dG[2] = c * q / G; dG[3] = D / G; dG[4] = M / G;
+        return;
+    }
+    const double Q = D * (pp - qq) + 2.0 * (p * q) * M;
+    const double Qp = 2.0 * (p * D + q * M), Qq = 2.0 * (p * M - q * D);
+    if (kind == GPK_QL_P_LAPLACE) {
+        const double m = prm[0], dd = prm[1] * prm[1], s = dd + g2, a = 0.5 * (4.0 - m), c = m - 2.0;
+        const double E = 2.0 * dd + m * g2;
+        const double G = (2.0 * f * pow(s, a) - c * Q) / E;
+        const double k = 4.0 * f * a * pow(s, a - 1.0);
+        dG[0] = 0.0;
+        dG[1] = ((k * p - c * Qp) - 2.0 * m * p * G) / E;
+        dG[2] = ((k * q - c * Qq) - 2.0 * m * q * G) / E;
+        dG[3] = -c * (pp - qq) / E;
+        dG[4] = -c * (2.0 * (p * q)) / E;
+        return;
+    }
+    const double W2 = 1.0 + g2, W = sqrt(W2), r = f + prm[0] * v0, E = 1.0 + W2;
+    const double G = (2.0 * (W2 * W) * r + Q) / E;
+    dG[0] = 2.0 * (W2 * W) * prm[0] / E;
+    dG[1] = ((6.0 * W * p * r + Qp) - 2.0 * p * G) / E;
+    dG[2] = ((6.0 * W * q * r + Qq) - 2.0 * q * G) / E;
+    dG[3] = (pp - qq) / E;
+    dG[4] = 2.0 * (p * q) / E;
+}
+__host__ __device__ __forceinline__ double ql_residual(int kind, const double* prm, double f, double u, double u1, double u2, double u11,
+                                                       double u12, double u22) {
+#pragma clang fp contract(off)
+    const double g2 = u1 * u1 + u2 * u2;
+    if (kind == GPK_QL_GAUSS_CURVATURE) return (u11 * u22 - u12 * u12) - f * pow(1.0 + g2, prm[0]);
+    const double T = (u1 * u1) * u11 + 2.0 * (u1 * u2) * u12 + (u2 * u2) * u22, lap = u11 + u22;
+    if (kind == GPK_QL_P_LAPLACE) {
+        const double m = prm[0], s = prm[1] * prm[1] + g2;
+        return pow(s, 0.5 * (m - 4.0)) * (s * lap + (m - 2.0) * T) - f;
+    }
+    const double W2 = 1.0 + g2;
+    return (W2 * lap - T) / (W2 * sqrt(W2)) - (f + prm[0] * u);
+}
+// why (kind, p0, p1, p2) is not an equation of the family, or nullptr
+static inline const char* gpk_ql_invalid(int kind, double p0, double p1, double p2) {
+    if (kind < GPK_QL_MEAN_CURVATURE || kind > GPK_QL_GAUSS_CURVATURE)
+        return "GPK_GN_QUASILINEAR: nonlin is not one of GPK_QL_MEAN_CURVATURE .. GPK_QL_GAUSS_CURVATURE";
+    if (!(std::isfinite(p0) && std::isfinite(p1) && std::isfinite(p2))) return "GPK_GN_QUASILINEAR: a parameter (p0, p1, p2) is not finite";
+    if (kind == GPK_QL_P_LAPLACE && !(p0 > 0.0 && p1 > 0.0)) return "GPK_GN_QUASILINEAR: GPK_QL_P_LAPLACE needs m (p0) > 0 and delta (p1) > 0";
+    return nullptr;
+}

@@ -25,11 +25,12 @@ struct GnTraits {
     int unknowns;       // unknown groups per collocation point: n_z = unknowns * N_d (0: not a system id)
     int rows;           // rows per domain point of the group factored with L: it has rows * N_d + N_b rows.  Darcy (a second factored group,
                         // data rows) and the relaxed system (penalty rows) add their further groups by hand in gn_dims
-    int grad_k;         // the gradient-unknown form with k = 2 or 3 (0: another form): unknowns [v_0 | v_1 | .. | v_k], rows [v_1; ..; v_k; PDE row;
+    int grad_k;         // the gradient-unknown form with k = 2, 3 or 4 (0: another form): unknowns [v_0 | v_1 | .. | v_k], rows [v_1; ..; v_k; PDE row;
                         // v_0; g] with unit entries everywhere but in the PDE row -- written by ONE frame, gn_build_gradient_rows
     int lz_layout;      // the column layout (BuildArgs::rev) gpk_gn_step runs the system in when the leading-zero schedule is on
                         // (tune.eikonal_lz; the elliptic systems' layout 1 does not ask): 1 elliptic, 2 the gradient-unknown form with k = 2,
-                        // 3 Burgers, 4 Darcy (on the GEMM-only solve path only, see step_layout), 5 the gradient-unknown form with k = 3
+                        // 3 Burgers, 4 Darcy (on the GEMM-only solve path only, see step_layout), 5 the gradient-unknown form with k = 3,
+                        // 6 the gradient-unknown form with k = 4
     bool v0_free_pde_row;   // v_0 does not enter the PDE row, so that the v_0 columns start N_d rows LATER, in the value row: Eikonal's exact
                         // two-segment profile (eikonal_profile) holds.  The Monge-Ampere system has exactly Eikonal's pattern and takes it.
                         // The semilinear system shares Eikonal's layout 2 but must NEVER take that profile: its v_0 columns carry N_u / eps in
@@ -37,13 +38,16 @@ struct GnTraits {
                         // with no other symptom.  Its exact profile is the closed form (column c < N_d holds v0_t, t = N_d - 1 - c, first row
                         // 2 N_d + t = n_z - 1 - c).  The semilinear system in three dimensions (layout 5, order v1, v2, v3, v0): the column at
                         // position pos holds its first non-zero in row pos -- the 1 of the rows d_k u for the gradient unknowns, N_u in the PDE
-                        // row 3 N_d + t for v0_t -- so the closed form with lead = n_z is exact, as for the elliptic system.
+                        // row 3 N_d + t for v0_t -- so the closed form with lead = n_z is exact, as for the elliptic system.  The quasilinear
+                        // system (layout 6, order v1, v2, v3, v4, v0) likewise: dG/dv0 is written in the PDE row 4 N_d + t = pos for EVERY
+                        // equation kind, also where it is 0, so that its profile is the closed form and never Eikonal's two-segment one.
     bool sharded;       // gpk_mg_gn_step admits it (in its leading-zero layout)
     bool p2_reserved;   // p2 must be 0 as well where nonlin must be GPK_NL_POWER
     const char* no_reaction;    // the system has no reaction term of the GPK_NL_* family: the refusal of nonlin != GPK_NL_POWER (nullptr: it has one)
     const char* bad_eps;        // its PDE row is divided by eps = p0, checked to be finite and not 0: the refusal (nullptr: not checked)
     const char* no_structured;  // why gpk_gn_structured_prepare does not serve it (nullptr: served; gpk_gn_step then looks for the prepared forms)
     const char* no_gram;        // why gpk_gn_gram_prepare does not
+    bool ql_kind = false;       // nonlin is a GPK_QL_* equation kind with the parameters p0, p1, p2 (gpk_ql_invalid), not a reaction term
 };
 
 __host__ __device__ constexpr GnTraits gn_traits(int system) {
@@ -70,6 +74,10 @@ __host__ __device__ constexpr GnTraits gn_traits(int system) {
                     "gn: GPK_GN_SEMILINEAR3D takes nonlin = 0 and p2 = 0 only (its nonlinearity is gq_a1 .. gq_c3, p0, p1, pen_lambda)", nullptr,
                     "structured solve: GPK_GN_SEMILINEAR3D is not served (its PDE row has four z-dependent entries per point)",
                     "gram_prepare: GPK_GN_SEMILINEAR3D is not served (it has no structured form)"};
+        case GPK_GN_QUASILINEAR:
+            return {5, 6, 4, 6, false, false, false, nullptr, nullptr,
+                    "structured solve: GPK_GN_QUASILINEAR is not served (its PDE row has five z-dependent entries per point)",
+                    "gram_prepare: GPK_GN_QUASILINEAR is not served (it has no structured form)", true};
         default: return {0, 0, 0, 0, false, false, false, nullptr, nullptr, nullptr, nullptr};
     }
 }
@@ -104,7 +112,8 @@ bool every_factor_has_dinv(const Dims& d) {
 struct BuildArgs {
     int system, Nd, Nb, Ndata;
     double p0, p1, lam;
-    int nonlin; double p2;   // reaction term of the elliptic systems (GPK_NL_*; nl_tau / nl_dtau of gpk_common.h)
+    int nonlin; double p2;   // reaction term of the elliptic systems (GPK_NL_*; nl_tau / nl_dtau of gpk_common.h); GPK_GN_QUASILINEAR: its
+                             // equation kind GPK_QL_* with the parameters (p0, p1, p2) (ql_G / ql_dG)
     double gq[8];            // GPK_GN_SEMILINEAR: (a1, a2, b, c1, c3) of N(u, grad u) (sl_N / sl_dN of gpk_common.h); GPK_GN_SEMILINEAR3D: (a1, a2,
                              // a3, b1, b2, b3, c1, c3) (sl3_N / sl3_dN), gathered from the doubles of gpk_gn_problem by build_args
     const double* f; const double* gb; const double* data; const double* z;
@@ -117,13 +126,15 @@ struct BuildArgs {
                        // a staircase of slope 1/3 (column zero above row pos/3; GpkLz::div = 3).  4: Darcy (round 4), unknown groups
                        // [w0 | w1 | w2 | v0 | v1 | v2] taken in the order v1, v2, w1, w2, w0, v0 -- see darcy_profiles below.  5: the semilinear
                        // system in three dimensions, unknown groups [v0 | v1 | v2 | v3] taken in the order v1, v2, v3, v0: their first
-                       // non-zeros sit in rows t, N_d + t, 2 N_d + t and 3 N_d + t (N_u in the PDE row) = pos exactly
+                       // non-zeros sit in rows t, N_d + t, 2 N_d + t and 3 N_d + t (N_u in the PDE row) = pos exactly.  6: the quasilinear
+                       // system, unknown groups [v0 | v1 | .. | v4] taken in the order v1, .., v4, v0: first non-zeros in rows t, .., 3 N_d + t
+                       // and 4 N_d + t (dG/dv0 in the PDE row) = pos exactly
     int nz;
     int family;        // elliptic system, gpk_gn_structured_prepare: 1 = only the unit entries of the first row group ([I; 0; 0], no F),
                        // 2 = only those of the second ([0; I; 0]) together with F(z); 0 = the normal [A(z) | F(z)]
 };
 
-// the layouts 2 (k = 2) and 5 (k = 3) of the gradient-unknown form: the groups [v0 | v1 | .. | vk] taken in the order v1, .., vk, v0
+// the layouts 2 (k = 2), 5 (k = 3) and 6 (k = 4) of the gradient-unknown form: the groups [v0 | v1 | .. | vk] taken in the order v1, .., vk, v0
 // (k a compile-time constant: the remainder is then no division)
 template <int k>
 __host__ __device__ __forceinline__ int stair_pos_gradient(int Nd, int j) { return ((j / Nd + k) % (k + 1)) * Nd + j % Nd; }
@@ -137,6 +148,7 @@ __host__ __device__ __forceinline__ int stair_pos(int rev, int Nd, int j) {
     }
     if (rev == 2) return stair_pos_gradient<2>(Nd, j);
     if (rev == 5) return stair_pos_gradient<3>(Nd, j);
+    if (rev == 6) return stair_pos_gradient<4>(Nd, j);
     return rev == 3 ? 3 * (j % Nd) + j / Nd : j;
 }
 
@@ -240,6 +252,18 @@ struct RowSemilinear3d {                                    // gpk.h, GPK_GN_SEM
     }
 };
 
+struct RowQuasilinear {                                     // gpk.h, GPK_GN_QUASILINEAR: rows [d_1 u; d_2 u; D u; M u; Delta u; u], PDE row G(x; v) of the kind a.nonlin
+    static constexpr int system = GPK_GN_QUASILINEAR, k = 4; static constexpr bool has_v0 = true;
+    static __device__ __forceinline__ void partials(const BuildArgs& a, int t, const double* v, double* dR) {
+        const double prm[3] = {a.p0, a.p1, a.p2};
+        ql_dG(a.nonlin, prm, a.f[t], v[0], v[1], v[2], v[3], v[4], dR);
+    }
+    static __device__ __forceinline__ double value(const BuildArgs& a, int t, const double* v) {
+        const double prm[3] = {a.p0, a.p1, a.p2};
+        return ql_G(a.nonlin, prm, a.f[t], v[0], v[1], v[2], v[3], v[4]);
+    }
+};
+
 // The ONE frame of the gradient-unknown systems (GnTraits::grad_k = Row::k), collocation index t: unit entries and F = v_j in the rows of
 // v_j, the PDE row, the unit entry and v_0 in the value row; g on the boundary.  v[] and dR[] are indexed by unrolled constants only: registers.
 template <class Row, class Z>
@@ -322,6 +346,7 @@ __device__ __forceinline__ void gn_build_rows(const BuildArgs& a, const int t, c
         else if (a.system == GPK_GN_SEMILINEAR) gn_build_gradient_rows<RowSemilinear>(a, t, z);
         else if (a.system == GPK_GN_MONGE_AMPERE) gn_build_gradient_rows<RowMongeAmpere>(a, t, z);
         else if (a.system == GPK_GN_SEMILINEAR3D) gn_build_gradient_rows<RowSemilinear3d>(a, t, z);
+        else if (a.system == GPK_GN_QUASILINEAR) gn_build_gradient_rows<RowQuasilinear>(a, t, z);
     } else if (a.system == GPK_GN_DARCY) {                  // src/InverseProblems.py:106-117 (F), :127-143 (A)
         const double gam = a.p0;                            // noise_level
         const int U = 3 * Nd, D = 7 * Nd + Nb;
@@ -466,6 +491,10 @@ int build(gpk_handle h, const gpk_gn_problem* p, const double* z, double* S, lon
 
 // the reaction term is one of the family, and only the systems whose record says so have one; a PDE row divided by eps needs a usable eps
 int check_nonlin(gpk_handle h, const gpk_gn_problem* p) {
+    if (gn_traits(p->system).ql_kind) {                              // nonlin is the equation kind, read as such for this system only
+        const char* bad = gpk_ql_invalid(p->nonlin, p->p0, p->p1, p->p2);
+        return bad ? gpk_bad_arg(h, bad) : 0;
+    }
     if (!gpk_nl_valid(p->nonlin)) return gpk_bad_arg(h, "gn: nonlin is not one of GPK_NL_POWER .. GPK_NL_CUBIC");
     const GnTraits t = gn_traits(p->system);
     if (t.no_reaction && (p->nonlin != GPK_NL_POWER || (t.p2_reserved && p->p2 != 0.0))) return gpk_bad_arg(h, t.no_reaction);
@@ -571,7 +600,7 @@ int step_layout(gpk_handle h, const gpk_gn_problem* p) {
 // Which systems of layout 2 may take the two-segment profile, and why the others must not: GnTraits::v0_free_pde_row.
 GpkLz step_profile(gpk_handle h, const gpk_gn_problem* p, int nz, int rev) {
     if (rev == 2 && gn_traits(p->system).v0_free_pde_row && h->tune.use_dinv && p->Dinv && p->dinv_block > 0 && h->tune.eikonal_lz != 2) return GpkLz::piecewise(eikonal_profile(p->Nd));
-    return ((rev >= 1 && rev <= 3) || rev == 5) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
+    return ((rev >= 1 && rev <= 3) || rev == 5 || rev == 6) ? GpkLz::closed(nz, rev == 3 ? 3 : 1) : GpkLz();
 }
 
 // the GEMM-only solve path is available and switched on, with the block size given (the structured modes of the other systems need it)
@@ -1424,7 +1453,7 @@ extern "C" int gpk_gn_build_rev(gpk_handle h, const gpk_gn_problem* p, const dou
     if (!h || !z || !S || !p) return GPK_ERR_ARG;
     // (round 6: also the Eikonal and Burgers systems in the staircase orders of their gpk_gn_step -- the sharded step uses them)
     const int rev = step_layout(h, p);
-    if (rev < 1 || rev > 5 || p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "gn_build_rev: not for the relaxed system / needs the leading-zero layout");
+    if (rev < 1 || rev > 6 || p->system == GPK_GN_ELLIPTIC_RELAXED) return gpk_bad_arg(h, "gn_build_rev: not for the relaxed system / needs the leading-zero layout");
     Dims d;
     gpk_gn_problem q = *p;
     if (gn_dims(&q, d) != 0) return gpk_bad_arg(h, "gn: system id / sizes");

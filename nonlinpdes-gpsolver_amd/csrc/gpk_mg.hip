@@ -663,6 +663,7 @@ extern "C" int gpk_mg_gn_step(gpk_mg_handle mg, const gpk_gn_problem* p, double*
     // profile; the a-part contributes the constant H_a and one replicated F column).  The relaxed system is one-GPU only.
     const int rev = gpk_i_gn_layout(h, p);
     const bool darcy = p->system == GPK_GN_DARCY;
+    if (p->system == GPK_GN_QUASILINEAR) return gpk_bad_arg(h, "gpk_mg_gn_step: GPK_GN_QUASILINEAR is not served on more than one GPU");
     if (!gpk_i_gn_sharded(p) || rev < 1 || rev > 4 || (darcy != (rev == 4)))
         return gpk_bad_arg(h, "gpk_mg_gn_step: elliptic, Eikonal, Burgers and Darcy systems only (leading-zero layout)");
     if (!p->Dinv || !S2) return gpk_bad_arg(h, "gpk_mg_gn_step: needs the inverted diagonal blocks (Dinv) and S2");

@@ -99,6 +99,9 @@ PROTOTYPES = {
     'gpk_assemble_hess': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_hess': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
     'gpk_pde_residual_ma': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    'gpk_assemble_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
+    'gpk_extend_functionals_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_pde_residual_ql': (_i, [_vp, _i, _pd, _i, _vp, _i, _vp, _vp]),
     'gpk_assemble_grad3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _vp, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_grad3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     'gpk_pde_residual_sl3d': (_i, [_vp, _pd, _i, _vp, _i, _vp, _vp, _vp]),

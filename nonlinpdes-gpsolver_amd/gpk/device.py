@@ -36,7 +36,8 @@ def dinv_block_for(n):
         db //= 2
     return db
 SYSTEM = {'Nonlinear_elliptic': 0, 'Burgers': 1, 'Eikonal': 2, 'Darcy_flow2d': 3, 'Nonlinear_elliptic_relaxed': 4, 'Semilinear2d': 5,
-          'MongeAmpere2d': 6, 'Semilinear3d': 7}
+          'MongeAmpere2d': 6, 'Semilinear3d': 7, 'Quasilinear2d': 9}
+QL_KIND = {'mean_curvature': 0, 'p_laplace': 1, 'gauss_curvature': 2}             # GPK_QL_*: equation kind of the system 'Quasilinear2d'
 NONLIN = {'power': 0, 'exp': 1, 'sinh': 2, 'sin': 3, 'cubic': 4}                  # GPK_NL_*: reaction term of the elliptic systems
 EVIDENCE_TERMS = ('log_Z', 'J', 'logdet_theta', 'logdet_H', 'gamma_term', 'two_pi_term')   # host_terms[6] of gpk_log_evidence
 
@@ -148,7 +149,8 @@ class GNProblem:
     def __init__(self, ctx, system, Nd, Nb, rhs_f, bdy_g, L, p0=0.0, p1=0.0, pen_lambda=0.0, data_u=None, L2=None, dinv=True, structured=False,
                  cache_a=None, nonlin=0, p2=0.0, gq=None, gq8=None):
         """nonlin, p2 (elliptic systems only): the reaction term tau(u) -- a GPK_NL_* id or its name in NONLIN -- with the parameters
-        p0, p1, p2; 0 / 'power' is p0 u^p1, the reference's equation.
+        p0, p1, p2; 0 / 'power' is p0 u^p1, the reference's equation.  System 'Quasilinear2d': nonlin is the equation kind -- a GPK_QL_* id
+        or its name in QL_KIND -- with the parameters p0, p1, p2.
         gq ('Semilinear2d' only): the coefficients (a1, a2, b, c1, c3) of N(u, grad u); p0 is eps there.
         gq8 ('Semilinear3d' only): the coefficients (a1, a2, a3, b1, b2, b3, c1, c3) of its N(u, grad u).  The struct has no fields of
         their own for a3, b2, b3: they travel in p0, p1, pen_lambda (include/gpk.h), so those three arguments must be left at 0.
@@ -172,7 +174,8 @@ class GNProblem:
         s.Nd, s.Nb = int(Nd), int(Nb)
         s.Ndata = 0 if data_u is None else int(np.asarray(data_u).size)
         s.p0, s.p1, s.pen_lambda = float(p0), float(p1), float(pen_lambda)
-        s.nonlin, s.p2 = (NONLIN[nonlin] if isinstance(nonlin, str) else int(nonlin)), float(p2)
+        names = QL_KIND if s.system == SYSTEM['Quasilinear2d'] else NONLIN
+        s.nonlin, s.p2 = (names[nonlin] if isinstance(nonlin, str) else int(nonlin)), float(p2)
         if gq is not None:
             gq = [float(v) for v in gq]
             if len(gq) != 5:
@@ -559,6 +562,28 @@ class Context:
         """Pointwise residual d11 d22 - d12^2 - f of the Monge-Ampere equation (gpk_pde_residual_ma), as an (Nt,) DeviceArray.
         fields: (3, Nt) d11, d12, d22 of the extension; rhs as for pde_residual."""
         return self._pde_residual(self.lib.gpk_pde_residual_ma, (), fields, rhs)
+
+    # ---- 2-jet layout: d1, d2, D = d11 - d22, M = 2 d12, Laplacian, delta (gpk_assemble_jet2, gpk_extend_functionals_jet2, gpk_pde_residual_ql) ----
+    def assemble_jet2(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the 2-jet layout (blocks d1, d2, D, M, Laplacian on Xd, delta on [Xd; Xb]): (DeviceArray N x N with
+        N = 6 Nd + Nb, [trace(block k) / trace(block 5) for k = 0..4]).  out: a DeviceArray to write into (any leading dimension >= N)."""
+        return self._assemble_blocks(self.lib.gpk_assemble_jet2, 2, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out,
+                                     rows=6, nratios=5)
+
+    def extend_functionals_jet2(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd11', 'd12', 'd22')):
+        """Value / derivatives up to order two of the extension on the 2-jet layout at Xt (gpk_extend_functionals_jet2): a
+        (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP).  coeff = Theta^{-1} sol_vec (6 Nd + Nb values)
+        with the Theta of assemble_jet2."""
+        return self._extend_functionals('extend_functionals_jet2', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_jet2, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
+
+    def pde_residual_ql(self, kind, params, fields, rhs):
+        """Pointwise residual of a quasilinear equation in its divergence / determinant form (gpk_pde_residual_ql), as an (Nt,)
+        DeviceArray.  kind: a GPK_QL_* id or its name in QL_KIND; params = (p0, p1, p2); fields: (6, Nt) value, d1, d2, d11, d12, d22 of
+        the extension; rhs as for pde_residual."""
+        p = (C.c_double * 3)(*[float(v) for v in (list(params) + [0.0, 0.0, 0.0])[:3]])
+        k = QL_KIND[kind] if isinstance(kind, str) else int(kind)
+        return self._pde_residual(self.lib.gpk_pde_residual_ql, (k, p), fields, rhs)
 
     # ---- operator and boundary functionals in three dimensions (gpk_assemble_op3d, gpk_extend_functionals_op3d) ----
     def _coeff_rows(self, c, n, width, what, per_point=''):

@@ -1,7 +1,7 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
 same elliptic equation on a box in three space dimensions, and Semilinear2d, the semilinear equation with a gradient-dependent
-nonlinearity on the Eikonal layout, and Semilinear3d, its counterpart in three dimensions and in time on the gradient layout (none has a
-counterpart in the reference).  The classes stand on _GPEquation; the two
+nonlinearity on the Eikonal layout, and Semilinear3d, its counterpart in three dimensions and in time on the gradient layout, and
+MongeAmpere2d and Quasilinear2d on the Hessian and the 2-jet layout (none has a counterpart in the reference).  The classes stand on _GPEquation; the two
 elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
 _family() what sets it apart.
 
@@ -20,6 +20,7 @@ import gpk
 from gpk.device import require_gaussian_family
 from ._runtime import eval_callback, get_context
 from .nonlinearity import GradientNonlinearity, GradientNonlinearity3d, Nonlinearity
+from .quasilinear import QuasilinearEquation
 from .sample_points import boundary_normals, boundary_normals3d, sampled_pts_grid, sampled_pts_grid3d, sampled_pts_rdm, sampled_pts_rdm3d
 
 _NAN_MSG = '[Error] Loss is nan: maybe nugget is too small!'
@@ -975,7 +976,7 @@ class Burgers(_GPEquation):
 class _GradientUnknowns(object):
     """Mixin of the equations whose unknowns per domain point are the value v_0 and k further fields v_1 .. v_k (derivatives of u) that
     have Gram rows of their own: _blocks_per_point = k + 1, unknowns [v_0 | v_1 | .. | v_k], rows [v_1; ..; v_k; PDE row; v_0; g] --
-    Eikonal, Semilinear2d, MongeAmpere2d (k = 2) and Semilinear3d (k = 3).  A class says what its PDE row is, in two hooks:
+    Eikonal, Semilinear2d, MongeAmpere2d (k = 2), Semilinear3d (k = 3) and Quasilinear2d (k = 4).  A class says what its PDE row is, in two hooks:
     _pde_row(v) at an iterate and _pde_row_linearised(v, o), the row linearised at the iterate o and evaluated at v (v, o: tuples
     (v_0, .., v_k)).  Everything else about its Gauss-Newton iteration is written here, once."""
     _zero_start = True
@@ -1161,6 +1162,83 @@ class MongeAmpere2d(_GradientUnknowns, _GPEquation):
 
     def _posterior_unserved(self):
         return 'MongeAmpere2d: gpk_assemble_cross has no rectangular evaluator for the Hessian layout yet'
+
+
+class Quasilinear2d(_GradientUnknowns, _GPEquation):
+    """A quasilinear equation on a rectangle, u = g on its boundary: its second-order coefficients depend on grad u.  No counterpart in
+    the reference.  equation (src/quasilinear.py):
+        ('mean_curvature', kappa)   div(grad u / sqrt(1 + |grad u|^2)) = f + kappa u     (minimal surface, prescribed mean curvature, capillarity)
+        ('p_laplace', m, delta)     div((delta^2 + |grad u|^2)^((m-2)/2) grad u) = f     (m > 0, delta > 0; m = 2: Poisson's equation)
+        ('gauss_curvature', e)      det D^2 u = f (1 + |grad u|^2)^e, f > 0, convex      (e = 2: prescribed Gauss curvature; e = 0: Monge-Ampere)
+    Each is solved for the Laplacian, Laplace(u) = G(x; u, grad u, D u, M u) with D = d_11 - d_22, M = 2 d_12, so the zero start is
+    admissible.  The Gram matrix is the 2-jet layout's (rows d_1 u, d_2 u, D u, M u, Laplace(u), u per domain point, then u on the
+    boundary: gpk_assemble_jet2, Gaussian kernels only), the Gauss-Newton system is GPK_GN_QUASILINEAR with unknowns
+    [u | d_1 u | d_2 u | D u | M u].  Dirichlet data only.  log_evidence and eq.line_search (src/linesearch.py) are the base class's;
+    posterior_variance / posterior_covariance / posterior_sample raise NotImplementedError (no rectangular cross evaluator for the
+    2-jet layout).  GPK_STRUCTURED is ignored: the system has no structured form."""
+    _layout = 'Jet2'
+    _system = 'Quasilinear2d'
+    _blocks_per_point = 5
+    _structured_optin = False
+    _deriv_names = ('value', 'd1', 'd2', 'd11', 'd12', 'd22')
+
+    def __init__(self, equation=('mean_curvature', 0.0), bdy=None, rhs=None, domain=onp.array([[0, 1], [0, 1]])):
+        self.equation = QuasilinearEquation.make(equation)
+        self.bdy = bdy
+        self.rhs = rhs
+        self.domain = domain
+
+    def _gn_params(self):
+        return self.equation.params[0], self.equation.params[1], 0.0
+
+    def _nl_args(self):
+        return dict(nonlin=self.equation.id, p2=self.equation.params[2])
+
+    def Gram_matrix(self, kernel='Gaussian', kernel_parameter=0.3, nugget=1e-8, nugget_type='adaptive'):
+        """kernel: Gaussian or anisotropic_Gaussian (the Matern family and the periodic kernel are refused: the 2-jet layout has no
+        evaluator for them)"""
+        require_gaussian_family(kernel, 'Quasilinear2d.Gram_matrix')
+        ratios = self._assemble(kernel, kernel_parameter, nugget, nugget_type)
+        if nugget_type == 'adaptive':
+            self.ratio = list(ratios[:5])
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        return ctx.assemble_jet2(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+
+    def _pde_row(self, v):
+        return self.equation.G(self.rhs_f, *v)
+
+    def _pde_row_linearised(self, v, o):
+        return self.equation.G(self.rhs_f, *o) + sum(d * (a - b) for d, a, b in zip(self.equation.dG(self.rhs_f, *o), v, o))
+
+    def GN_method(self, max_iter=8, step_size=1, initial_sol='zero', print_hist=True):
+        """initial_sol: 'zero', 'rdm' (standard normal draw), or an ndarray with one value per unknown: the iterate to start from."""
+        self._gn_solve(self._n_unknowns(), max_iter, step_size, initial_sol, print_hist)
+
+    def extend_sol(self, X_test):
+        ctx = get_context()
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        coeff = self._coeff(self._dL, self.sol_vec)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = ctx.extend_functionals_jet2(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                        coeff, which=('value',)).download().reshape(-1)
+
+    def _derivative_fields(self, X_test):
+        coeff = self._coeff(self._dL, self.sol_vec)
+        return {'u': get_context().extend_functionals_jet2(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                           coeff, which=self._deriv_names)}
+
+    def extend_derivatives(self, X_test):
+        """value, d1, d2, d11, d12 and d22 of the GP solution at X_test (numpy arrays)"""
+        return super().extend_derivatives(X_test)
+
+    def _residual(self, fields_u, fields_a, rhs):
+        """the equation in its divergence / determinant form on the six rows of the extension (gpk_pde_residual_ql)"""
+        return get_context().pde_residual_ql(self.equation.id, self.equation.params, fields_u, rhs).download().reshape(-1)
+
+    def _posterior_unserved(self):
+        return 'Quasilinear2d: no rectangular cross evaluator for the 2-jet layout'
 
 
 class Semilinear3d(_GradientUnknowns, Nonlinear_elliptic3d):

@@ -4,7 +4,8 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Semilinear2d, Semilinear3d
+from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Quasilinear2d, Semilinear2d, Semilinear3d
+from .quasilinear import QuasilinearEquation
 from .nonlinearity import GradientNonlinearity, Nonlinearity
 
 
@@ -36,6 +37,16 @@ def _tau_of(c):
     if spec is None or (isinstance(spec, str) and spec == 'power'):
         return None
     return Nonlinearity.make(spec)
+
+
+_QL_FORMS = {'mean_curvature': 'div(grad u / sqrt(1 + |grad u|^2)) = f + kappa*u',
+             'p_laplace': 'div((delta^2 + |grad u|^2)^((m-2)/2) grad u) = f',
+             'gauss_curvature': 'det D^2 u = f*(1 + |grad u|^2)^e, convex solution'}
+
+
+def _quasilinear_of(c):
+    """the QuasilinearEquation of a Quasilinear2d configuration: cfg.equation, else the class's default ('mean_curvature', 0)"""
+    return QuasilinearEquation.make(getattr(c, 'equation', None) or ('mean_curvature', 0.0))
 
 
 def _gradient_nl_of(c):
@@ -146,6 +157,12 @@ _EQUATIONS = {
         lambda c: ['[Equation type] Monge-Ampere equation (fully nonlinear)',
                    '[Equation form] det D^2 u = f, convex solution: Delta u = sqrt((u_11 - u_22)^2 + (2 u_12)^2 + 4 f)'],
         None),
+    'Quasilinear2d': (
+        # (cfg.equation: ('mean_curvature', kappa) | ('p_laplace', m, delta) | ('gauss_curvature', e), or a QuasilinearEquation)
+        lambda c, **k: Quasilinear2d(equation=_quasilinear_of(c), **k),
+        lambda c: ['[Equation type] Quasilinear equation (second-order coefficients depend on grad u)',
+                   '[Equation form] ' + _QL_FORMS[_quasilinear_of(c).kind]],
+        lambda c: f'[Equation parameter] {_quasilinear_of(c).kind}: (p0, p1, p2) = {_quasilinear_of(c).params}'),
     'Darcy_flow2d': (
         lambda c, **k: Darcy_flow2d(**k),
         lambda c: ['[Inverse problem type] Darcy flow 2d', '[Inverse problem form] -div(a grad u) = f, infer a from f and some observed u'],
