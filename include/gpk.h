@@ -143,7 +143,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_jet2 / gpk_assemble_grad3d call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_jet2 / gpk_assemble_grad3d / gpk_assemble_disp call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -326,6 +326,30 @@ int gpk_assemble_jet2(gpk_handle h, int kernel, const double* host_kparams, cons
  * Theta^{-1} sol_vec with the Theta of gpk_assemble_jet2.  fmask, out, ldo and the contract (fixed reduction order, a row's bits do not
  * depend on the other rows requested) as gpk_extend_functionals_hess. */
 int gpk_extend_functionals_jet2(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
+                                const double* Xd, int Nd, const double* Xb, int Nb,
+                                const double* coeff, int fmask, double* out, int ldo);
+/* ---- Dispersive layout: the Burgers layout with the third space derivative in place of the second ("Dispersive
+ *      equations: the third-order layout"), for u_t + alpha u u_x + delta u_xxx = f.  No reference call site.  Points are (t, x) rows: axis 1
+ *      is time, axis 2 is space, as for GPK_LAYOUT_BURGERS.  Block 0 = d_t, block 1 = d_x, block 2 = d_x^3, each on the Nd domain points;
+ *      block 3 = delta on the Nd+Nb domain and boundary points.  N = 4Nd+Nb, Theta N x N, ld >= N: gpk_potrf, gpk_potrs, the
+ *      GPK_GN_BURGERS system with p1 = -delta, gpk_log_evidence and gpk_pde_residual(GPK_GN_BURGERS) with u_xxx in the fourth row apply
+ *      to it.  Theta is symmetric to the bit.  Kernels: Gaussian and anisotropic Gaussian (any other id: -9001).  host_kparams, Xd, Xb as
+ *      gpk_assemble.  Nugget as gpk_assemble_hess: adaptive = nugget * trace(block k) / trace(block 3) on the blocks 0..2, nugget on
+ *      block 3.  host_ratios3 (three doubles, may be NULL) = those ratios, with the values at d = 0
+ *        <d_t,d_t> = p1,   <d_x,d_x> = p2,   <d_x^3,d_x^3> = 15 p2^3,   <delta,delta> = 1,
+ *      written for every nugget type.  Any alignment of Theta / ld is accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte
+ *      stores otherwise, with the same values; nothing outside the N x N view is written); the launch is timed like gpk_assemble's
+ *      when the per-phase timing is on (gpk_prof_read_assembly).  Bad arguments: -9001, named in gpk_last_error. */
+int gpk_assemble_disp(gpk_handle h, int kernel, const double* host_kparams, const double* Xd, int Nd, const double* Xb, int Nb,
+                      double nugget, int nugget_type, double* Theta, int ld, double* host_ratios3);
+/* Value and derivatives of the extension on the dispersive layout at test points Xt (Nt,2), matrix-free: coeff (4Nd+Nb) =
+ * Theta^{-1} sol_vec with the Theta of gpk_assemble_disp.  fmask: a non-empty subset of GPK_FN_VALUE, GPK_FN_D1 (u_t), GPK_FN_D2 (u_x),
+ * GPK_FN_D2D2 (u_xx) and GPK_FN_D2D2D2 (u_xxx) (anything else, GPK_FN_LAPLACIAN and GPK_FN_D3 included: -9001); out is functional-major,
+ * row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.  Fixed reduction order (wave
+ * shuffles, then LDS, no atomics): a repeated call gives bit-identical output, and a row has the same bits whichever other rows are
+ * requested. */
+#define GPK_FN_D2D2D2 64      /* d^3/dx2^3: gpk_extend_functionals_disp only (bit 6, after GPK_FN_LAPLACIAN and GPK_FN_D3) */
+int gpk_extend_functionals_disp(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                                 const double* Xd, int Nd, const double* Xb, int Nb,
                                 const double* coeff, int fmask, double* out, int ldo);
 /* ---- Operator and boundary functionals in three dimensions ("Operator and boundary functionals in three dimensions"):

@@ -1,7 +1,7 @@
-// gpk_assemble_common.h -- what the ten Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts and their
+// gpk_assemble_common.h -- what the eleven Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts and their
 // Gaussian family, gpk_assemble_matern.hip: their Matern family, gpk_assemble_periodic.hip: their periodic kernel, gpk_assemble3d.hip,
 // gpk_assemble_bc.hip: Neumann / Robin, gpk_assemble_op.hip: variable-coefficient operator, gpk_assemble_op3d.hip: the operator and the
-// boundary functionals in three dimensions, gpk_assemble_hess.hip: the Hessian layout, gpk_assemble_jet2.hip: the 2-jet layout,
+// boundary functionals in three dimensions, gpk_assemble_hess.hip: the Hessian layout, gpk_assemble_jet2.hip: the 2-jet layout, gpk_assemble_disp.hip: the dispersive layout,
 // gpk_assemble_grad3d.hip: the gradient layout in three
 // dimensions, which shares gpk_assemble_op3.h with gpk_assemble_op3d.hip).  The kernels and the per-pair arithmetic that
 // differs between them (pair_coeff in its roundings, pair_coeff3, the tables of the operator) stay in those files -- the kernels of the

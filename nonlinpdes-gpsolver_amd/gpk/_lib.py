@@ -98,6 +98,8 @@ PROTOTYPES = {
     'gpk_extend_functionals_op3d': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     'gpk_assemble_hess': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_hess': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_assemble_disp': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
+    'gpk_extend_functionals_disp': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
     'gpk_pde_residual_ma': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     'gpk_assemble_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),

@@ -17,6 +17,7 @@ NUGGET = {'none': 0, 'identity': 1, 'adaptive': 2}
 FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # GPK_FN_* bits of gpk_extend_functionals
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
 FUNCTIONAL_OP = {'value': 1, 'd1': 2, 'd2': 4, 'd11': 8, 'd12': 16, 'd22': 32}   # GPK_OPFN_* bits of gpk_extend_functionals_op
+FUNCTIONAL_DISP = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'd2d2d2': 64}         # bits accepted by gpk_extend_functionals_disp (GPK_FN_D2D2D2 = 64)
 OP3_NAMES = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')   # the monomials of op3, in its order
 FUNCTIONAL_OP3 = {n: 1 << k for k, n in enumerate(OP3_NAMES)}                    # GPK_OP3FN_* bits of gpk_extend_functionals_op3d
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
@@ -539,6 +540,21 @@ class Context:
         (len(which), Nt) DeviceArray, row k = functional which[k] (names: FUNCTIONAL_OP).  coeff = Theta^{-1} sol_vec (4 Nd + Nb values)
         with the Theta of assemble_hess."""
         return self._extend_functionals('extend_functionals_hess', FUNCTIONAL_OP, 2, self.lib.gpk_extend_functionals_hess, (),
+                                        kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
+
+    # ---- dispersive layout: d_t, d_x, d_x^3, delta on (t, x) points (gpk_assemble_disp, gpk_extend_functionals_disp) ----
+    def assemble_disp(self, kernel, kernel_parameter, Xd, Xb, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the dispersive layout (blocks d_t, d_x, d_x^3 on Xd, delta on [Xd; Xb]; points (t, x)): (DeviceArray N x N
+        with N = 4 Nd + Nb, [trace(block k) / trace(block 3) for k = 0, 1, 2]).  out: a DeviceArray to write into (any leading
+        dimension >= N)."""
+        return self._assemble_blocks(self.lib.gpk_assemble_disp, 2, kernel, kernel_parameter, Xd, Xb, None, nugget, nugget_type, out,
+                                     rows=4, nratios=3)
+
+    def extend_functionals_disp(self, kernel, kernel_parameter, Xt, Xd, Xb, coeff, which=('value', 'd1', 'd2', 'd2d2', 'd2d2d2')):
+        """u, u_t, u_x, u_xx, u_xxx of the extension on the dispersive layout at Xt (gpk_extend_functionals_disp): a (len(which), Nt)
+        DeviceArray, row k = functional which[k] (names: FUNCTIONAL_DISP).  coeff = Theta^{-1} sol_vec (4 Nd + Nb values) with the
+        Theta of assemble_disp."""
+        return self._extend_functionals('extend_functionals_disp', FUNCTIONAL_DISP, 2, self.lib.gpk_extend_functionals_disp, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
 
     def _on_device(self, a, fields=False):

@@ -1,7 +1,8 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
 same elliptic equation on a box in three space dimensions, and Semilinear2d, the semilinear equation with a gradient-dependent
 nonlinearity on the Eikonal layout, and Semilinear3d, its counterpart in three dimensions and in time on the gradient layout, and
-MongeAmpere2d and Quasilinear2d on the Hessian and the 2-jet layout (none has a counterpart in the reference).  The classes stand on _GPEquation; the two
+MongeAmpere2d and Quasilinear2d on the Hessian and the 2-jet layout, and KdV, the Burgers system on the dispersive layout (none has a
+counterpart in the reference).  The classes stand on _GPEquation; the two
 elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
 _family() what sets it apart.
 
@@ -971,6 +972,81 @@ class Burgers(_GPEquation):
         Nd = self.N_domain
         v0, v2, v3 = sol[:Nd], sol[Nd:2 * Nd], sol[2 * Nd:]
         return onp.concatenate((self.nu * v3 + self.rhs_f - self.alpha * v0 * v2, v2, v3, v0, self.bdy_g), axis=0), v0
+
+
+class KdV(Burgers):
+    """u_t + alpha u u_x + delta u_xxx = f on (t,x) in a rectangle: equations of Korteweg-de Vries type (solitons, shallow-water and
+    plasma waves).  No counterpart in the reference.  It is the Burgers system with one row functional exchanged: rows
+    [u_t; u_x; u_xxx; u] per domain point, then u on the boundary (the dispersive Gram layout, gpk_assemble_disp, Gaussian kernels only),
+    unknowns [u | u_x | u_xxx], and GPK_GN_BURGERS with nu = -delta is the Gauss-Newton system -- loss, step, line search, the structured
+    modes (GPK_STRUCTURED) and log_evidence are the base class's.  The boundary carries Dirichlet data only: the third boundary condition
+    of the equation is not imposed, the minimum-norm interpolant supplies it.  posterior_variance / posterior_covariance /
+    posterior_sample raise NotImplementedError (the layout has no rectangular cross evaluator yet)."""
+    _layout = 'Dispersive'                                    # (no GPK_LAYOUT_* id: the evaluator is a call of its own)
+    _system = 'Burgers'
+    _deriv_names = ('value', 'd1', 'd2', 'd2d2d2')            # u, u_t, u_x, u_xxx: the rows gpk_pde_residual(GPK_GN_BURGERS) reads
+
+    def __init__(self, alpha=6.0, delta=1.0, bdy=None, rhs=None, domain=onp.array([[0, 1], [-1, 1]])):
+        super().__init__(alpha=alpha, nu=-delta, bdy=bdy, rhs=rhs, domain=domain)
+        self.delta = delta
+
+    def _gn_params(self):
+        return float(self.alpha), -float(self.delta), 0.0
+
+    def Gram_matrix(self, kernel='anisotropic_Gaussian', kernel_parameter=[1 / 3, 1 / 5], nugget=1e-8, nugget_type='adaptive'):
+        """kernel: Gaussian or anisotropic_Gaussian (the Matern family and the periodic kernel are refused: the dispersive layout has no
+        evaluator for them)"""
+        require_gaussian_family(kernel, 'KdV.Gram_matrix')
+        super().Gram_matrix(kernel, kernel_parameter, nugget, nugget_type)
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        return ctx.assemble_disp(kernel, kernel_parameter, self.X_domain, self.X_boundary, nugget, nugget_type)
+
+    def _initial(self, initial_sol, n):
+        """'profile': the data at the first time of the domain held constant in time -- u = u_0(x) at every domain point, with u_x and
+        u_xxx of u_0 by central differences of the boundary callback (a start, not data: O(h^2) is ample)"""
+        if isinstance(initial_sol, str) and initial_sol == 'profile':
+            t0 = float(self.domain[0][0])
+            x = self.X_domain[:, 1]
+            h = 1e-3 * (float(self.domain[1][1]) - float(self.domain[1][0]))
+            u = {k: onp.asarray(eval_callback(self.get_bd, onp.full_like(x, t0), x + k * h), dtype=onp.float64) for k in (-2, -1, 0, 1, 2)}
+            return onp.concatenate((u[0], (u[1] - u[-1]) / (2 * h), (u[2] - 2 * u[1] + 2 * u[-1] - u[-2]) / (2 * h ** 3)))
+        return super()._initial(initial_sol, n)
+
+    def GN_method(self, max_iter=10, step_size=1, initial_sol='rdm', print_hist=True):
+        """initial_sol: 'rdm' (standard normal draw), 'profile' (the initial data held constant in time), or an ndarray with one value
+        per unknown: the iterate to start from."""
+        super().GN_method(max_iter, step_size, initial_sol, print_hist)
+
+    def _sol_vec(self, sol):
+        Nd = self.N_domain
+        v0, v2, v3 = sol[:Nd], sol[Nd:2 * Nd], sol[2 * Nd:]
+        return onp.concatenate((-self.delta * v3 + self.rhs_f - self.alpha * v0 * v2, v2, v3, v0, self.bdy_g), axis=0), v0
+
+    def _fields(self, X_test, which):
+        return get_context().extend_functionals_disp(self.kernel, self.kernel_parameter, X_test, self.X_domain, self.X_boundary,
+                                                     self._coeff(self._dL, self.sol_vec), which=which)
+
+    def extend_sol(self, X_test):
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = self._fields(X_test, ('value',)).download().reshape(-1)
+
+    def _derivative_fields(self, X_test):
+        return {'u': self._fields(X_test, self._deriv_names)}
+
+    def extend_derivatives(self, X_test):
+        """value, d1 = u_t, d2 = u_x and d2d2d2 = u_xxx of the GP solution at X_test (numpy arrays)"""
+        return super().extend_derivatives(X_test)
+
+    def PDE_residual(self, X_test):
+        """u_t + alpha u u_x + delta u_xxx - f at X_test from the derivatives of the GP solution: gpk_pde_residual(GPK_GN_BURGERS) with
+        (alpha, -delta) and u_xxx in the fourth row (f evaluated at X_test)"""
+        return super().PDE_residual(X_test)
+
+    def _posterior_unserved(self):
+        return 'KdV: gpk_assemble_cross has no rectangular evaluator for the dispersive layout yet'
 
 
 class _GradientUnknowns(object):

@@ -4,7 +4,7 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Quasilinear2d, Semilinear2d, Semilinear3d
+from .PDEs import Burgers, Eikonal, KdV, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Quasilinear2d, Semilinear2d, Semilinear3d
 from .quasilinear import QuasilinearEquation
 from .nonlinearity import GradientNonlinearity, Nonlinearity
 
@@ -132,6 +132,10 @@ _EQUATIONS = {
         lambda c, **k: Burgers(alpha=c.alpha, nu=c.nu, **k),
         lambda c: ['[Equation type] Burgers equation', '[Equation form] u_t+ alpha u u_x- nu u_xx=0'],
         lambda c: f'[Equation parameter] alpha = {c.alpha}, m = {c.nu}'),        # sic: the reference prints "m ="
+    'KdV': (
+        lambda c, **k: KdV(alpha=c.alpha, delta=c.delta, **k),
+        lambda c: ['[Equation type] Korteweg-de Vries equation (dispersive)', '[Equation form] u_t+ alpha u u_x+ delta u_xxx=f'],
+        lambda c: f'[Equation parameter] alpha = {c.alpha}, delta = {c.delta}'),
     'Eikonal': (
         lambda c, **k: Eikonal(eps=c.eps, **k),
         lambda c: ['[Equation type] Eikonal equation', '[Equation form] |grad u|^2 = f + eps*Delta u'],
