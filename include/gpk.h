@@ -143,7 +143,7 @@ int gpk_prof_read_pipeline(gpk_handle h, int* host_pipelined, double* host_syrk_
  * host_flops4 = {solve S = L^{-1}[A | F], updates inside the factorisation of Hb, the product Hb = S^T S, unused};
  * host_launches4 (may be NULL) = number of launches behind each figure.  The panel / substitution kernels are not counted. */
 int gpk_prof_read_flops(gpk_handle h, double* host_flops4, long* host_launches4);
-/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_jet2 / gpk_assemble_grad3d / gpk_assemble_disp call issued while the per-phase timing was on (HIP events on the
+/* Duration of the Gram evaluator launch of the LAST gpk_assemble / gpk_assemble3d / gpk_assemble_bc / gpk_assemble_op / gpk_assemble_op3d / gpk_assemble_hess / gpk_assemble_jet2 / gpk_assemble_grad3d / gpk_assemble_disp / gpk_assemble_evo call issued while the per-phase timing was on (HIP events on the
  * handle's stream around that launch alone; the point packing kernel and the host-side set-up stay outside).  Synchronises. */
 int gpk_prof_read_assembly(gpk_handle h, double* host_ms);
 
@@ -352,6 +352,35 @@ int gpk_assemble_disp(gpk_handle h, int kernel, const double* host_kparams, cons
 int gpk_extend_functionals_disp(gpk_handle h, int kernel, const double* host_kparams, const double* Xt, int Nt,
                                 const double* Xd, int Nd, const double* Xb, int Nb,
                                 const double* coeff, int fmask, double* out, int ldo);
+/* ---- Evolution layout: the Burgers layout with a general spatial operator in place of the second space derivative (DESIGN.md section K,
+ *      "Evolution equations: the general spatial operator"), for u_t + alpha u u_x + Q[u] = f with
+ *        Q = c2 d_x^2 + c3 d_x^3 + c4 d_x^4 + c5 d_x^5,   host_c4 = {c2, c3, c4, c5} (finite, not all zero: otherwise -9001)
+ *      -- Kuramoto-Sivashinsky (c2 = c4 = 1), Kawahara (c3, c5), KdV-Burgers (c2 = -nu, c3 = delta), Benney-Lin (all four).  No reference
+ *      call site.  Points are (t, x) rows.  Block 0 = d_t, block 1 = d_x, block 2 = Q, each on the Nd domain points; block 3 = delta on
+ *      the Nd domain points followed by c0 delta + c1 d_t + c2 d_x on the Nb boundary points, with (c0, c1, c2) = row b of bc (device,
+ *      (Nb,3) row-major, the format of gpk_assemble_bc; NULL = delta everywhere).  N = 4Nd+Nb, Theta N x N, ld >= N: gpk_potrf, gpk_potrs,
+ *      the GPK_GN_BURGERS system with p1 = -1, gpk_log_evidence and gpk_pde_residual(GPK_GN_BURGERS) with Q[u] in the fourth row apply to
+ *      it.  Theta is symmetric to the bit.  Kernels: Gaussian and anisotropic Gaussian (any other id: -9001).  host_kparams, Xd, Xb as
+ *      gpk_assemble.  Nugget as gpk_assemble_disp: adaptive = nugget * trace(block k) / trace(block 3) on the blocks 0..2, nugget on
+ *      block 3.  host_ratios3 (three doubles, may be NULL) = those ratios, with the values at d = 0
+ *        <d_t,d_t> = p1,   <d_x,d_x> = p2,   <delta,delta> = 1,   <B_b,B_b> = c0^2 + p1 c1^2 + p2 c2^2,
+ *        <Q,Q> = 3 c2^2 p2^2 + 15 c3^2 p2^3 + 105 c4^2 p2^4 + 945 c5^2 p2^5 - 30 c2 c4 p2^3 - 210 c3 c5 p2^4,
+ *      written for every nugget type (bc != NULL: the call reads bc back and synchronises the stream).  Any alignment of Theta / ld is
+ *      accepted (16-byte stores when base, ld, Nd and Nb allow; 8-byte stores otherwise, with the same values; nothing outside the
+ *      N x N view is written); the launch is timed like gpk_assemble's when the per-phase timing is on (gpk_prof_read_assembly).  Bad
+ *      arguments: -9001, named in gpk_last_error, before any launch. */
+int gpk_assemble_evo(gpk_handle h, int kernel, const double* host_kparams, const double* host_c4 /* c2..c5 */,
+                     const double* Xd, int Nd, const double* Xb, int Nb, const double* bc /* (Nb,3) device, NULL = delta */,
+                     double nugget, int nugget_type, double* Theta, int ld, double* host_ratios3);
+/* Value and derivatives of the extension on the evolution layout at test points Xt (Nt,2), matrix-free: coeff (4Nd+Nb) =
+ * Theta^{-1} sol_vec with the Theta of gpk_assemble_evo (the same host_c4 and bc).  fmask: a non-empty subset of GPK_FN_VALUE, GPK_FN_D1
+ * (u_t), GPK_FN_D2 (u_x), GPK_FN_D2D2 (u_xx) and GPK_FN_Q (Q[u]) (anything else, GPK_FN_D2D2D2 included: -9001); out is functional-major,
+ * row k (the k-th set bit of fmask, ascending) at out + k*ldo, ldo >= Nt; entries past Nt untouched.  Fixed reduction order (wave
+ * shuffles, then LDS, no atomics): a repeated call gives bit-identical output. */
+#define GPK_FN_Q 128          /* Q[u] = sum_k c_k d^k/dx2^k: gpk_extend_functionals_evo only (bit 7, after GPK_FN_D2D2D2) */
+int gpk_extend_functionals_evo(gpk_handle h, int kernel, const double* host_kparams, const double* host_c4,
+                               const double* Xt, int Nt, const double* Xd, int Nd, const double* Xb, int Nb, const double* bc,
+                               const double* coeff, int fmask, double* out, int ldo);
 /* ---- Operator and boundary functionals in three dimensions ("Operator and boundary functionals in three dimensions"):
  *      -psi[u] + alpha u^m = f on a box in R^3 with psi_i = c0 delta + sum_k b_k d_k + sum_{k<=l} a_kl d_k d_l at domain point i -- 3-D
  *      advection-diffusion-reaction, and with axis 3 as time psi = nu (d_1 d_1 + d_2 d_2) - d_3: u_t - nu Laplace_x u + alpha u^m = f in two

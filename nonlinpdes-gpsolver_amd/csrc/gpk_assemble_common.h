@@ -1,7 +1,8 @@
-// gpk_assemble_common.h -- what the eleven Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts and their
+// gpk_assemble_common.h -- what the twelve Gram-evaluator translation units share (gpk_assemble.hip: the reference layouts and their
 // Gaussian family, gpk_assemble_matern.hip: their Matern family, gpk_assemble_periodic.hip: their periodic kernel, gpk_assemble3d.hip,
 // gpk_assemble_bc.hip: Neumann / Robin, gpk_assemble_op.hip: variable-coefficient operator, gpk_assemble_op3d.hip: the operator and the
 // boundary functionals in three dimensions, gpk_assemble_hess.hip: the Hessian layout, gpk_assemble_jet2.hip: the 2-jet layout, gpk_assemble_disp.hip: the dispersive layout,
+// gpk_assemble_evo.hip: the evolution layout with the general spatial operator,
 // gpk_assemble_grad3d.hip: the gradient layout in three
 // dimensions, which shares gpk_assemble_op3.h with gpk_assemble_op3d.hip).  The kernels and the per-pair arithmetic that
 // differs between them (pair_coeff in its roundings, pair_coeff3, the tables of the operator) stay in those files -- the kernels of the
@@ -58,6 +59,23 @@ __host__ __device__ __forceinline__ void hermite_compensated(double p, double d,
     h[2] = (q2 - p) + q2e;
     h[3] = q * ((q2 - t) + (q2e - te));
     h[4] = __builtin_fma(q2, q2 - 6.0 * p, 3.0 * p * p);
+}
+
+// Orders 0..N-1, N up to 11 (evo: <Q,Q> with a fifth derivative reaches order ten).  h0..h4 are hermite_compensated's; from there the
+// three-term recurrence h_(n+1) = q h_n - n p h_(n-1), one fma per order.  Not Horner in q^2: the monomials of He_10 reach 6e5 where the
+// polynomial is 1e4 (s = sqrt(p) d near 2.5), and their roundings would be ~7 eps of the value at d = 0 after the Gaussian factor; the
+// terms of the recurrence are of the size of the polynomials themselves.  q is odd in d, so h_n(-d) = (-1)^n h_n(d) to the bit.
+template <int N>
+__host__ __device__ __forceinline__ void hermite_recurrence(double p, double d, double (&h)[N]) {
+#pragma clang fp contract(off)
+    static_assert(N >= 5 && N <= 11, "orders 4 .. 10");
+    double l[5];
+    hermite_compensated(p, d, l);
+#pragma unroll
+    for (int n = 0; n < 5; ++n) h[n] = l[n];
+    const double q = p * d;
+#pragma unroll
+    for (int n = 4; n + 1 < N; ++n) h[n + 1] = __builtin_fma(q, h[n], -(((double)n * p) * h[n - 1]));
 }
 
 // kappa of bc / op: exp(-(p1 d1^2 + p2 d2^2) / 2) with the one fma written out

@@ -100,6 +100,8 @@ PROTOTYPES = {
     'gpk_extend_functionals_hess': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
     'gpk_assemble_disp': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_disp': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),
+    'gpk_assemble_evo': (_i, [_vp, _i, _pd, _pd, _vp, _i, _vp, _i, _vp, _d, _i, _vp, _i, _pd]),
+    'gpk_extend_functionals_evo': (_i, [_vp, _i, _pd, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     'gpk_pde_residual_ma': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     'gpk_assemble_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _d, _i, _vp, _i, _pd]),
     'gpk_extend_functionals_jet2': (_i, [_vp, _i, _pd, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i]),

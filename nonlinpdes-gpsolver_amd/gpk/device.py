@@ -18,6 +18,7 @@ FUNCTIONAL = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'laplacian': 16}      # G
 FUNCTIONAL3D = {'value': 1, 'd1': 2, 'd2': 4, 'laplacian': 16, 'd3': 32}          # bits accepted by gpk_extend_functionals3d (GPK_FN_D3 = 32)
 FUNCTIONAL_OP = {'value': 1, 'd1': 2, 'd2': 4, 'd11': 8, 'd12': 16, 'd22': 32}   # GPK_OPFN_* bits of gpk_extend_functionals_op
 FUNCTIONAL_DISP = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'd2d2d2': 64}         # bits accepted by gpk_extend_functionals_disp (GPK_FN_D2D2D2 = 64)
+FUNCTIONAL_EVO = {'value': 1, 'd1': 2, 'd2': 4, 'd2d2': 8, 'q': 128}                # bits accepted by gpk_extend_functionals_evo (GPK_FN_Q = 128)
 OP3_NAMES = ('value', 'd1', 'd2', 'd3', 'd11', 'd12', 'd13', 'd22', 'd23', 'd33')   # the monomials of op3, in its order
 FUNCTIONAL_OP3 = {n: 1 << k for k, n in enumerate(OP3_NAMES)}                    # GPK_OP3FN_* bits of gpk_extend_functionals_op3d
 DINV_BLOCK = int(__import__('os').environ.get('GPK_DINV_BLOCK', '0'))   # rows per inverted diagonal block of a factor (256 .. 2048); 0 = by size
@@ -556,6 +557,38 @@ class Context:
         Theta of assemble_disp."""
         return self._extend_functionals('extend_functionals_disp', FUNCTIONAL_DISP, 2, self.lib.gpk_extend_functionals_disp, (),
                                         kernel, kernel_parameter, Xt, Xd, Xb, None, coeff, which)
+
+    # ---- evolution layout: d_t, d_x, Q = sum c_k d_x^k, delta / boundary functionals on (t, x) points (gpk_assemble_evo, gpk_extend_functionals_evo) ----
+    @staticmethod
+    def _operator_c4(coeffs):
+        c = np.asarray(coeffs, dtype=np.float64).ravel()
+        if c.shape != (4,):
+            raise ValueError(f'coeffs must be (c2, c3, c4, c5), got {coeffs!r}')
+        return (C.c_double * 4)(*c)
+
+    def _evo_entry(self, entry, coeffs, lead):
+        """the library entry with host_c4 in its place behind host_kparams, in the argument order _assemble_blocks / _extend_functionals use"""
+        c4 = self._operator_c4(coeffs)
+
+        def call(h, *args):
+            return entry(h, *args[:lead], c4, *args[lead:])
+        call.__name__ = entry.__name__
+        return call
+
+    def assemble_evo(self, kernel, kernel_parameter, coeffs, Xd, Xb, bc=None, nugget=0.0, nugget_type='none', out=None):
+        """Gram matrix of the evolution layout (blocks d_t, d_x, Q = c2 d_x^2 + c3 d_x^3 + c4 d_x^4 + c5 d_x^5 on Xd with coeffs =
+        (c2, c3, c4, c5); block 3: delta on Xd, bc[b] = (c0, c1, c2) -> c0 delta + c1 d_t + c2 d_x at boundary point b, bc = None: delta;
+        points (t, x)): (DeviceArray N x N with N = 4 Nd + Nb, [trace(block k) / trace(block 3) for k = 0, 1, 2]).  out: a DeviceArray
+        to write into (any leading dimension >= N)."""
+        return self._assemble_blocks(self._evo_entry(self.lib.gpk_assemble_evo, coeffs, 2), 2, kernel, kernel_parameter, Xd, Xb,
+                                     lambda Nd, Nb: (self._boundary_coeffs(bc, Nb),), nugget, nugget_type, out, rows=4, nratios=3)
+
+    def extend_functionals_evo(self, kernel, kernel_parameter, coeffs, Xt, Xd, Xb, bc, coeff, which=('value', 'd1', 'd2', 'd2d2', 'q')):
+        """u, u_t, u_x, u_xx, Q[u] of the extension on the evolution layout at Xt (gpk_extend_functionals_evo): a (len(which), Nt)
+        DeviceArray, row k = functional which[k] (names: FUNCTIONAL_EVO).  coeff = Theta^{-1} sol_vec (4 Nd + Nb values) with the
+        Theta of assemble_evo (the same coeffs and bc)."""
+        return self._extend_functionals('extend_functionals_evo', FUNCTIONAL_EVO, 2, self._evo_entry(self.lib.gpk_extend_functionals_evo, coeffs, 2),
+                                        (), kernel, kernel_parameter, Xt, Xd, Xb, lambda Nd, Nb: (self._boundary_coeffs(bc, Nb),), coeff, which)
 
     def _on_device(self, a, fields=False):
         """a DeviceArray as it is; a host array uploaded as (rows, Nt) fields or as one vector"""

@@ -1,8 +1,8 @@
 """Equation classes with the reference's public API (src/PDEs.py): Nonlinear_elliptic2d, Burgers, Eikonal -- and Nonlinear_elliptic3d, the
 same elliptic equation on a box in three space dimensions, and Semilinear2d, the semilinear equation with a gradient-dependent
 nonlinearity on the Eikonal layout, and Semilinear3d, its counterpart in three dimensions and in time on the gradient layout, and
-MongeAmpere2d and Quasilinear2d on the Hessian and the 2-jet layout, and KdV, the Burgers system on the dispersive layout (none has a
-counterpart in the reference).  The classes stand on _GPEquation; the two
+MongeAmpere2d and Quasilinear2d on the Hessian and the 2-jet layout, and KdV and Evolution1d, the Burgers system on the dispersive
+layout and on the evolution layout with a general spatial operator (none has a counterpart in the reference).  The classes stand on _GPEquation; the two
 elliptic ones are siblings on _EllipticEquation, which holds everything they share, and each says in its class attributes and in
 _family() what sets it apart.
 
@@ -1047,6 +1047,122 @@ class KdV(Burgers):
 
     def _posterior_unserved(self):
         return 'KdV: gpk_assemble_cross has no rectangular evaluator for the dispersive layout yet'
+
+
+class Evolution1d(Burgers):
+    """u_t + alpha u u_x + Q[u] = f on (t,x) in a rectangle with Q = c2 d_x^2 + c3 d_x^3 + c4 d_x^4 + c5 d_x^5 (constant coefficients):
+    Kuramoto-Sivashinsky (c2 = c4 = 1), Kawahara (c3, c5), KdV-Burgers (c2 = -nu, c3 = delta), Benney-Lin (all four); viscous Burgers
+    and KdV are special cases.  No counterpart in the reference.  It is the Burgers system with the row functional d_x^2 exchanged for
+    Q: rows [u_t; u_x; Q u; u] per domain point, then the boundary functionals (the evolution Gram layout, gpk_assemble_evo, Gaussian
+    kernels only), unknowns [u | u_x | Q u], and GPK_GN_BURGERS with nu = -1 is the Gauss-Newton system -- loss, step, line search, the
+    structured modes (GPK_STRUCTURED) and log_evidence are the base class's.
+
+    coeffs = (c2, c3, c4, c5), or equation = ('kuramoto_sivashinsky',) | ('kawahara', a, b): a u_xxx + b u_xxxxx |
+    ('kdv_burgers', nu, delta): -nu u_xx + delta u_xxx | ('benney_lin', c2, c3, c4, c5).
+    bc = 'dirichlet': u = bdy on every boundary point.  bc = 'clamped' (two conditions per wall, what an operator of fourth order
+    takes): every boundary point with x at either end of the domain appears twice, behind the given points a second copy that carries
+    u_x = bdy_x(t, x); the points of the initial line keep u alone.  set_boundary_operator(rows) sets any (N_boundary, 3) array of rows
+    (c0, c1, c2): c0 u + c1 u_t + c2 u_x = bdy_g[b].
+    posterior_variance / posterior_covariance / posterior_sample raise NotImplementedError (the layout has no rectangular cross
+    evaluator)."""
+    _layout = 'Evolution'                                     # (no GPK_LAYOUT_* id: the evaluator is a call of its own)
+    _system = 'Burgers'
+    _deriv_names = ('value', 'd1', 'd2', 'q')                 # u, u_t, u_x, Q[u]: the rows gpk_pde_residual(GPK_GN_BURGERS) reads
+    _equations = {'kuramoto_sivashinsky': (0, lambda: (1.0, 0.0, 1.0, 0.0)), 'kawahara': (2, lambda a, b: (0.0, a, 0.0, b)),
+                  'kdv_burgers': (2, lambda nu, delta: (-nu, delta, 0.0, 0.0)), 'benney_lin': (4, lambda *c: c)}
+
+    def __init__(self, alpha=1.0, coeffs=None, equation=None, bdy=None, rhs=None, domain=onp.array([[0, 1], [-1, 1]]), bc='dirichlet',
+                 bdy_x=None):
+        super().__init__(alpha=alpha, nu=-1.0, bdy=bdy, rhs=rhs, domain=domain)
+        if (coeffs is None) == (equation is None):
+            raise ValueError('Evolution1d: give coeffs=(c2, c3, c4, c5) or equation=(name, ...), one of the two')
+        if equation is not None:
+            name, args = equation[0], tuple(float(v) for v in equation[1:])
+            if name not in self._equations or len(args) != self._equations[name][0]:
+                raise ValueError(f'Evolution1d: equation {equation!r}: one of ' + ', '.join(
+                    f'({n!r}' + ', ..' * k + ')' for n, (k, _) in self._equations.items()))
+            coeffs = self._equations[name][1](*args)
+        c = onp.asarray(coeffs, dtype=onp.float64).ravel()
+        if c.shape != (4,) or not onp.all(onp.isfinite(c)) or not onp.any(c != 0.0):
+            raise ValueError(f'Evolution1d: coeffs must be four finite numbers (c2, c3, c4, c5), not all zero, got {coeffs!r}')
+        if bc not in ('dirichlet', 'clamped'):
+            raise ValueError(f"Evolution1d: bc must be 'dirichlet' or 'clamped', got {bc!r}")
+        if bc == 'clamped' and bdy_x is None:
+            raise ValueError("Evolution1d: bc='clamped' needs bdy_x(t, x), the data of u_x on the walls")
+        self.coeffs = tuple(float(v) for v in c)
+        self.bc = bc
+        self.bdy_x = bdy_x
+        self.boundary_coeffs = None
+
+    def _gn_params(self):
+        return float(self.alpha), -1.0, 0.0
+
+    def _set_points(self, X_domain, X_boundary):
+        X_boundary = self._pts(X_boundary)
+        if self.bc != 'clamped':
+            super()._set_points(X_domain, X_boundary)
+            self.boundary_coeffs = None                       # a custom operator belongs to the points it was set for
+            return
+        lo, hi = float(self.domain[1][0]), float(self.domain[1][1])
+        wall = onp.flatnonzero((X_boundary[:, 1] == lo) | (X_boundary[:, 1] == hi))
+        n = X_boundary.shape[0]
+        super()._set_points(X_domain, onp.concatenate([X_boundary, X_boundary[wall]]))
+        self.wall_points = wall
+        rows = onp.zeros((n + wall.size, 3))
+        rows[:n, 0] = 1.0
+        rows[n:, 2] = 1.0
+        self.boundary_coeffs = rows
+        gx = eval_callback(self.bdy_x, X_boundary[wall, 0], X_boundary[wall, 1])
+        self.bdy_g = onp.concatenate((onp.asarray(self.bdy_g)[:n], onp.asarray(gx, dtype=onp.float64).reshape(-1)))
+
+    def set_boundary_operator(self, coeffs):
+        """Row b of coeffs (N_boundary, 3) = (c0, c1, c2): the condition at boundary point b reads c0 u + c1 u_t + c2 u_x = bdy_g[b]
+        (bdy_g stays as it is: set it to the data of these conditions).  Call after the points are set; dropped when they change.
+        Discards the Gram matrix and everything derived from it."""
+        coeffs = onp.array(coeffs, dtype=onp.float64)
+        if coeffs.shape != (self.N_boundary, 3):
+            raise ValueError(f'coeffs must have shape ({self.N_boundary}, 3), got {coeffs.shape}')
+        self.boundary_coeffs = coeffs
+        self._drop_device_state()
+
+    def Gram_matrix(self, kernel='anisotropic_Gaussian', kernel_parameter=[1 / 3, 1 / 5], nugget=1e-8, nugget_type='adaptive'):
+        """kernel: Gaussian or anisotropic_Gaussian (the Matern family and the periodic kernel are refused: the evolution layout has no
+        evaluator for them)"""
+        require_gaussian_family(kernel, 'Evolution1d.Gram_matrix')
+        super().Gram_matrix(kernel, kernel_parameter, nugget, nugget_type)
+
+    def _evaluate_gram(self, ctx, kernel, kernel_parameter, nugget, nugget_type):
+        return ctx.assemble_evo(kernel, kernel_parameter, self.coeffs, self.X_domain, self.X_boundary, self.boundary_coeffs, nugget, nugget_type)
+
+    def _sol_vec(self, sol):
+        Nd = self.N_domain
+        v0, v2, v3 = sol[:Nd], sol[Nd:2 * Nd], sol[2 * Nd:]
+        return onp.concatenate((-v3 + self.rhs_f - self.alpha * v0 * v2, v2, v3, v0, self.bdy_g), axis=0), v0
+
+    def _fields(self, X_test, which):
+        return get_context().extend_functionals_evo(self.kernel, self.kernel_parameter, self.coeffs, X_test, self.X_domain, self.X_boundary,
+                                                    self.boundary_coeffs, self._coeff(self._dL, self.sol_vec), which=which)
+
+    def extend_sol(self, X_test):
+        X_test = onp.asarray(X_test, dtype=onp.float64)
+        self.X_test = X_test
+        self.N_test = X_test.shape[0]
+        self.extended_sol = self._fields(X_test, ('value',)).download().reshape(-1)
+
+    def _derivative_fields(self, X_test):
+        return {'u': self._fields(X_test, self._deriv_names)}
+
+    def extend_derivatives(self, X_test):
+        """value, d1 = u_t, d2 = u_x and q = Q[u] of the GP solution at X_test (numpy arrays)"""
+        return super().extend_derivatives(X_test)
+
+    def PDE_residual(self, X_test):
+        """u_t + alpha u u_x + Q[u] - f at X_test from the derivatives of the GP solution: gpk_pde_residual(GPK_GN_BURGERS) with
+        (alpha, -1) and Q[u] in the fourth row (f evaluated at X_test)"""
+        return super().PDE_residual(X_test)
+
+    def _posterior_unserved(self):
+        return 'Evolution1d: gpk_assemble_cross has no rectangular evaluator for the evolution layout'
 
 
 class _GradientUnknowns(object):

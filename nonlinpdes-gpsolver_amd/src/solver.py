@@ -4,7 +4,7 @@ import numpy as onp
 
 from ._runtime import get_context
 from .InverseProblems import Darcy_flow2d
-from .PDEs import Burgers, Eikonal, KdV, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Quasilinear2d, Semilinear2d, Semilinear3d
+from .PDEs import Burgers, Eikonal, Evolution1d, KdV, MongeAmpere2d, Nonlinear_elliptic2d, Nonlinear_elliptic3d, Quasilinear2d, Semilinear2d, Semilinear3d
 from .quasilinear import QuasilinearEquation
 from .nonlinearity import GradientNonlinearity, Nonlinearity
 
@@ -136,6 +136,14 @@ _EQUATIONS = {
         lambda c, **k: KdV(alpha=c.alpha, delta=c.delta, **k),
         lambda c: ['[Equation type] Korteweg-de Vries equation (dispersive)', '[Equation form] u_t+ alpha u u_x+ delta u_xxx=f'],
         lambda c: f'[Equation parameter] alpha = {c.alpha}, delta = {c.delta}'),
+    'Evolution1d': (
+        # cfg: alpha; equation (name, ...) or coeffs (c2, c3, c4, c5); bc 'dirichlet' | 'clamped' and, for 'clamped', bdy_x: the callable u_x(t, x)
+        lambda c, **k: Evolution1d(alpha=c.alpha, coeffs=getattr(c, 'coeffs', None), equation=getattr(c, 'equation', None),
+                                   bc=getattr(c, 'bc', 'dirichlet'), bdy_x=getattr(c, 'bdy_x', None), **k),
+        lambda c: ['[Equation type] evolution equation with a general spatial operator',
+                   '[Equation form] u_t+ alpha u u_x+ c2 u_xx+ c3 u_xxx+ c4 u_xxxx+ c5 u_xxxxx=f'],
+        lambda c: f"[Equation parameter] alpha = {c.alpha}, " + (f"coeffs = {tuple(c.coeffs)}" if getattr(c, 'coeffs', None) is not None
+                                                                  else f"equation = {tuple(c.equation)}") + f", bc = {getattr(c, 'bc', 'dirichlet')}"),
     'Eikonal': (
         lambda c, **k: Eikonal(eps=c.eps, **k),
         lambda c: ['[Equation type] Eikonal equation', '[Equation form] |grad u|^2 = f + eps*Delta u'],
